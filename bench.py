@@ -13,6 +13,10 @@ GPU (weak scaling: the ladder has 128*N chains, block-partitioned over the ranks
 `--config 3|4|5` selects the other GPU configs of BASELINE.json (per-GPU share of the ladder,
 table CONFIGS below); the default line the driver records stays config 2.
 Prints ONE JSON line on rank 0.
+A plain run sets up (the device calibration included), warms up, times the K steps and prints the line;
+`--full` adds what the headline figure does not need: the CPU baseline (`cpu_baseline`, --cpu-seconds).
+`--dump-outputs DIR` writes what the timed path handed back after its last step (the sample rows of its
+last launch and the ladder state) as DIR/<name>.npy in float64, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -27,6 +31,7 @@ import numpy as np
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VALU_PEAK_TF = 78.6  # fp64 vector peak
+OUTPUTS_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
 
 # BASELINE.json configs as one GPU sees them: workload, chains per GPU, data points, n_swap
 # (0 = the reference's rule 2000/n_beta of the per-GPU ladder; ladders beyond 2000 chains need an
@@ -68,7 +73,11 @@ def parse():
     ap.add_argument("--lds", type=int, default=0, help="0 choose, 1 stage the data vector in LDS, 2 read it through L2")
     ap.add_argument("--no-samples", action="store_true", help="do not write per-step sample rows")
     ap.add_argument("--no-calibrate", action="store_true", help="skip the device calibration before the timed steps")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg; 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the cpu_baseline leg (--cpu-seconds)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (--full); 0 = skip")
     ap.add_argument("--calib-dump", default=None, help="write the calibration's per-chain status and sweep counts (JSON)")
     ap.add_argument("--maps-dump", default=None, help="debug: write /proc/self/maps there before exiting (to assign the "
                                                       "addresses of a native stack trace to libraries)")
@@ -81,6 +90,8 @@ def parse():
                     help="one rank without torch in the process: sample rows in a buffer of the engine's own, one HIP "
                          "runtime (what the profile scripts run: tools/profile_config.sh)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     for k, v in CONFIGS[a.config].items():
         if getattr(a, k, None) is None:
             setattr(a, k, v)
@@ -178,6 +189,27 @@ def cpu_baseline(w, st_template, n_swap, seconds):
                       % (rounds, n_swap, st_template.n_chain, dt)}
 
 
+def write_outputs(d, arrays, max_bytes=OUTPUTS_MAX_BYTES):
+    """arrays as d/<name>.npy in float64.  The smaller arrays are written whole; an array that would take the
+    total over max_bytes is replaced by a fixed, seeded sample of its rows (all axes but the last flattened), in
+    their original order, and the flat indices of the rows kept go to d/<name>_rows.npy."""
+    header = 128   # bytes of an .npy header (format 1.0, a shape of a few axes)
+    os.makedirs(d, exist_ok=True)
+    left = max_bytes
+    for name in sorted(arrays, key=lambda k: np.asarray(arrays[k]).size):
+        x = np.asarray(arrays[name], dtype=np.float64)
+        if x.nbytes + header > left:
+            rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(-1, 1)
+            k = max(1, min(rows.shape[0], (left - 2 * header) // (8 * rows.shape[1] + 8)))
+            idx = np.sort(np.random.RandomState(0).choice(rows.shape[0], k, replace=False))
+            np.save(os.path.join(d, name + "_rows.npy"), idx.astype(np.float64))
+            left -= idx.nbytes + header
+            x = rows[idx]
+        np.save(os.path.join(d, name + ".npy"), x)
+        left -= x.nbytes + header
+    return d
+
+
 def kernel_sources_sha1():
     """sha1 over the kernel sources (csrc/*.h and the kernels' translation unit apemost_model.hip -- not
     apemost_hip.hip, the host side of the ABI, whose changes leave every kernel's code object what it was):
@@ -249,7 +281,7 @@ def main():
         import torch.distributed as dist
     from apemost_amd import capi, workloads as wl
     from apemost_amd.sampler import HipSampler, get_chain_beta
-    from apemost_amd.state import LadderState
+    from apemost_amd.state import ALL_FIELDS, LadderState
     from apemost_amd.distributed import HipShardEngine, ShardedLadder
 
     if a.same_device:
@@ -365,6 +397,18 @@ def main():
         per_rank = np.array([e.cpu().numpy() for e in every])
 
     acc1 = s.get_state()
+    if a.dump_outputs:
+        # what a caller of the timed path holds after its last step: the sample rows of the step's last launch
+        # (every launch writes the same buffer) and the ladder state, the closing swap attempt still pending
+        outputs = {f: getattr(acc1, f) for f in ALL_FIELDS}
+        if samples is not None and torch is not None:
+            outputs["samples"] = samples.cpu().numpy()
+        elif samples is not None:
+            rows = np.empty((R, n_swap, n_local, w.n_par + 2))
+            capi.check(s.L.apemost_hip_samples_read(s._h, C.c_void_p(samples.data_ptr()), R * n_swap,
+                                                    rows.ctypes.data_as(C.POINTER(C.c_double))))
+            outputs["samples"] = rows
+        write_outputs(a.dump_outputs if world == 1 else os.path.join(a.dump_outputs, "rank%d" % rank), outputs)
     d_acc = (acc1.accept - acc0.accept).astype(np.float64)
     d_rej = (acc1.reject - acc0.reject).astype(np.float64)
     acceptance = float(np.mean(d_acc / np.maximum(d_acc + d_rej, 1)))
@@ -483,7 +527,7 @@ def main():
             pass
         out["calibration"] = calibration
     if rank == 0:
-        if world == 1 and a.cpu_seconds > 0:
+        if a.full and world == 1 and a.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(w, acc0, n_swap, a.cpu_seconds)
         else:
             out["cpu_baseline"] = None

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -68,3 +70,38 @@ def test_spawned_ranks_end_with_the_failing_ranks_code():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device",
                           "--cpu-seconds", "0"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert out.returncode == 7 and not out.stdout.strip()
+
+
+def test_plain_run_options(monkeypatch):
+    """a plain run leaves the CPU baseline to --full and writes no outputs; --steps is the number of timed steps"""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = b.parse()
+    assert a.steps == 3 and a.warmup == 1 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
+
+
+def test_outputs_are_float64_and_a_large_one_is_a_seeded_sample(tmp_path):
+    import numpy as np
+    b = _bench()
+    small = {"beta": np.linspace(0, 1, 8), "accept": np.arange(8, dtype=np.uint64)}
+    b.write_outputs(str(tmp_path / "a"), dict(small, samples=np.arange(60.0).reshape(2, 5, 6)))
+    assert sorted(os.listdir(tmp_path / "a")) == ["accept.npy", "beta.npy", "samples.npy"]
+    for name in ("accept", "beta"):
+        x = np.load(str(tmp_path / "a" / (name + ".npy")))
+        assert x.dtype == np.float64 and np.array_equal(x, small[name])
+    assert np.array_equal(np.load(str(tmp_path / "a" / "samples.npy")), np.arange(60.0).reshape(2, 5, 6))
+    big = np.random.RandomState(1).normal(size=(50, 40, 6))
+    for d in ("b", "c"):
+        b.write_outputs(str(tmp_path / d), dict(small, samples=big), max_bytes=4096)
+        total = sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(tmp_path / d))
+        assert total <= 4096
+    rows = np.load(str(tmp_path / "b" / "samples_rows.npy")).astype(np.int64)
+    got = np.load(str(tmp_path / "b" / "samples.npy"))
+    assert len(rows) > 10 and np.all(np.diff(rows) > 0) and np.array_equal(got, big.reshape(-1, 6)[rows])
+    assert np.array_equal(got, np.load(str(tmp_path / "c" / "samples.npy")))
