@@ -315,7 +315,8 @@ struct apemost_hip_sampler {
     hipEvent_t ev_copy;
     u64 *h_word;             // pinned copy of the launch error word, refreshed by every async read
     bool one_barrier;    // stepping launches use pt_round_ob_kernel
-    bool ob_helper;      // ... in its form with a helper wavefront (see ob_wants_helper)
+    bool ob_helper;      // ... in its form with a helper wavefront (see ob_wants_helper), where the betas allow it:
+    bool betas_split_ok; // every beta on the device is > 0 with a finite 1/beta (betas_allow_split; true until betas arrive)
     int cus;             // compute units of the device
     int kmodel;          // template argument of this sampler's kernels: cfg.model, + kVariantModel when a
                          // non-default proposal law or swap schedule is asked for (pt_device.h)
@@ -736,6 +737,7 @@ static int create_body(apemost_hip_sampler *s) {
         s->one_barrier = has_one_barrier(s->waves) && !(cfg->flags & APEMOST_HIP_FLAG_TWO_BARRIER_STEP) && !s->user.module;
         s->cus = prop.multiProcessorCount;
         s->ob_helper = s->one_barrier && ob_wants_helper(s, cfg->n_chains);
+        s->betas_split_ok = true;
         int b_lds = 0, b_plain = 0;
         if (s->user.module) {
             HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&b_plain, s->user.round[s->waves], s->waves * kWave, s->lds_fixed_bytes));
@@ -961,7 +963,7 @@ extern "C" int apemost_hip_launch_policy(apemost_hip_sampler *s, int32_t *one_ba
                                          int32_t *max_rounds) {
     CHECK_S(s);
     if (one_barrier)
-        *one_barrier = s->one_barrier ? (s->ob_helper ? 2 : 1) : 0;
+        *one_barrier = s->one_barrier ? (s->ob_helper && s->betas_split_ok ? 2 : 1) : 0;
     if (cooperative)
         *cooperative = (s->cooperative && s->resident_ok && !s->handoff_failed) ? 1 : 0;
     if (max_rounds)
@@ -1062,12 +1064,32 @@ static int check_box(apemost_hip_sampler *s, const apemost_hip_state_view *v) {
     return APEMOST_HIP_OK;
 }
 
+// The helper wavefront's threshold S_max = X - Y (pt_onebarrier.h, ObThreshold<PULSE>) holds both halves scaled by
+// 1/beta: where that is not finite (beta = 0, or a beta below ~5.6e-309) X and Y are infinities of the same sign
+// whenever prior_new and T = prob + ln U are, their difference is NaN and the step is rejected whatever it
+// proposed.  The owner's form (prior_new - T) / beta - p1 gives the right infinity.  Such a ladder (BETA_0 = 0: the hottest chain at beta 0)
+// is a legitimate configuration of the reference, so it is not refused: its launches take the eight-wave form.
+static bool betas_allow_split(const double *beta, int n) {
+    for (int i = 0; i < n; i++)
+        if (!(beta[i] > 0 && std::isfinite(1.0 / beta[i])))
+            return false;
+    return true;
+}
+
 extern "C" int apemost_hip_set_state(apemost_hip_sampler *s, const apemost_hip_state_view *v) {
     CHECK_S(s);
     if (!v)
         return fail(APEMOST_HIP_ERR_INVALID, "state view is NULL");
-    const int rc = check_box(s, v);
-    return rc ? rc : xfer_state(s, v, true);
+    int rc = check_box(s, v);
+    if (rc)
+        return rc;
+    // (a transfer that fails half way may have left the new betas on the device: only a good one clears them)
+    const bool split_ok = v->beta ? betas_allow_split(v->beta, s->cfg.n_chains) : s->betas_split_ok;
+    s->betas_split_ok = s->betas_split_ok && split_ok;
+    if ((rc = xfer_state(s, v, true)))
+        return rc;
+    s->betas_split_ok = split_ok;
+    return APEMOST_HIP_OK;
 }
 extern "C" int apemost_hip_get_state(apemost_hip_sampler *s, const apemost_hip_state_view *v) {
     int rc = xfer_state(s, v, false);
@@ -1154,7 +1176,8 @@ static int launch_shape(apemost_hip_sampler *s, KernelKind kind, int grid, const
 // likelihood evaluations) reads it through L2 instead of copying it into LDS first
 static int launch(apemost_hip_sampler *s, KernelKind kind, int grid, const void *args, bool stage_data = true,
                   bool coop = false) {
-    return launch_shape(s, kind, grid, args, s->waves, s->lds_data && stage_data, coop, kind == K_ROUND_OB && s->ob_helper);
+    return launch_shape(s, kind, grid, args, s->waves, s->lds_data && stage_data, coop,
+                        kind == K_ROUND_OB && s->ob_helper && s->betas_split_ok);
 }
 
 extern "C" int apemost_hip_calc_model(apemost_hip_sampler *s, int32_t first, int32_t count) {
@@ -1738,7 +1761,7 @@ static CalibShape calib_shape(const apemost_hip_sampler *s, int n_active) {
         g.waves = s->waves; // (development builds hold only some shapes)
     g.one_barrier = has_one_barrier(g.waves) && s->kmodel < kVariantModel && !(s->cfg.flags & APEMOST_HIP_FLAG_TWO_BARRIER_STEP) &&
                     !s->user.module;
-    g.helper = g.one_barrier && ob_wants_helper(s, n_active);
+    g.helper = g.one_barrier && ob_wants_helper(s, n_active) && s->betas_split_ok;
     const size_t bytes = g.one_barrier ? ob_lds_bytes(s, true) : classic_lds_bytes(s, g.waves, true);
     g.lds_data = !s->user.module && bytes <= 160 * 1024 - 1024 && c.lds_policy != 2 && (c.lds_policy == 1 || choose_lds(c, bytes));
     // A segment of about a quarter of a second: likelihood evaluations a chain gets through in that

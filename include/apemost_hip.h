@@ -222,7 +222,9 @@ int apemost_hip_synchronize(apemost_hip_sampler *s);
 int apemost_hip_stream(apemost_hip_sampler *s, void **stream);
 int apemost_hip_waves_per_chain(apemost_hip_sampler *s, int *waves, int *data_in_lds);
 /* how this sampler's stepping launches are issued as things stand: the one-barrier kernel (1; 2: in its form
- * with a helper wavefront, the models with a prior on ladders of at most one chain per CU) or the
+ * with a helper wavefront, the models with a prior on ladders of at most one chain per CU whose betas are all
+ * > 0 with a finite 1/beta -- so it depends on the state: a set_state whose betas include 0 or one below
+ * ~5.6e-309 turns it to 1, one without them back to 2; before any betas are set it assumes they allow it) or the
  * two-phase one (0), multi-round launches through hipLaunchCooperativeKernel or plain, and how many
  * rounds one launch may hold (1: the grid is not resident, a cooperative launch was refused, or a
  * hand-off timed out) */

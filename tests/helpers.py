@@ -6,16 +6,24 @@ from apemost_amd.state import LadderState, ALL_FIELDS
 from oracle import oracle as orc
 
 
-def make_pair(w, n_chain, beta_0=0.02, seed=1234, chain_offset=0, n_global=None, init_prob=False):
-    """A calibrated-looking ladder: chebyshev betas, steps = step0 * beta^-1/2 (the
-    SKIP_CALIBRATE_ALLCHAINS prediction, src/parallel_tempering.c:190-196), identical in the
-    device mirror and the oracle."""
+def make_pair(w, n_chain, beta_0=0.02, seed=1234, chain_offset=0, n_global=None, init_prob=False,
+              ladder_kind=orc.LADDER_CHEBYSHEV_BETA, betas=None):
+    """A calibrated-looking ladder: betas of `ladder_kind` (chebyshev by default), steps = step0 *
+    beta^-1/2 (the SKIP_CALIBRATE_ALLCHAINS prediction, src/parallel_tempering.c:190-196), capped at
+    the prior range, identical in the device mirror and the oracle.  `betas` ({local chain: beta})
+    overrides chosen chains' betas; a beta of 0 gets the capped step (beta^-1/2 is infinite)."""
     n_global = n_global or n_chain
     st = LadderState.from_params(n_chain, w.start, w.pmin, w.pmax, w.step * 0.3)
     for i in range(n_chain):
-        b = orc.get_chain_beta(orc.LADDER_CHEBYSHEV_BETA, chain_offset + i, n_global, beta_0)
+        b = orc.get_chain_beta(ladder_kind, chain_offset + i, n_global, beta_0)
+        if betas and i in betas:
+            b = float(betas[i])
         st.beta[i] = b
-        st.step[i] = np.minimum(st.step[i] * b ** -0.5, (w.pmax - w.pmin))
+        f = b ** -0.5 if b > 0 else np.inf
+        if np.isfinite(f):
+            st.step[i] = np.minimum(st.step[i] * f, (w.pmax - w.pmin))
+        else:
+            st.step[i] = w.pmax - w.pmin
     lad = orc.Ladder(w.model, n_chain, w.n_par, w.data, chain_offset=chain_offset)
     to_oracle(st, lad)
     if init_prob:
