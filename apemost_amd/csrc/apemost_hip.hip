@@ -303,11 +303,13 @@ struct apemost_hip_sampler {
     } cal;
     unsigned big_lds_set; // bit w: the LDS opt-in of the w-wave kernels has been made
     // APEMOST_MODEL_USER: the kernels of the user's likelihood, compiled by hiprtc at create time
-    // (indexed by the waves per chain of the two-phase kernels: 1, 2, 4, 8 -- a user likelihood is an
-    // arbitrary function of the data sum, so the one-barrier kernels' threshold form is not for it)
+    // (indexed by the waves per chain of the two-phase kernels: 1, 2, 4, 8; with
+    // APEMOST_HIP_FLAG_USER_ONE_BARRIER also the one-barrier kernels of 4 and 8 likelihood waves, which decide
+    // through the user's finish() instead of the built-in models' threshold form)
     struct {
         hipModule_t module;
         hipFunction_t round[9], calibrate[9], calc_model[9], loglike[9];
+        hipFunction_t round_ob[9], calibrate_ob[9]; // (calibrate_ob: not for the variant instantiations)
     } user;
     double *edge_out, *edge_in;  // edge records for in-process shard exchanges (created on first use)
     hipEvent_t ev_exported, ev_imported;
@@ -374,6 +376,7 @@ template <bool LDS>
 static hipError_t round_occupancy(int model, int waves, bool producers, bool one_barrier, bool helper, size_t lds_bytes, int *blocks);
 static size_t ob_lds_bytes(const apemost_hip_sampler *s, bool lds_data);
 static bool ob_wants_helper(const apemost_hip_sampler *s, int n_chains);
+static bool user_may_ob(const apemost_hip_sampler *s);
 
 template <class T>
 static int dev_alloc(apemost_hip_sampler *s, T **p, size_t count) {
@@ -549,10 +552,13 @@ static void source_dirs(std::string &csrc, std::string &inc) {
 namespace {
 constexpr int kUserShapes = 4;
 constexpr int kUserWaves[kUserShapes] = {1, 2, 4, 8};
+constexpr int kUserObShapes = 2; // APEMOST_HIP_FLAG_USER_ONE_BARRIER: likelihood waves of the one-barrier kernels
+constexpr int kUserObWaves[kUserObShapes] = {4, 8};
 struct UserModelCode {
     std::string key;
     std::vector<char> code;
     std::string lowered[4 * kUserShapes];
+    std::string lowered_ob[2 * kUserObShapes]; // round, calibration ("": not compiled)
     double compile_seconds;
 };
 std::vector<UserModelCode> g_user_models;
@@ -580,6 +586,13 @@ static int user_model_load(apemost_hip_sampler *s, const UserModelCode &m) {
         HIP_TRY(hipModuleGetFunction(&s->user.calibrate[w], s->user.module, m.lowered[4 * k + 1].c_str()));
         HIP_TRY(hipModuleGetFunction(&s->user.calc_model[w], s->user.module, m.lowered[4 * k + 2].c_str()));
         HIP_TRY(hipModuleGetFunction(&s->user.loglike[w], s->user.module, m.lowered[4 * k + 3].c_str()));
+    }
+    for (int k = 0; k < kUserObShapes; k++) {
+        const int w = kUserObWaves[k];
+        if (!m.lowered_ob[2 * k + 0].empty())
+            HIP_TRY(hipModuleGetFunction(&s->user.round_ob[w], s->user.module, m.lowered_ob[2 * k + 0].c_str()));
+        if (!m.lowered_ob[2 * k + 1].empty())
+            HIP_TRY(hipModuleGetFunction(&s->user.calibrate_ob[w], s->user.module, m.lowered_ob[2 * k + 1].c_str()));
     }
     s->user_compile_seconds = m.compile_seconds;
     return APEMOST_HIP_OK;
@@ -625,7 +638,20 @@ static int user_model_build(apemost_hip_sampler *s) {
     }
     for (auto &n : names)
         rtc.add_name(prog, n);
-    const std::string key = std::to_string(s->kmodel) + "|" + prop.gcnArchName + "|" + user;
+    // APEMOST_HIP_FLAG_USER_ONE_BARRIER: the one-barrier round kernels, and the calibration kernels where the
+    // calibration takes them (the default proposal law and swap schedule: calib_shape)
+    const bool ob = (s->cfg.flags & APEMOST_HIP_FLAG_USER_ONE_BARRIER) != 0;
+    char names_ob[2 * kUserObShapes][128] = {};
+    for (int k = 0; ob && k < kUserObShapes; k++) {
+        const int w = kUserObWaves[k];
+        snprintf(names_ob[2 * k + 0], sizeof names_ob[0], "apemost::pt_round_ob_kernel<%d, %d, false, false>", km, w);
+        if (km < kVariantModel)
+            snprintf(names_ob[2 * k + 1], sizeof names_ob[0], "apemost::pt_calibrate_ob_kernel<%d, %d, false, false>", km, w);
+    }
+    for (auto &n : names_ob)
+        if (n[0])
+            rtc.add_name(prog, n);
+    const std::string key = std::to_string(s->kmodel) + (ob ? "|ob|" : "|") + prop.gcnArchName + "|" + user;
     {
         std::lock_guard<std::mutex> hold(g_user_models_lock);
         for (const UserModelCode &m : g_user_models)
@@ -661,6 +687,16 @@ static int user_model_build(apemost_hip_sampler *s) {
             return fail(APEMOST_HIP_ERR_RUNTIME, "hiprtcGetLoweredName(%s) failed", names[i]);
         }
         m.lowered[i] = low;
+    }
+    for (int i = 0; i < 2 * kUserObShapes; i++) {
+        if (!names_ob[i][0])
+            continue;
+        const char *low = nullptr;
+        if (rtc.lowered(prog, names_ob[i], &low) != HIPRTC_SUCCESS || !low) {
+            rtc.destroy(&prog);
+            return fail(APEMOST_HIP_ERR_RUNTIME, "hiprtcGetLoweredName(%s) failed", names_ob[i]);
+        }
+        m.lowered_ob[i] = low;
     }
     rtc.destroy(&prog);
     rc = user_model_load(s, m);
@@ -734,12 +770,15 @@ static int create_body(apemost_hip_sampler *s) {
         HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
         // the round kernel this sampler's stepping launches use: one barrier per step where that
         // variant exists (8 likelihood waves per chain), the classic two-phase step otherwise
-        s->one_barrier = has_one_barrier(s->waves) && !(cfg->flags & APEMOST_HIP_FLAG_TWO_BARRIER_STEP) && !s->user.module;
+        s->one_barrier = has_one_barrier(s->waves) && !(cfg->flags & APEMOST_HIP_FLAG_TWO_BARRIER_STEP) && user_may_ob(s);
         s->cus = prop.multiProcessorCount;
         s->ob_helper = s->one_barrier && ob_wants_helper(s, cfg->n_chains);
         s->betas_split_ok = true;
         int b_lds = 0, b_plain = 0;
-        if (s->user.module) {
+        if (s->user.module && s->one_barrier) {
+            HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&b_plain, s->user.round_ob[s->waves], ob_block(s->waves, false),
+                                                                       ob_lds_bytes(s, false)));
+        } else if (s->user.module) {
             HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&b_plain, s->user.round[s->waves], s->waves * kWave, s->lds_fixed_bytes));
         } else {
         if (s->lds_data)
@@ -813,7 +852,8 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
     if (cfg->flags & ~(APEMOST_HIP_FLAG_SINGLE_ROUND_LAUNCHES | APEMOST_HIP_FLAG_COOPERATIVE_LAUNCH |
                        APEMOST_HIP_FLAG_TWO_BARRIER_STEP | APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC |
                        APEMOST_HIP_FLAG_PROPOSAL_UNIFORM | APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_ADAPT |
-                       APEMOST_HIP_FLAG_TEST_REFUSE_COOPERATIVE | APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH | APEMOST_HIP_FLAG_RWM))
+                       APEMOST_HIP_FLAG_TEST_REFUSE_COOPERATIVE | APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH | APEMOST_HIP_FLAG_RWM |
+                       APEMOST_HIP_FLAG_USER_ONE_BARRIER))
         return fail(APEMOST_HIP_ERR_INVALID, "unknown bits in flags: 0x%x", (unsigned)cfg->flags);
     if ((cfg->flags & APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC) && (cfg->flags & APEMOST_HIP_FLAG_PROPOSAL_UNIFORM))
         return fail(APEMOST_HIP_ERR_INVALID, "PROPOSAL_LOGISTIC and PROPOSAL_UNIFORM are alternatives");
@@ -851,6 +891,8 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
     }
     if (cfg->model != APEMOST_MODEL_USER && cfg->device_model_source)
         return fail(APEMOST_HIP_ERR_INVALID, "device_model_source is for APEMOST_MODEL_USER only");
+    if (cfg->model != APEMOST_MODEL_USER && (cfg->flags & APEMOST_HIP_FLAG_USER_ONE_BARRIER))
+        return fail(APEMOST_HIP_ERR_INVALID, "APEMOST_HIP_FLAG_USER_ONE_BARRIER is for APEMOST_MODEL_USER only");
     int rc = apemost_hip_device_info(cfg->device, nullptr, 0, nullptr, nullptr);
     if (rc != APEMOST_HIP_OK)
         return rc;
@@ -1127,7 +1169,15 @@ static bool ob_wants_helper(const apemost_hip_sampler *s, int n_chains) {
     return n_chains <= s->cus;
 }
 
+// the one-barrier kernels are for the built-in models, and for a user-supplied one that opts in
+// (APEMOST_HIP_FLAG_USER_ONE_BARRIER: user_model_build compiled them)
+static bool user_may_ob(const apemost_hip_sampler *s) {
+    return !s->user.module || (s->cfg.flags & APEMOST_HIP_FLAG_USER_ONE_BARRIER);
+}
+
 static size_t ob_lds_bytes(const apemost_hip_sampler *s, bool lds_data) {
+    if (s->cfg.model == APEMOST_MODEL_USER) // (no data staged: the user rows' copies where the built-in models put their data)
+        return (size_t)(kObFixedDoubles + kObUserDoubles) * sizeof(double);
     return (size_t)kObFixedDoubles * sizeof(double) + (lds_data ? (size_t)2 * s->cfg.n_data * sizeof(double) : 0);
 }
 // dynamic LDS of the two-phase kernels for workgroups of `waves` likelihood wavefronts
@@ -1154,14 +1204,18 @@ static int launch_shape(apemost_hip_sampler *s, KernelKind kind, int grid, const
         return fail(APEMOST_HIP_ERR_RUNTIME, "kernel launch failed: cooperative launch refused (test hook)");
     if (s->user.module) {
         // the kernels of a user-supplied model live in a run-time module: the two-phase step, data through L2
+        // (APEMOST_HIP_FLAG_USER_ONE_BARRIER: the one-barrier kernels too, without a helper wavefront)
         hipFunction_t f = nullptr;
+        const bool ob = kind == K_ROUND_OB || kind == K_CALIB_OB;
         if (waves >= 1 && waves <= 8)
             f = kind == K_ROUND ? s->user.round[waves] : kind == K_CALIB ? s->user.calibrate[waves]
-                : kind == K_CALC ? s->user.calc_model[waves] : kind == K_EVAL ? s->user.loglike[waves] : nullptr;
-        if (!f || lds_data || coop)
+                : kind == K_CALC ? s->user.calc_model[waves] : kind == K_EVAL ? s->user.loglike[waves]
+                : kind == K_ROUND_OB ? s->user.round_ob[waves] : s->user.calibrate_ob[waves];
+        if (!f || lds_data || coop || helper)
             return fail(APEMOST_HIP_ERR_RUNTIME, "kernel launch failed: no such kernel for a user-supplied model");
+        const unsigned block = ob ? (unsigned)ob_block(waves, false) : (unsigned)(waves * kWave);
         void *params[] = {const_cast<void *>(args)};
-        const hipError_t e = hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, (unsigned)(waves * kWave), 1, 1, (unsigned)op.lds, s->stream, params, nullptr);
+        const hipError_t e = hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, block, 1, 1, (unsigned)op.lds, s->stream, params, nullptr);
         if (e != hipSuccess)
             return fail(APEMOST_HIP_ERR_RUNTIME, "kernel launch failed: %s", hipGetErrorString(e));
         return APEMOST_HIP_OK;
@@ -1760,7 +1814,7 @@ static CalibShape calib_shape(const apemost_hip_sampler *s, int n_active) {
     if (!s->user.module && !built(s->kmodel, g.waves))
         g.waves = s->waves; // (development builds hold only some shapes)
     g.one_barrier = has_one_barrier(g.waves) && s->kmodel < kVariantModel && !(s->cfg.flags & APEMOST_HIP_FLAG_TWO_BARRIER_STEP) &&
-                    !s->user.module;
+                    user_may_ob(s);
     g.helper = g.one_barrier && ob_wants_helper(s, n_active) && s->betas_split_ok;
     const size_t bytes = g.one_barrier ? ob_lds_bytes(s, true) : classic_lds_bytes(s, g.waves, true);
     g.lds_data = !s->user.module && bytes <= 160 * 1024 - 1024 && c.lds_policy != 2 && (c.lds_policy == 1 || choose_lds(c, bytes));

@@ -489,7 +489,10 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
             }
             for (unsigned s = 0; s < a.n_steps; s++) {
                 OB_STAMP_BEGIN;
-                e.lik_step(p); // (takes one more barrier inside when a proposal has to be redrawn)
+                if constexpr (decltype(e)::kUser)
+                    e.lik_step_user(p); // (the user-supplied model: the decision through its finish())
+                else
+                    e.lik_step(p); // (takes one more barrier inside when a proposal has to be redrawn)
                 OB_STAMP_END;
                 __syncthreads();
                 p ^= 1;
@@ -1059,7 +1062,10 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
                 break;
             int p = 0;
             for (int s = 0; s < n_steps; s++) {
-                e.lik_step(p);
+                if constexpr (decltype(e)::kUser)
+                    e.lik_step_user(p);
+                else
+                    e.lik_step(p);
                 __syncthreads();
                 p ^= 1;
             }

@@ -32,6 +32,15 @@
 //
 // Draws, proposals, sums (same tree order as Engine with the same number of likelihood waves) and
 // recorded values are those of Engine; only the form of the accept comparison differs.
+//
+// A user-supplied likelihood (APEMOST_MODEL_USER, opt-in: APEMOST_HIP_FLAG_USER_ONE_BARRIER) is an
+// arbitrary function of the data sum, so it has no threshold S_max.  It keeps the structure and drops
+// the threshold form: the owner publishes prob and ln U instead of S_max, and behind the barrier every
+// likelihood wave and the owner call apemost_user_finish() on the data sum and the parameters of the
+// step being decided and apply check_accept as the reference writes it (ob_check_accept).  Every wave
+// then makes Engine's decision bit for bit.  The parameters of the step being decided are a copy
+// (s_urow) that likelihood wave 0 takes right after its pick: the owner rewrites the proposal rows of
+// that parity while the decision is being made.
 #pragma once
 
 #include "pt_device.h"
@@ -49,10 +58,24 @@ constexpr int kObProp = 44;                       // [2][2][64] proposals: [pari
 constexpr int kObCand = kObProp + 2 * 2 * kWave;  // [8][64] double2 candidate ring
 constexpr int kObLogTab = kObCand + 8 * 2 * kWave;  // the logarithm's table (pulse models)
 constexpr int kObFixedDoubles = kObLogTab + kLogTabLdsDoubles;
+// the user-supplied model only, where the built-in models stage their data (a user model stages none):
+constexpr int kObUserRow = kObFixedDoubles;       // [2][64] parameters of the step a likelihood wave picked, per parity
+constexpr int kObUserDoubles = 2 * kWave;
+
+// check_accept (src/markov_chain.c:282-311) as the reference writes it: a NaN prob_new rejects
+__device__ __forceinline__ bool ob_check_accept(double prob_new, double prob, double lu) {
+    return prob_new == prob || prob_new > prob || lu < prob_new - prob;
+}
 
 // S_max of a step: accept <=> data sum < S_max.  T = prob + ln U.
 template <int MODEL>
 struct ObThreshold;
+
+// A user-supplied model has no threshold: every wave decides through ob_check_accept (see the top of this file).
+template <>
+struct ObThreshold<APEMOST_MODEL_USER> {
+    __device__ __forceinline__ void init(const ModelConsts &, double) {}
+};
 
 // kSplit (the models with a prior): S_max = X - Y in two halves that different wavefronts compute side by
 // side -- X from the proposal alone (its prior and additive parameter: the helper, a candidate producer), Y
@@ -168,6 +191,7 @@ struct ObEngine {
     static constexpr bool kVariants = MODEL >= kVariantModel; // see kVariantModel (pt_device.h)
     static constexpr int kBase = MODEL % kVariantModel;
     static constexpr bool kSine = kBase == APEMOST_MODEL_SIMPLESIN || kBase == APEMOST_MODEL_SINE3;
+    static constexpr bool kUser = Model<kBase>::kIndexed; // a user-supplied model: the decision through finish()
 #ifndef APEMOST_PHILOX_MERGED
 #define APEMOST_PHILOX_MERGED 2 // 0: never, 1: always, 2: the sine models
 #endif
@@ -225,6 +249,7 @@ struct ObEngine {
         return lds + kObProp + (parity * 2 + variant) * kWave;
     }
     __device__ __forceinline__ double2 *s_cand(u64 t) const { return (double2 *)(lds + kObCand) + (int)(t & 7) * kWave; }
+    __device__ __forceinline__ double *s_urow(int parity) const { return lds + kObUserRow + parity * kWave; }
     __device__ __forceinline__ volatile int *fail_flag() const { return (volatile int *)(lds + kObCtl) + 2; }
 
     // every wave: who am I, where is the data; stages the data vector (all threads copy)
@@ -282,13 +307,17 @@ struct ObEngine {
             qidx = 1 << 30;
         }
     }
-    __device__ __forceinline__ void setup_lik(const DevArrays &, const ChainShape &sh, int c) {
+    __device__ __forceinline__ void setup_lik(const DevArrays &d, const ChainShape &sh, int c) {
         setup_lanes(sh, c); // (the first two candidate sets are made by likelihood waves)
         consts = sh.consts;
         x_abs_max = sh.x_abs_max;
         rows_in_regs = false;
         m.init();
         m.set_consts(consts);
+        if constexpr (kUser) { // (the likelihood waves decide through finish(), which takes beta)
+            m.set_data(d.data, sh.n_data, (int)((unsigned)sh.variant >> 16));
+            beta_all = d.beta()[c + 1];
+        }
     }
     __device__ __forceinline__ void setup_owner(const DevArrays &d, const ChainShape &sh, int c) {
         consts = sh.consts;
@@ -303,6 +332,8 @@ struct ObEngine {
             m.set_lean(false);
         m.set_consts(consts);
         m.set_box(d.pmin() + (size_t)c * sh.n_par, d.pmax() + (size_t)c * sh.n_par, sh.x_abs_max);
+        if constexpr (kUser)
+            m.set_data(d.data, sh.n_data, (int)((unsigned)sh.variant >> 16));
     }
 
     // ---- candidates (same arithmetic as Engine::cand_begin / cand_finish) ----
@@ -477,6 +508,8 @@ struct ObEngine {
 
     // ---- likelihood waves ----
     __device__ __forceinline__ void cache_rows() {
+        if constexpr (kUser)
+            return; // (a user-supplied model reads its rows itself, by index: see Engine::cache_rows)
         rows_in_regs = n_data == kWide * kLikThreads;
 #pragma unroll
         for (int j = 0; j < kWide; j++) {
@@ -548,8 +581,48 @@ struct ObEngine {
         return wave_reduce_sum_lane63(acc); // valid in lane 63
     }
 
+    // the user-supplied model: the wave's share of sum_i term(i), the rows i = tid, tid + kLikThreads, ...
+    // (Engine::reduce_data_indexed: the same loop, butterfly and tree, so the same sum bit for bit)
+    __device__ __forceinline__ double lik_partial_user() const {
+        double acc = 0;
+        for (int i = tid; i < n_data; i += kLikThreads)
+            acc += m.term_index(i);
+        return wave_reduce_sum_lane63(acc); // valid in lane 63
+    }
+    // The previous step's decision from its data sum, its parameters (the copy in s_urow) and what the owner
+    // published for it (prob, ln U); then this step's row, picked by pointer, and its likelihood.
+    __device__ __forceinline__ void lik_step_user(int parity) {
+        double part[LW];
+        const double *sp = s_part(parity);
+#pragma unroll
+        for (int w = 0; w < LW; w++)
+            part[w] = sp[w];
+        const double prob = *s_thr(parity), lu = *s_thx(parity);
+        const int pending = *s_flag(parity);
+#pragma unroll
+        for (int span = 1; span < LW; span *= 2) {
+#pragma unroll
+            for (int w = 0; w + span < LW; w += 2 * span)
+                part[w] += part[w + span];
+        }
+        m.load(s_urow(parity ^ 1), n_par, 0);
+        double prior_new = 0; // (the owner keeps the prior; finish() writes it before it reads it)
+        const bool first = ob_check_accept(m.finish(part[0], beta_all, consts, &prior_new), prob, lu);
+        if (__builtin_amdgcn_readfirstlane(pending) != 0)
+            __syncthreads(); // rare: the owner is replacing a proposal that could not be prepared (redraw path)
+        m.fetch2(s_prop(parity, 0), s_prop(parity, 1));
+        m.pick2(first, n_par);
+        // the row stays intact until the next barrier only: the owner rewrites s_prop(parity, .) in the next step,
+        // while this step is being decided
+        if (hw == 0 && lane < n_par)
+            s_urow(parity)[lane] = m.ctx.params[lane];
+        const double mine = lik_partial_user();
+        if (lane == 63)
+            s_part(parity ^ 1)[hw] = mine;
+    }
+
     // One step of a likelihood wave.  `parity` holds what the previous step published: its partial
-    // sums and threshold, and the two prepared proposals of this step.
+    // sums and threshold, and the two prepared proposals of this step.  (The user-supplied model: lik_step_user.)
     __device__ __forceinline__ void lik_step(int parity) {
         // everything the decision needs is requested at once: the partial sums, the threshold, the
         // redraw flag and BOTH prepared proposals (selecting the row first and reading it afterwards
@@ -724,6 +797,10 @@ struct ObEngine {
         __builtin_amdgcn_wave_barrier();
         if (lane < n_par)
             s_prop(0, 0)[lane] = row[lane];
+        if constexpr (kUser) { // (the likelihood waves decide a step that was not taken: parameters they may read)
+            if (lane < n_par)
+                s_urow(1)[lane] = row[lane];
+        }
 #ifdef APEMOST_EXP_NO_ATTEMPTS
         if (lane < n_par)
             s_prop(1, 0)[lane] = s_prop(1, 1)[lane] = row[lane];
@@ -773,6 +850,15 @@ struct ObEngine {
     // (src/markov_chain.c:48-58), not after every step
     __device__ __forceinline__ void owner_results(int parity, double *sample, int which = -1, bool check_best = true) {
         const double sum = tree(parity);
+        double prob_new;
+        if constexpr (kUser) {
+            // finish() at the parameters of the step (m holds its row since owner_choose) and the decision every
+            // likelihood wave makes from the same three values: prob, ln U of the step's tick, prob_new
+            double prior_new = prior; // (kept where finish() does not set it, as in Engine::step)
+            prob_new = m.finish(sum, beta_all, consts, &prior_new);
+            accepted = ob_check_accept(prob_new, prob, read_lane(cand_y, 63));
+            prior = prior_new; // not restored on reject (quirk Q7)
+        } else {
         if constexpr (kSplit) {
             // the helper's half of the threshold and the prior it took for it, published by the barrier
             // that closed the step; `thr` holds the owner's own half since owner_publish
@@ -782,9 +868,10 @@ struct ObEngine {
         accepted = sum < thr;
         OB_SEG(0); // LDS batch, partial sums, decision
         // (the proposal's prior was computed for its threshold, a step ago: not again)
-        const double prob_new = m.finish_known_prior(sum, beta_all, consts, prior_inflight);
+        prob_new = m.finish_known_prior(sum, beta_all, consts, prior_inflight);
         if (Model<kBase>::kHasPrior)
             prior = prior_inflight; // not restored on reject (quirk Q7)
+        }
         if (which < 0) {
             n_accepted += accepted ? 1u : 0u; // the four counters move together here (all-parameter steps): settled at the end
         } else {
@@ -832,7 +919,9 @@ struct ObEngine {
             __builtin_amdgcn_wave_barrier();
             par_val = cand() ? row[grp] : 0.0;
         }
-        if constexpr (Model<kBase>::kHasPrior)
+        if constexpr (kUser)
+            m.load(row, n_par, 0); // (the row is read by finish() in the next step, before owner_publish rewrites this parity)
+        else if constexpr (Model<kBase>::kHasPrior)
             m.load_offset(row, n_par); // (prior_only, offset and finish_known_prior read the heights and the additive parameter, nothing else)
         else
             m.load(row, n_par, x_abs_max);
@@ -870,13 +959,15 @@ struct ObEngine {
 #endif
         // S_max of the step in flight (kSplit: the chain's half of it; the helper adds the proposal's)
         double prior_new = 0;
-        if constexpr (Model<kBase>::kHasPrior && !kSplit) {
+        if constexpr (Model<kBase>::kHasPrior && !kSplit && !kUser) {
             prior_new = m.prior_only(consts);
             prior_inflight = prior_new;
         }
         OB_SEG(4); // the prior of the proposal in flight (kSplit: the helper's since round 4)
         const double lu = read_lane(cand_y, 63);
-        if constexpr (kSplit)
+        if constexpr (kUser)
+            thr = prob; // (no threshold: prob and ln U go out as they are, see ob_check_accept)
+        else if constexpr (kSplit)
             thr = thr_fn.y_part(prob + lu);
         else if constexpr (Model<kBase>::kHasPrior)
             thr = thr_fn.s_max(prob + lu, m, prior_new, m.offset());
@@ -884,6 +975,8 @@ struct ObEngine {
             thr = thr_fn.s_max(prob + lu, m, 0.0, 0.0);
         if (lane == 0) {
             *s_thr(next) = thr;
+            if constexpr (kUser)
+                *s_thx(next) = lu;
 #ifdef APEMOST_EXP_OWNER_SLACK
             *s_flag(next) = 0;
 #else

@@ -2,8 +2,9 @@
 the same translation unit the engine hands to hiprtc when a sampler of APEMOST_MODEL_USER is created
 (apemost_hip.hip user_model_build) -- '#include "pt_kernels.h"' + the user's file, the four kernels of
 each workgroup shape (1, 2, 4, 8 waves per chain) named as template instantiations -- compiled for gfx950 through libhiprtc with ctypes.
+With one_barrier (--one-barrier) the one-barrier kernels of APEMOST_HIP_FLAG_USER_ONE_BARRIER are named too.
 
-    python -m apemost_amd.device_model my_model.hip
+    python -m apemost_amd.device_model [--one-barrier] my_model.hip
 """
 import ctypes as C
 import os
@@ -23,8 +24,20 @@ def _hiprtc():
     raise OSError("libhiprtc.so not found")
 
 
-def compile_check(path, variant=False, arch="gfx950"):
-    """-> (ok, compiler log, code bytes)"""
+OB_WAVES = (4, 8)   # likelihood waves of the one-barrier kernels (pt_kernels.h has_one_barrier)
+
+
+def ob_kernel_names(km):
+    """the one-barrier instantiations user_model_build adds under APEMOST_HIP_FLAG_USER_ONE_BARRIER: the round
+    kernel for every kmodel, the calibration kernel for the default proposal law and swap schedule only"""
+    names = ["apemost::pt_round_ob_kernel<%d, %d, false, false>" % (km, w) for w in OB_WAVES]
+    if km < VARIANT:
+        names += ["apemost::pt_calibrate_ob_kernel<%d, %d, false, false>" % (km, w) for w in OB_WAVES]
+    return names
+
+
+def compile_check(path, variant=False, arch="gfx950", one_barrier=False, code=False):
+    """-> (ok, compiler log, code bytes); code=True: (ok, log, the code object itself, b"" on failure)"""
     rtc = _hiprtc()
     src = ('#define APEMOST_USER_MODEL 1\n#include "pt_kernels.h"\n#line 1 "%s"\n%s\n' % (path, open(path).read())).encode()
     prog = C.c_void_p()
@@ -38,6 +51,9 @@ def compile_check(path, variant=False, arch="gfx950"):
                      "apemost::pt_calc_model_kernel<%d, %d, false>" % (MODEL_USER, w),
                      "apemost::pt_loglike_kernel<%d, %d, false>" % (MODEL_USER, w)):
             rtc.hiprtcAddNameExpression(prog, name.encode())
+    if one_barrier:
+        for name in ob_kernel_names(km):
+            rtc.hiprtcAddNameExpression(prog, name.encode())
     opts = [b"--offload-arch=" + arch.encode(), b"-O3", b"-ffp-contract=off", b"-std=c++17",
             b"-I" + os.path.join(HERE, "csrc").encode(), b"-I" + os.path.join(ROOT, "include").encode(), b"-I/opt/rocm/include"]
     rc = rtc.hiprtcCompileProgram(prog, len(opts), (C.c_char_p * len(opts))(*opts))
@@ -47,16 +63,22 @@ def compile_check(path, variant=False, arch="gfx950"):
     if n.value:
         rtc.hiprtcGetProgramLog(prog, log)
     size = C.c_size_t(0)
+    blob = b""
     if rc == 0:
         rtc.hiprtcGetCodeSize(prog, C.byref(size))
+        if code:
+            buf = C.create_string_buffer(size.value)
+            rtc.hiprtcGetCode(prog, buf)
+            blob = buf.raw
     rtc.hiprtcDestroyProgram(C.byref(prog))
-    return rc == 0, log.value.decode("utf-8", "replace"), size.value
+    return rc == 0, log.value.decode("utf-8", "replace"), blob if code else size.value
 
 
 if __name__ == "__main__":
     ok_all = True
-    for p in sys.argv[1:]:
-        ok, log, size = compile_check(p)
+    one_barrier = "--one-barrier" in sys.argv[1:]
+    for p in [a for a in sys.argv[1:] if a != "--one-barrier"]:
+        ok, log, size = compile_check(p, one_barrier=one_barrier)
         print("%s: %s%s" % (p, "compiles (%d bytes of gfx950 code)" % size if ok else "DOES NOT COMPILE", "\n" + log if log.strip() else ""))
         ok_all = ok_all and ok
     sys.exit(0 if ok_all else 1)

@@ -16,6 +16,11 @@
  * lanes of the chain's wavefront), finish() is everything else: get_beta(m), the prior, set_prob /
  * set_prior.  A likelihood without a data loop returns 0 from term().
  *
+ * Under APEMOST_HIP_FLAG_USER_ONE_BARRIER (include/apemost_hip.h) the model also runs in the one-barrier kernels.
+ * There every lane of every likelihood wave calls finish(), and so does the chain's own wave, so finish() must
+ * be a pure function of (ctx, sum, beta) and must not read *prior before it writes it.  The example sources in
+ * apemost_amd/host/examples/device_models/ satisfy this.
+ *
  * The file is compiled as HIP device code for gfx950 (-O3 -ffp-contract=off -std=c++17); it may use
  * the device math library (sin, exp, log, pow, ...).  No host code, no other includes.
  */

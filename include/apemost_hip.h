@@ -140,7 +140,15 @@ enum {
      * U / sqrt(n_iter) * (min(1, exp(prob - prob_old)) - adapt_target) * (max - min), clamped to
      * [1e-7, 1e6] * (max - min); U = word p % 4 of block (tick << 24) | (1 + p / 4) of the accept slot.
      * Every round is a launch of its own (as with APEMOST_HIP_FLAG_ADAPT, which runs after it). */
-    APEMOST_HIP_FLAG_RWM = 512
+    APEMOST_HIP_FLAG_RWM = 512,
+    /* APEMOST_MODEL_USER only (APEMOST_HIP_ERR_INVALID with a built-in model): the user's likelihood also runs in
+     * the one-barrier round and calibration kernels, wherever a built-in model would take them (4 or 8 likelihood
+     * waves per chain; APEMOST_HIP_FLAG_TWO_BARRIER_STEP still wins; the calibration of the default proposal law and
+     * swap schedule only; launch_round_for stays two-phase).  No helper wavefront, no cooperative launches.  Every
+     * likelihood wave and the chain's wave call apemost_user_finish() and apply the reference's check_accept to its
+     * result: the same decisions, bit for bit, as the two-phase kernels, if finish() keeps the contract stated in
+     * include/apemost_device_model.h.  hiprtc compiles four more kernels at create time. */
+    APEMOST_HIP_FLAG_USER_ONE_BARRIER = 1024
 };
 
 typedef struct {
