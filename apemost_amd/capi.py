@@ -55,6 +55,15 @@ class CalibConfig(C.Structure):
                 ("progress_chain", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SummaryConfig(C.Structure):
+    _fields_ = [("n_hist_chains", C.c_int32), ("nbins", C.c_int32), ("batch_size", C.c_uint64),
+                ("max_batches", C.c_uint64), ("lo", _dp), ("hi", _dp)]
+
+
+class SummaryView(C.Structure):
+    _fields_ = [("n", _up), ("prob_sum", _dp), ("hist", _up), ("batch_sums", _dp), ("n_batches", _up)]
+
+
 # every symbol include/apemost_hip.h declares
 EXPORTS = [
     "apemost_hip_last_error", "apemost_hip_abi_version", "apemost_hip_device_count",
@@ -72,6 +81,8 @@ EXPORTS = [
     "apemost_hip_calibrate_end", "apemost_hip_calibrate_poll", "apemost_hip_calibrate_cancel", "apemost_hip_calibrate_wait_any",
     "apemost_hip_calibrate_progress", "apemost_hip_calibrate_stats", "apemost_hip_rng_raw",
     "apemost_hip_rng_attempts", "apemost_hip_timer_begin", "apemost_hip_timer_end",
+    "apemost_hip_summary_begin", "apemost_hip_summary_accumulate", "apemost_hip_summary_get",
+    "apemost_hip_summary_set", "apemost_hip_summary_end",
 ]
 
 _lib = None
@@ -161,6 +172,11 @@ def lib():
     L.apemost_hip_rng_attempts.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64,
                                            C.c_int32, _dp, _dp, C.POINTER(C.c_int32), _dp]
     L.apemost_hip_user_model_compile_seconds.argtypes = [vp, _dp]
+    L.apemost_hip_summary_begin.argtypes = [vp, C.POINTER(SummaryConfig)]
+    L.apemost_hip_summary_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_summary_get.argtypes = [vp, C.POINTER(SummaryView)]
+    L.apemost_hip_summary_set.argtypes = [vp, C.POINTER(SummaryView)]
+    L.apemost_hip_summary_end.argtypes = [vp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

@@ -1,6 +1,7 @@
 // apemost_hip.hip -- kernels and C ABI of the gfx950 parallel-tempering engine
 // (declared in include/apemost_hip.h).  Written for MI355X only.
 #include "pt_kernels.h"
+#include "pt_summary.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -327,6 +328,15 @@ struct apemost_hip_sampler {
     double user_compile_seconds; // hiprtc's time for this sampler's user model (0: taken from the process's cache)
     double *rwm_keep;            // APEMOST_HIP_FLAG_RWM: what the extra step of a round must not be seen to change
     bool in_rwm;
+    // the run summary (apemost_hip_summary_begin .. end): accumulated by summary_kernel on copy_stream
+    struct {
+        bool open;
+        int n_hist, nbins;
+        u64 bs, max_batches;
+        u64 n; // kept samples so far (the host knows it without a sync)
+        double *d_lo, *d_hi, *d_prob_sum, *d_batch;
+        u64 *d_hist;
+    } sum;
 };
 
 extern "C" const char *apemost_hip_last_error(void) { return g_last_error.c_str(); }
@@ -430,6 +440,15 @@ static int choose_waves(const apemost_hip_config &c) {
     return by_chip < by_data ? by_chip : by_data;
 }
 
+// the run summary's device arrays (the caller has synchronised the streams that use them)
+static void summary_free(apemost_hip_sampler *s) {
+    for (void *p : {(void *)s->sum.d_lo, (void *)s->sum.d_hi, (void *)s->sum.d_prob_sum, (void *)s->sum.d_batch,
+                    (void *)s->sum.d_hist})
+        if (p)
+            hipFree(p);
+    s->sum = {};
+}
+
 // everything a sampler owns on the device; safe on a half-built sampler
 static void release(apemost_hip_sampler *s) {
     if (s->stream)
@@ -456,6 +475,7 @@ static void release(apemost_hip_sampler *s) {
         hipStreamSynchronize(s->copy_stream);
         hipStreamDestroy(s->copy_stream);
     }
+    summary_free(s); // (its kernels ran on copy_stream)
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     if (s->ev_exported)
@@ -920,6 +940,7 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
     s->user_compile_seconds = 0;
     s->rwm_keep = nullptr;
     s->in_rwm = false;
+    s->sum = {};
     if (s->waves == 6 && (cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
                                         APEMOST_HIP_FLAG_RANDOMSWAP))) {
         delete s;
@@ -1561,6 +1582,192 @@ extern "C" int apemost_hip_samples_wait(apemost_hip_sampler *s) {
     HIP_TRY(hipStreamSynchronize(s->copy_stream));
     if (*s->h_word != 0)
         return apemost_hip_synchronize(s); // reports, clears and falls back (check_handoff)
+    return APEMOST_HIP_OK;
+}
+
+// ---- run summary (pt_summary.h) ----
+// batches of batch_means_error() closed after n samples: sample n (counted from 1) closes one when
+// n % bs == bs - 1 -- for bs >= 2 the first batch holds bs - 1 samples, every later one bs
+static u64 summary_closed(u64 n, u64 bs) { return bs == 1 ? n : (n + 1) / bs; }
+// samples still to come before the batch that is open after n samples closes (1 .. bs)
+static u64 summary_left(u64 n, u64 bs) {
+    const u64 m = (bs - (n + 1) % bs) % bs;
+    return m == 0 ? bs : m;
+}
+
+static int ensure_copy_stream(apemost_hip_sampler *s) {
+    if (!s->copy_stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&s->ev_copy, hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc((void **)&s->h_word, sizeof(u64), hipHostMallocDefault));
+        *s->h_word = 0;
+    }
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_summary_begin(apemost_hip_sampler *s, const apemost_hip_summary_config *cfg) {
+    CHECK_S(s);
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: config is NULL");
+    const int np = s->cfg.n_par;
+    if (cfg->nbins < 1 || cfg->nbins > kSummaryMaxBins)
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: nbins %d outside [1,%d]", cfg->nbins, kSummaryMaxBins);
+    if (cfg->n_hist_chains < 0 || cfg->n_hist_chains > s->cfg.n_chains)
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: n_hist_chains %d outside [0,%d]", cfg->n_hist_chains,
+                    s->cfg.n_chains);
+    if (cfg->batch_size < 1)
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: batch_size must be >= 1");
+    if (cfg->n_hist_chains > 0 && (!cfg->lo || !cfg->hi))
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: histograms need lo and hi");
+    for (int p = 0; p < np && cfg->lo && cfg->hi; p++)
+        if (!std::isfinite(cfg->lo[p]) || !std::isfinite(cfg->hi[p]) || !(cfg->lo[p] < cfg->hi[p]))
+            return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: parameter %d: range [%g, %g] invalid", p, cfg->lo[p],
+                        cfg->hi[p]);
+    const size_t n_hp = (size_t)cfg->n_hist_chains * np;
+    if (cfg->max_batches > ((size_t)1 << 40) || (n_hp > 0 && cfg->max_batches + 1 > ((size_t)1 << 40) / n_hp))
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: max_batches %llu too large",
+                    (unsigned long long)cfg->max_batches);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a summary before this one may still be accumulating
+    summary_free(s);
+    s->sum.n_hist = cfg->n_hist_chains;
+    s->sum.nbins = cfg->nbins;
+    s->sum.bs = cfg->batch_size;
+    s->sum.max_batches = cfg->max_batches;
+    s->sum.n = 0;
+    const size_t nb = n_hp * (cfg->max_batches + 1), nh = n_hp * cfg->nbins;
+    HIP_TRY(hipMalloc((void **)&s->sum.d_prob_sum, s->cfg.n_chains * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->sum.d_lo, np * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->sum.d_hi, np * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->sum.d_batch, (nb > 0 ? nb : 1) * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->sum.d_hist, (nh > 0 ? nh : 1) * sizeof(u64)));
+    HIP_TRY(hipMemsetAsync(s->sum.d_prob_sum, 0, s->cfg.n_chains * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->sum.d_batch, 0, (nb > 0 ? nb : 1) * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->sum.d_hist, 0, (nh > 0 ? nh : 1) * sizeof(u64), s->stream));
+    HIP_TRY(hipMemsetAsync(s->sum.d_lo, 0, np * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->sum.d_hi, 0, np * sizeof(double), s->stream));
+    if (cfg->lo && cfg->hi) {
+        HIP_TRY(hipMemcpyAsync(s->sum.d_lo, cfg->lo, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->sum.d_hi, cfg->hi, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->sum.open = true;
+    return APEMOST_HIP_OK;
+}
+
+// Queued on copy_stream behind everything launched so far on the sampler's stream, like
+// apemost_hip_samples_read_async: launches issued after this call overlap with it, and
+// apemost_hip_samples_wait / apemost_hip_summary_get wait for it -- the caller does one of them before
+// d_samples is written again.
+extern "C" int apemost_hip_summary_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                              uint64_t skip, uint64_t thin) {
+    CHECK_S(s);
+    if (!s->sum.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_accumulate: no summary_begin");
+    if (thin < 1 || (!d_samples && n_steps > 0))
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_accumulate: bad arguments");
+    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    if (summary_closed(s->sum.n + kept, s->sum.bs) > s->sum.max_batches)
+        return fail(APEMOST_HIP_ERR_INVALID,
+                    "summary_accumulate: %llu samples would close batch %llu, beyond max_batches = %llu",
+                    (unsigned long long)(s->sum.n + kept), (unsigned long long)summary_closed(s->sum.n + kept, s->sum.bs),
+                    (unsigned long long)s->sum.max_batches);
+    if (kept == 0)
+        return APEMOST_HIP_OK;
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const int n_hp = s->sum.n_hist * s->cfg.n_par;
+    const int grid = n_hp + (s->cfg.n_chains + kSummaryThreads - 1) / kSummaryThreads;
+    // (the LDS bins count in 32 bits: at most 2^31 samples per launch)
+    for (u64 k0 = 0; k0 < kept; k0 += (u64)1 << 31) {
+        SummaryArgs a;
+        a.rows = d_samples;
+        a.n_chains = s->cfg.n_chains;
+        a.n_par = s->cfg.n_par;
+        a.skip = skip + k0 * thin;
+        a.thin = thin;
+        a.n_kept = kept - k0 < ((u64)1 << 31) ? kept - k0 : (u64)1 << 31;
+        a.n_hist = s->sum.n_hist;
+        a.nbins = s->sum.nbins;
+        a.lo = s->sum.d_lo;
+        a.hi = s->sum.d_hi;
+        a.bs = s->sum.bs;
+        a.left = summary_left(s->sum.n, s->sum.bs);
+        a.n_closed = summary_closed(s->sum.n, s->sum.bs);
+        a.prob_sum = s->sum.d_prob_sum;
+        a.hist = s->sum.d_hist;
+        a.batch = s->sum.d_batch;
+        a.batch_stride = s->sum.max_batches + 1;
+        hipLaunchKernelGGL(summary_kernel, dim3(grid), dim3(kSummaryThreads), 0, s->copy_stream, a);
+        HIP_TRY(hipGetLastError());
+        s->sum.n += a.n_kept;
+    }
+    return APEMOST_HIP_OK;
+}
+
+static int summary_xfer(apemost_hip_sampler *s, const apemost_hip_summary_view *v, bool up) {
+    if (!s->sum.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "summary_%s: no summary_begin", up ? "set" : "get");
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "summary view is NULL");
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const size_t n_hp = (size_t)s->sum.n_hist * s->cfg.n_par;
+    const size_t nb = n_hp * (s->sum.max_batches + 1), nh = n_hp * s->sum.nbins;
+    if (up && v->n) {
+        if (summary_closed(*v->n, s->sum.bs) > s->sum.max_batches)
+            return fail(APEMOST_HIP_ERR_INVALID, "summary_set: %llu samples close more than max_batches batches",
+                        (unsigned long long)*v->n);
+        if (v->n_batches && *v->n_batches != summary_closed(*v->n, s->sum.bs))
+            return fail(APEMOST_HIP_ERR_INVALID, "summary_set: n_batches %llu does not follow from n = %llu",
+                        (unsigned long long)*v->n_batches, (unsigned long long)*v->n);
+    }
+    // stream order: behind every accumulate queued so far, on the stream they run on
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+#define SUMMARY_COPY(dev, host, bytes)                                                                          \
+    do {                                                                                                       \
+        if ((host) && (bytes) > 0)                                                                             \
+            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
+                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
+    } while (0)
+    SUMMARY_COPY(s->sum.d_prob_sum, v->prob_sum, s->cfg.n_chains * sizeof(double));
+    SUMMARY_COPY(s->sum.d_hist, v->hist, nh * sizeof(u64));
+    SUMMARY_COPY(s->sum.d_batch, v->batch_sums, nb * sizeof(double));
+#undef SUMMARY_COPY
+    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    if (up) {
+        if (v->n)
+            s->sum.n = *v->n;
+    } else {
+        if (v->n)
+            *v->n = s->sum.n;
+        if (v->n_batches)
+            *v->n_batches = summary_closed(s->sum.n, s->sum.bs);
+    }
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_summary_get(apemost_hip_sampler *s, const apemost_hip_summary_view *v) {
+    CHECK_S(s);
+    return summary_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_summary_set(apemost_hip_sampler *s, const apemost_hip_summary_view *v) {
+    CHECK_S(s);
+    return summary_xfer(s, v, true);
+}
+
+extern "C" int apemost_hip_summary_end(apemost_hip_sampler *s) {
+    CHECK_S(s);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    summary_free(s);
     return APEMOST_HIP_OK;
 }
 

@@ -2,7 +2,9 @@
  * outside the GPU path).  Same inputs, outputs and formulas as reference
  * src/analyse.c:33-285 and its histogram helper (src/histogram.c:33-42): the thermodynamic
  * integral over beta of the mean log-likelihood, and per-parameter marginal histograms with a
- * batch-means Monte-Carlo error.  The reference's n_beta < 100 limit does not apply. */
+ * batch-means Monte-Carlo error.  The reference's n_beta < 100 limit does not apply.
+ * With `summary` in APEMOST_DUMP the same numbers come from summary.bin (run_summary.h), the sums the
+ * device folded during the run, instead of the dump files; the printed lines and written files are the same. */
 #include <math.h>
 #include <string.h>
 #include "mcmc.h"
@@ -10,6 +12,7 @@
 #include "parallel_tempering_config.h"
 #include "utils.h"
 #include "debug.h"
+#include "run_summary.h"
 
 #ifndef NBINS
 #define NBINS 200
@@ -21,14 +24,41 @@
 /* ln p(D|M) = integral over beta of <ln L>_beta: per chain the mean of column 2 of
  * prob-chain<i>.dump (prob - prior = beta * ln L) divided by beta, rectangle rule from the
  * hottest chain down to beta = 1 */
+static void read_summary_or_die(run_summary *r, unsigned int n_beta, unsigned int n_par) {
+    if (run_summary_read(RUN_SUMMARY_FILE, r) != 0) {
+        fprintf(stderr, "APEMOST_DUMP=summary: %s not found\n", RUN_SUMMARY_FILE);
+        exit(1);
+    }
+    if (r->n_beta != n_beta || r->n_par != n_par || r->nbins != NBINS || r->n_hist < 1) {
+        fprintf(stderr, "%s holds %u chains, %u parameters, %u bins; this analysis has %u, %u, %d\n", RUN_SUMMARY_FILE,
+                r->n_beta, r->n_par, r->nbins, n_beta, n_par, NBINS);
+        exit(1);
+    }
+}
+
 void analyse_data_probability() {
     const unsigned int n_beta = apemost_n_beta();
     mcmc **chains = setup_chains();
     double *mean = (double *)calloc(n_beta, sizeof(double));
     double logprob = 0, previous_beta = 0;
     unsigned int i, j;
+    run_summary summary;
+    const int from_summary = run_summary_requested();
     read_calibration_file(chains, n_beta);
-    for (i = 0; i < n_beta; i++) {
+    if (from_summary)
+        read_summary_or_die(&summary, n_beta, get_n_par(chains[0]));
+    for (i = 0; i < n_beta && from_summary; i++) {
+        printf("reading probabilities of chain %d\r", i);
+        fflush(stdout);
+        if (summary.n == 0) {
+            fprintf(stderr, "calculating data probability failed: no data points found in %s\n", RUN_SUMMARY_FILE);
+            return;
+        }
+        mean[i] = summary.prob_sum[i] / get_beta(chains[i]) / summary.n;
+    }
+    if (from_summary)
+        run_summary_free(&summary);
+    for (i = 0; i < n_beta && !from_summary; i++) {
         char name[100];
         FILE *f;
         double total, part, sum = 0;
@@ -74,6 +104,17 @@ void analyse_data_probability() {
     free(mean);
 }
 
+/* the same from the batch sums of a run summary: batch k's sum is batch_sums[k] */
+static double batch_means_error_summary(double mean, const double *batch_sums, uint64_t nbatches, unsigned long batchsize) {
+    double errorsum = 0;
+    uint64_t k;
+    for (k = 0; k < nbatches; k++) {
+        const double d = batch_sums[k] / batchsize - mean;
+        errorsum += d * d;
+    }
+    return sqrt(errorsum / (int)nbatches);
+}
+
 /* spread of the batch means (batches of `batchsize` consecutive samples) around the mean */
 static double batch_means_error(double mean, const char *filename, unsigned long batchsize) {
     FILE *f = openfile(filename);
@@ -97,7 +138,7 @@ static double batch_means_error(double mean, const char *filename, unsigned long
 /* NBINS-bin density of one parameter's visited values (chain 0) over [min, max] of the prior box
  * (or of the data with -DHISTOGRAMS_MINMAX); the top edge is widened by 1e-4 of the range so the
  * maximum falls into the last bin.  Output: "<name>.histogram", lines "lower upper density". */
-static void marginal_distribution(mcmc **chains, unsigned int param, int find_minmax) {
+static void marginal_distribution(mcmc **chains, unsigned int param, int find_minmax, const run_summary *summary) {
     const char *name = get_params_descr(chains[0])[param];
     double lo = get_params_min_for(chains[0], param), hi = get_params_max_for(chains[0], param);
     double bins[NBINS], edges[NBINS + 1], v, total = 0, mean = 0, var = 0, width, err;
@@ -106,7 +147,10 @@ static void marginal_distribution(mcmc **chains, unsigned int param, int find_mi
     int b;
     sprintf(in_name, "%s-chain-%d.prob.dump", name, 0);
     sprintf(out_name, "%s.histogram", name);
-    if (get_column_count(in_name) != 1) {
+    if (summary != NULL) {
+        lo = summary->lo[param]; /* the range the device binned with */
+        hi = summary->hi[param];
+    } else if (get_column_count(in_name) != 1) {
         fprintf(stderr, "number of columns different in file %s\n", in_name);
         exit(1);
     }
@@ -128,8 +172,13 @@ static void marginal_distribution(mcmc **chains, unsigned int param, int find_mi
     memset(bins, 0, sizeof bins);
     printf("reading values: chain %3d parameter %s   \r", 0, name);
     fflush(stdout);
-    f = openfile(in_name);
-    while (fscanf(f, "%lf", &v) == 1) {
+    if (summary != NULL)
+        for (b = 0; b < NBINS; b++) {
+            bins[b] = (double)summary->hist[(size_t)param * NBINS + b];
+            total += bins[b];
+        }
+    f = summary != NULL ? NULL : openfile(in_name);
+    while (f != NULL && fscanf(f, "%lf", &v) == 1) {
         if (v < edges[0] || v >= edges[NBINS])
             continue;
         b = (int)((v - lo) / (hi - lo) * NBINS);
@@ -142,7 +191,8 @@ static void marginal_distribution(mcmc **chains, unsigned int param, int find_mi
         bins[b] += 1;
         total += 1;
     }
-    fclose(f);
+    if (f != NULL)
+        fclose(f);
     width = (hi - lo) / NBINS;
     f = fopen(out_name, "w");
     assert(f != NULL);
@@ -165,7 +215,15 @@ static void marginal_distribution(mcmc **chains, unsigned int param, int find_mi
         }
         var /= wsum;
     }
-    err = batch_means_error(mean, in_name, (unsigned long)sqrt(total));
+    if (summary != NULL) {
+        const unsigned long want = (unsigned long)sqrt(total);
+        err = batch_means_error_summary(mean, summary->batch_sums + (size_t)param * (summary->max_batches + 1),
+                                        summary->n_batches, (unsigned long)summary->bs);
+        if (summary->bs != want)
+            fprintf(stderr, "%s: batch size %lu recorded in %s, floor(sqrt(%.0f values)) = %lu\n", name,
+                    (unsigned long)summary->bs, RUN_SUMMARY_FILE, total, want);
+    } else
+        err = batch_means_error(mean, in_name, (unsigned long)sqrt(total));
     printf("mcmc error estimate of %s: %f %s\n", name, err, (err > sqrt(var) * 0.01 ? "** high!" : " (ok)"));
     printf("Note: Include a error estimate in your publication!\n");
 }
@@ -177,12 +235,23 @@ void analyse_marginal_distributions() {
     int find_minmax = 0;
     unsigned int i;
     FILE *plot;
+    run_summary summary;
+    const int from_summary = run_summary_requested();
     read_calibration_file(chains, n_beta);
 #ifdef HISTOGRAMS_MINMAX
     find_minmax = 1;
+    if (from_summary) {
+        fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
+                        "would have to be known before the first sample\n");
+        exit(1);
+    }
 #endif
+    if (from_summary)
+        read_summary_or_die(&summary, n_beta, n_par);
     for (i = 0; i < n_par; i++)
-        marginal_distribution(chains, i, find_minmax);
+        marginal_distribution(chains, i, find_minmax, from_summary ? &summary : NULL);
+    if (from_summary)
+        run_summary_free(&summary);
     plot = fopen("marginal_distributions.gnuplot", "w");
     assert(plot != NULL);
     fprintf(plot, "# set terminal png size %d,%d; set output \"marginal_distributions.png\"\n", 600, 300 * n_par);

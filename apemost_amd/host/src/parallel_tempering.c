@@ -12,6 +12,7 @@
 #include "parallel_tempering_config.h"
 #include "parallel_tempering_run.h"
 #include "apemost_bridge.h"
+#include "run_summary.h"
 #include "debug.h"
 #include "define_defaults.h"
 #include "gsl_helper.h"
@@ -199,15 +200,23 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            of every chain (tools/samples_bin.py reads it and expands it into the text files)
  *   binary:all   the same with the parameter vector of every chain
  *   thin:N   keep every N-th iteration only (either format)
+ *   summary  fold the kept rows on the device into summary.bin (run_summary.h): what `analyse` prints,
+ *            without the sample files.  On its own (summary, summary,thin:N) no sample file is written;
+ *            with text or binary[:all] those are written as well
  * The reference prints one line per chain per step, which at device speed is the whole run time
  * (SURVEY 8 f1); binary and thinned sinks are the additive options for that. */
 #define SINK_MAGIC "APEMOSTB"
+#ifndef NBINS
+#define NBINS 200 /* the analyse phase's histogram bins (analyse.c) */
+#endif
 #ifndef PROB_FILES_OPEN_MAX
 #define PROB_FILES_OPEN_MAX 256 /* beyond this many chains prob-chain files are opened per batch */
 #endif
 
 typedef struct {
     int binary;               /* 0 text, 1 binary, 2 binary with every chain's parameters */
+    int summary;              /* summary.bin from the device (APEMOST_DUMP token `summary`) */
+    int files;                /* sample files are written (not so for `summary` alone) */
     unsigned int n_param_chains; /* binary: chains 0..n-1 carry their parameter vectors */
     double *pack;             /* binary: one batch, packed */
     size_t pack_capacity;
@@ -221,25 +230,37 @@ typedef struct {
 
 static void sink_parse(sample_sink *k) {
     const char *spec = getenv("APEMOST_DUMP");
+    int format_given = 0;
     k->binary = 0;
     k->thin = 1;
+    k->summary = 0;
     while (spec != NULL && *spec != 0) {
         if (strncmp(spec, "binary:all", 10) == 0)
-            k->binary = 2;
+            k->binary = 2, format_given = 1;
         else if (strncmp(spec, "binary", 6) == 0)
-            k->binary = 1;
+            k->binary = 1, format_given = 1;
         else if (strncmp(spec, "text", 4) == 0)
-            k->binary = 0;
+            k->binary = 0, format_given = 1;
         else if (strncmp(spec, "thin:", 5) == 0 && atol(spec + 5) > 0)
             k->thin = (unsigned long)atol(spec + 5);
+        else if (strncmp(spec, "summary", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
+            k->summary = 1;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary; got '%s'\n", spec);
             exit(1);
         }
         spec = strchr(spec, ',');
         if (spec != NULL)
             spec++;
     }
+    k->files = !k->summary || format_given;
+#ifdef HISTOGRAMS_MINMAX
+    if (k->summary) {
+        fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
+                        "would have to be known before the first sample\n");
+        exit(1);
+    }
+#endif
 }
 
 static FILE *open_or_die(const char *name, const char *mode) {
@@ -266,6 +287,8 @@ static void sink_open(sample_sink *k, mcmc **chains, unsigned int n_beta, unsign
     k->pack = NULL;
     k->pack_capacity = 0;
     k->n_param_chains = 0;
+    if (!k->files)
+        return;
     if (k->binary) {
         unsigned char header[64];
         uint32_t u32[4], u32b;
@@ -427,6 +450,104 @@ static void sink_close(sample_sink *k) {
     }
 }
 
+/* APEMOST_DUMP=summary: one device summary per shard (chain 0's histograms on shard 0).  The batch size
+ * of the error estimate is floor(sqrt(samples planned)); --append loads summary.bin and keeps its own. */
+static void summary_open(run_summary *r, apemost_ladder *l, mcmc **chains, const unsigned int *lo,
+                         unsigned int n_shards, unsigned int n_swap, unsigned long iter, unsigned long max_iterations,
+                         unsigned long thin, const char *mode) {
+    const unsigned int n_beta = lo[n_shards], n_par = get_n_par(chains[0]);
+    unsigned long end = iter;
+    uint64_t planned, b;
+    run_summary old;
+    int resumed = 0;
+    unsigned int j, p;
+    if (max_iterations == 0) {
+        fprintf(stderr, "APEMOST_DUMP=summary needs a bounded run (MAX_ITERATIONS > 0): the batch size of the "
+                        "error estimate is fixed before the first sample\n");
+        exit(1);
+    }
+    if (end < max_iterations) /* whole rounds: the last one may run past max_iterations */
+        end += (max_iterations - iter + n_swap - 1) / n_swap * n_swap;
+    planned = end / thin - iter / thin; /* iterations thin, 2 thin, ... are kept */
+    memset(&old, 0, sizeof old);
+    if (mode[0] == 'a' && run_summary_read(RUN_SUMMARY_FILE, &old) == 0) {
+        if (old.n_beta != n_beta || old.n_par != n_par || old.nbins != NBINS || old.thin != thin || old.n_hist != 1) {
+            fprintf(stderr, "%s: written by a run of another shape (chains, parameters, NBINS or thin:N); "
+                            "cannot append\n", RUN_SUMMARY_FILE);
+            exit(1);
+        }
+        resumed = 1;
+    } else if (mode[0] == 'a')
+        fprintf(stderr, "--append: no %s, the summary starts with this run\n", RUN_SUMMARY_FILE);
+    r->n_beta = n_beta;
+    r->n_par = n_par;
+    r->nbins = NBINS;
+    r->n_hist = 1;
+    r->thin = thin;
+    r->n = resumed ? old.n : 0;
+    r->bs = resumed ? old.bs : (uint64_t)sqrt((double)planned);
+    if (r->bs < 1)
+        r->bs = 1;
+    r->max_batches = run_summary_batches(r->n + planned, r->bs);
+    run_summary_alloc(r);
+    for (p = 0; p < n_par; p++) {
+        r->lo[p] = get_params_min_for(chains[0], p);
+        r->hi[p] = get_params_max_for(chains[0], p);
+        if (resumed && (old.lo[p] != r->lo[p] || old.hi[p] != r->hi[p])) {
+            fprintf(stderr, "%s: parameter %u had the range [%g, %g], now [%g, %g]; cannot append\n",
+                    RUN_SUMMARY_FILE, p, old.lo[p], old.hi[p], r->lo[p], r->hi[p]);
+            exit(1);
+        }
+    }
+    if (resumed) {
+        memcpy(r->prob_sum, old.prob_sum, n_beta * sizeof(double));
+        memcpy(r->hist, old.hist, (size_t)n_par * NBINS * sizeof(uint64_t));
+        for (p = 0; p < n_par; p++) /* closed batches and the open one, at the new capacity's stride */
+            for (b = 0; b <= old.n_batches; b++)
+                r->batch_sums[p * (r->max_batches + 1) + b] = old.batch_sums[p * (old.max_batches + 1) + b];
+        run_summary_free(&old);
+    }
+    r->n_batches = run_summary_batches(r->n, r->bs);
+    for (j = 0; j < n_shards; j++) {
+        apemost_hip_sampler *s = apemost_ladder_shard(l, j);
+        apemost_hip_summary_config c;
+        apemost_hip_summary_view v;
+        c.n_hist_chains = j == 0 ? 1 : 0;
+        c.nbins = NBINS;
+        c.batch_size = r->bs;
+        c.max_batches = r->max_batches;
+        c.lo = r->lo;
+        c.hi = r->hi;
+        apemost_hip_or_die(apemost_hip_summary_begin(s, &c), "summary_begin");
+        if (resumed) {
+            v.n = &r->n;
+            v.prob_sum = r->prob_sum + lo[j];
+            v.hist = j == 0 ? r->hist : NULL;
+            v.batch_sums = j == 0 ? r->batch_sums : NULL;
+            v.n_batches = NULL;
+            apemost_hip_or_die(apemost_hip_summary_set(s, &v), "summary_set");
+        }
+    }
+}
+
+/* collects the shards' summaries into summary.bin */
+static void summary_close(run_summary *r, apemost_ladder *l, const unsigned int *lo, unsigned int n_shards) {
+    unsigned int j;
+    for (j = 0; j < n_shards; j++) {
+        apemost_hip_sampler *s = apemost_ladder_shard(l, j);
+        apemost_hip_summary_view v;
+        v.n = &r->n;
+        v.prob_sum = r->prob_sum + lo[j];
+        v.hist = j == 0 ? r->hist : NULL;
+        v.batch_sums = j == 0 ? r->batch_sums : NULL;
+        v.n_batches = j == 0 ? &r->n_batches : NULL;
+        apemost_hip_or_die(apemost_hip_summary_get(s, &v), "summary_get");
+        apemost_hip_or_die(apemost_hip_summary_end(s), "summary_end");
+    }
+    run_summary_write(RUN_SUMMARY_FILE, r);
+    run_summary_free(r);
+}
+
 /* The sampler loop.  The device runs batches of rounds (apemost_hip_run: n_swap steps per chain,
  * one swap attempt, ... -- the body of the reference's loop, src/parallel_tempering.c:392-409);
  * while batch k+1 runs, the rows of batch k drain into pinned host memory on a second stream and
@@ -450,7 +571,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     uint64_t *h_counts[2][APEMOST_MAX_SHARDS];
     double *d_packed[2] = {NULL, NULL};
     unsigned int lo[APEMOST_MAX_SHARDS + 1], n_shards, i, j;
-    int k = 0, device_pack;
+    int k = 0, device_pack, rows_on_host;
+    run_summary summary;
 
     if (max_rounds < 1)
         max_rounds = 1;
@@ -478,8 +600,10 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             const size_t n_local = lo[j + 1] - lo[j];
             void *p = NULL;
             apemost_hip_or_die(apemost_hip_samples_alloc(s, max_rounds * n_swap, &d_samples[i][j]), "samples_alloc");
-            apemost_hip_or_die(apemost_hip_host_alloc(max_rounds * n_swap * n_local * (n_par + 2) * sizeof(double), &p),
-                               "host_alloc");
+            p = NULL; /* (a summary alone brings no rows to the host) */
+            if (sink.files)
+                apemost_hip_or_die(apemost_hip_host_alloc(max_rounds * n_swap * n_local * (n_par + 2) * sizeof(double), &p),
+                                   "host_alloc");
             h_samples[i][j] = (double *)p;
             /* (+ n_par doubles: chain 0's latest point behind the counters of a packed read) */
             apemost_hip_or_die(apemost_hip_host_alloc((2 * n_local + n_par) * sizeof(uint64_t), &p), "host_alloc");
@@ -488,7 +612,11 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     /* One shard and a sink that does not want every row as it is (binary records, thinning): the
      * device packs each batch into what will be written, so that only that crosses PCIe and the host
      * writes the pinned buffer without touching it. */
-    device_pack = n_shards == 1 && (sink.binary || sink.thin > 1);
+    device_pack = sink.files && n_shards == 1 && (sink.binary || sink.thin > 1);
+    rows_on_host = sink.files && !device_pack;
+    memset(&summary, 0, sizeof summary);
+    if (sink.summary)
+        summary_open(&summary, l, chains, lo, n_shards, n_swap, iter, max_iterations, sink.thin, mode);
     for (i = 0; i < 2 && device_pack; i++)
         apemost_hip_or_die(apemost_hip_samples_alloc(apemost_ladder_shard(l, 0), max_rounds * n_swap, &d_packed[i]),
                            "samples_alloc");
@@ -522,10 +650,21 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
                                                                    (int32_t)sink.n_param_chains, sink.binary ? 0 : 1, d_packed[k],
                                                                    h_samples[k][0], h_counts[k][0], &kept),
                                "samples_pack_read_async");
-        for (j = 0; j < n_shards && !device_pack; j++)
+        for (j = 0; j < n_shards && rows_on_host; j++)
             apemost_hip_or_die(apemost_hip_samples_read_async(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
                                                               h_samples[k][j], h_counts[k][j]),
                                "samples_read_async");
+        /* the summary folds the batch on the device, on the stream of those reads (the wait below covers it) */
+        for (j = 0; j < n_shards && sink.summary; j++)
+            apemost_hip_or_die(apemost_hip_summary_accumulate(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
+                                                              (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
+                               "summary_accumulate");
+        /* no sample files: only the counters and chain 0's latest point cross (a packed read that keeps no step) */
+        for (j = 0; j < n_shards && !sink.files; j++)
+            apemost_hip_or_die(apemost_hip_samples_pack_read_async(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
+                                                                   n_steps, 1, 0, 1, d_samples[k][j], (double *)h_counts[k][j],
+                                                                   h_counts[k][j], NULL),
+                               "samples_pack_read_async");
         PLAN_BATCH(iter_after, rounds_next);
         if (rounds_next > 0) /* the device goes on while this batch drains and is written */
             apemost_ladder_run(l, rounds_next, n_swap, d_samples[k ^ 1]);
@@ -533,7 +672,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             apemost_hip_or_die(apemost_hip_samples_wait(apemost_ladder_shard(l, j)), "samples_wait");
         if (device_pack)
             sink_write_packed(&sink, chains, h_samples[k][0], (unsigned long)kept);
-        else
+        else if (rows_on_host)
             sink_write(&sink, chains, h_samples[k], lo, n_shards, iter, n_steps);
         iter = iter_after;
         apemost_swap_round += rounds_now;
@@ -541,7 +680,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             /* chain 0's latest row and counters live in shard 0 */
             /* (a packed batch holds the kept iterations only -- an older one, or none: the packed read leaves
              * chain 0's point after the batch's last step behind the counters) */
-            const double *last = !device_pack ? h_samples[k][0] + (n_steps - 1) * (size_t)(lo[1] - lo[0]) * (n_par + 2)
+            const double *last = rows_on_host ? h_samples[k][0] + (n_steps - 1) * (size_t)(lo[1] - lo[0]) * (n_par + 2)
                                               : (const double *)(h_counts[k][0] + 2 * (lo[1] - lo[0]));
             const uint64_t accept0 = h_counts[k][0][0], reject0 = h_counts[k][0][lo[1] - lo[0]];
             if (dumpflag) {
@@ -571,6 +710,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     }
 #undef PLAN_BATCH
     apemost_ladder_download(l);
+    if (sink.summary)
+        summary_close(&summary, l, lo, n_shards);
     for (i = 0; i < 2; i++)
         for (j = 0; j < n_shards; j++) {
             apemost_hip_samples_free(apemost_ladder_shard(l, j), d_samples[i][j]);
@@ -591,15 +732,19 @@ void prepare_and_run_sampler(const unsigned long max_iterations, int append) {
     int n_swap = N_SWAP;
     char *mode = (append == 1 ? "a" : "w");
     mcmc **chains = setup_chains();
+    sample_sink wanted;
 #ifdef DUMP_ALL_CHAINS
     unsigned int i;
 #endif
     read_calibration_file(chains, n_beta);
-    mcmc_open_dump_files(chains[0], "-chain", 0, mode);
+    sink_parse(&wanted);
+    if (wanted.files) {
+        mcmc_open_dump_files(chains[0], "-chain", 0, mode);
 #ifdef DUMP_ALL_CHAINS
-    for (i = 1; i < n_beta; i++)
-        mcmc_open_dump_files(chains[i], "-chain", i, mode);
+        for (i = 1; i < n_beta; i++)
+            mcmc_open_dump_files(chains[i], "-chain", i, mode);
 #endif
+    }
     if (n_swap < 0) {
         n_swap = 2000 / n_beta;
         printf("automatic n_swap: %d\n", n_swap);

@@ -199,6 +199,62 @@ class HipSampler:
         self._adopt(d_samples)
         capi.check(self.L.apemost_hip_run(self._h, n_rounds, n_swap, d_samples))
 
+    # -- run summary (apemost_amd/summary.py) ------------------------------------------------
+    def summary_begin(self, lo=None, hi=None, n_hist_chains=1, nbins=200, batch_size=1, max_batches=0, thin=1):
+        """start an on-device summary: prob - prior sums of every chain, and histograms over [lo, hi] and
+        batch sums of batch_size (batch_means_error()) for chains 0 .. n_hist_chains-1.  `thin` is only
+        recorded with the summary (accumulate takes the rows' own skip/thin)."""
+        cfg = capi.SummaryConfig(n_hist_chains=n_hist_chains, nbins=nbins, batch_size=batch_size, max_batches=max_batches)
+        dp = C.POINTER(C.c_double)
+        self._sum_lo = None if lo is None else np.ascontiguousarray(lo, dtype=np.float64)
+        self._sum_hi = None if hi is None else np.ascontiguousarray(hi, dtype=np.float64)
+        if self._sum_lo is not None:
+            assert self._sum_lo.shape == (self.n_par,) and self._sum_hi.shape == (self.n_par,)
+            cfg.lo, cfg.hi = self._sum_lo.ctypes.data_as(dp), self._sum_hi.ctypes.data_as(dp)
+        capi.check(self.L.apemost_hip_summary_begin(self._h, C.byref(cfg)))
+        self._sum_cfg = dict(n_hist_chains=n_hist_chains, nbins=nbins, batch_size=batch_size, max_batches=max_batches,
+                             thin=thin)
+
+    def summary_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2] into the
+        summary; asynchronous (summary() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_summary_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def _summary_view(self, arrays):
+        return capi.SummaryView(n=arrays["n"].ctypes.data_as(capi._up), prob_sum=arrays["prob_sum"].ctypes.data_as(C.POINTER(C.c_double)),
+                                hist=arrays["hist"].ctypes.data_as(capi._up),
+                                batch_sums=arrays["batch_sums"].ctypes.data_as(C.POINTER(C.c_double)),
+                                n_batches=arrays["n_batches"].ctypes.data_as(capi._up))
+
+    def summary(self):
+        """the summary so far as a RunSummary (synchronises with the accumulates issued so far)"""
+        from .summary import RunSummary
+        c = self._sum_cfg
+        a = dict(n=np.zeros(1, dtype=np.uint64), prob_sum=np.zeros(self.n_chains),
+                 hist=np.zeros((c["n_hist_chains"], self.n_par, c["nbins"]), dtype=np.uint64),
+                 batch_sums=np.zeros((c["n_hist_chains"], self.n_par, c["max_batches"] + 1)),
+                 n_batches=np.zeros(1, dtype=np.uint64))
+        capi.check(self.L.apemost_hip_summary_get(self._h, C.byref(self._summary_view(a))))
+        lo = self._sum_lo if self._sum_lo is not None else np.zeros(self.n_par)
+        hi = self._sum_hi if self._sum_hi is not None else np.zeros(self.n_par)
+        return RunSummary(int(a["n"][0]), a["prob_sum"], a["hist"], a["batch_sums"], int(a["n_batches"][0]), lo, hi,
+                          c["batch_size"], c["thin"])
+
+    def summary_set(self, rs):
+        """load a RunSummary (a resumed run) into the summary begun with the same configuration"""
+        a = dict(n=np.array([rs.n], dtype=np.uint64), prob_sum=np.ascontiguousarray(rs.prob_sum, dtype=np.float64),
+                 hist=np.ascontiguousarray(rs.hist, dtype=np.uint64),
+                 batch_sums=np.ascontiguousarray(rs.batch_sums, dtype=np.float64),
+                 n_batches=np.array([rs.n_batches], dtype=np.uint64))
+        c = self._sum_cfg
+        assert a["prob_sum"].shape == (self.n_chains,)
+        assert a["hist"].shape == (c["n_hist_chains"], self.n_par, c["nbins"])
+        assert a["batch_sums"].shape == (c["n_hist_chains"], self.n_par, c["max_batches"] + 1)
+        capi.check(self.L.apemost_hip_summary_set(self._h, C.byref(self._summary_view(a))))
+
+    def summary_end(self):
+        capi.check(self.L.apemost_hip_summary_end(self._h))
+
     def edge_export(self, side, d_buf):
         capi.check(self.L.apemost_hip_edge_export(self._h, side, d_buf))
 

@@ -409,6 +409,55 @@ int apemost_hip_calibrate_progress(apemost_hip_sampler *s, double *rows, int32_t
 int apemost_hip_calibrate_stats(apemost_hip_sampler *s, uint64_t *segments, uint64_t *evaluations,
                                 uint64_t launches_by_waves[9], double seconds_by_waves[9]);
 
+/* ---- run summary: what `analyse` needs, folded on the device -------------------------------
+ * The three quantities the analyse phase computes from the dump files (apemost_amd/host/src/analyse.c),
+ * accumulated from the sample rows while they are still on the device:
+ *   n             kept samples so far (the same for every chain);
+ *   prob_sum[c]   sum of column n_par+1 (prob - prior) of chain c, a sequential `sum += v` in sample order
+ *                 (analyse_data_probability);
+ *   hist[h][p][b] counts of the values of parameter p of chain h < n_hist_chains in the nbins bins of
+ *                 marginal_distribution() over [lo[p], hi[p]] (top edge widened by (hi-lo)/10000; values
+ *                 outside, NaN included, are not counted);
+ *   batch_sums[h][p][k]  sequential sums of the batches of batch_means_error(): sample n (counted from 1)
+ *                 closes a batch when n % batch_size == batch_size - 1, so batch 0 holds batch_size - 1
+ *                 samples and every later one batch_size; k < n_batches are closed, slot n_batches holds
+ *                 the sum of the batch still open.  The array is [h][p][max_batches + 1].
+ * Every sum is one thread's chain of additions in sample order: the results are bitwise equal to the host
+ * loops, whatever the boundaries of the accumulate calls are.  Sharded ladders keep one summary per shard
+ * (n_hist_chains = 0 on all but the shard that holds chain 0); the caller concatenates prob_sum. */
+typedef struct {
+    int32_t n_hist_chains; /* chains 0 .. n_hist_chains-1 get histograms and batch sums (0 .. n_chains) */
+    int32_t nbins;         /* 1 .. 4096 */
+    uint64_t batch_size;   /* >= 1 */
+    uint64_t max_batches;  /* capacity: an accumulate that would close batch max_batches + 1 is invalid */
+    const double *lo, *hi; /* host [n_par]: the histogram range, finite, lo < hi (may be NULL without histograms) */
+} apemost_hip_summary_config;
+
+/* host arrays; any pointer may be NULL (that part is skipped) */
+typedef struct {
+    uint64_t *n;
+    double *prob_sum;   /* [n_chains] */
+    uint64_t *hist;     /* [n_hist_chains][n_par][nbins] */
+    double *batch_sums; /* [n_hist_chains][n_par][max_batches + 1] */
+    uint64_t *n_batches;
+} apemost_hip_summary_view;
+
+/* allocates and zeroes the accumulator (a summary begun before is dropped) */
+int apemost_hip_summary_begin(apemost_hip_sampler *s, const apemost_hip_summary_config *cfg);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2], the rows of
+ * the launches issued so far) into the summary.  Asynchronous: queued behind those launches on the stream of
+ * apemost_hip_samples_read_async, so launches issued afterwards overlap with it; apemost_hip_samples_wait (or
+ * summary_get) must have returned before d_samples is written again. */
+int apemost_hip_summary_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                   uint64_t thin);
+/* copies the summary out (synchronises with the accumulates issued so far) */
+int apemost_hip_summary_get(apemost_hip_sampler *s, const apemost_hip_summary_view *v);
+/* loads a summary saved by summary_get into a summary begun with the same configuration (a resumed run):
+ * n_batches, if given, must be the number that n closes */
+int apemost_hip_summary_set(apemost_hip_sampler *s, const apemost_hip_summary_view *v);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_summary_end(apemost_hip_sampler *s);
+
 /* ---- test hooks: device RNG conformance ------------------------------------ */
 /* n raw 32-bit outputs of rocRAND philox4x32_10 (seed, subsequence, offset) */
 int apemost_hip_rng_raw(int device, uint64_t seed, uint64_t subsequence, uint64_t offset, int32_t n,

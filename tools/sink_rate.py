@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """End-to-end rate of the C host's run phase per sample sink (BASELINE config 2: simplesin, 128
 chains x 1024 points): Metropolis steps/s from process start to exit, against the kernel-only rate
-of bench.py.  Writes into a scratch directory (default /dev/shm, a tmpfs).
+of bench.py, and the wall time of `analyse` on the summary and on the text dumps.  Writes into a scratch directory (default /dev/shm, a tmpfs).
 
     python tools/sink_rate.py [iterations] [scratch dir]"""
 import os
@@ -35,7 +35,8 @@ def main():
         env = dict(os.environ, APEMOST_SEED="1")
         for phase in ("calibrate_first", "calibrate_rest"):
             subprocess.check_call([exe, phase], cwd=base, env=env, stdout=subprocess.DEVNULL)
-        for mode, n in (("binary", iters), ("binary:all", iters), ("binary,thin:10", iters), ("text,thin:100", iters), ("text", iters // 30)):
+        for mode, n in (("binary", iters), ("summary", iters), ("binary:all", iters), ("binary,thin:10", iters),
+                        ("text,thin:100", iters), ("text", iters // 30)):
             work = os.path.join(top, mode.replace(",", "_").replace(":", ""))
             shutil.copytree(base, work)
             exe_n = exe
@@ -48,6 +49,11 @@ def main():
             size = sum(os.path.getsize(os.path.join(work, f)) for f in os.listdir(work))
             print("APEMOST_DUMP=%-16s %9d iterations x %d chains in %6.2f s = %.3g steps/s end to end, %.2f GB written"
                   % (mode, n, n_beta, dt, n * n_beta / dt, size / 1e9), flush=True)
+            if mode in ("summary", "text"):
+                # the analyse phase: from summary.bin, or from the dump files
+                t0 = time.time()
+                subprocess.check_call([exe_n, "analyse"], cwd=work, env=dict(env, APEMOST_DUMP=mode), stdout=subprocess.DEVNULL)
+                print("  analyse from %-9s %d iterations: %6.3f s" % (mode, n, time.time() - t0), flush=True)
             shutil.rmtree(work)
     finally:
         shutil.rmtree(top, ignore_errors=True)
