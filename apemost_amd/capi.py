@@ -83,6 +83,8 @@ EXPORTS = [
     "apemost_hip_rng_attempts", "apemost_hip_timer_begin", "apemost_hip_timer_end",
     "apemost_hip_summary_begin", "apemost_hip_summary_accumulate", "apemost_hip_summary_get",
     "apemost_hip_summary_set", "apemost_hip_summary_end",
+    "apemost_hip_samples_text_bound", "apemost_hip_samples_text_read_async", "apemost_hip_device_alloc",
+    "apemost_hip_device_free",
 ]
 
 _lib = None
@@ -177,6 +179,11 @@ def lib():
     L.apemost_hip_summary_get.argtypes = [vp, C.POINTER(SummaryView)]
     L.apemost_hip_summary_set.argtypes = [vp, C.POINTER(SummaryView)]
     L.apemost_hip_summary_end.argtypes = [vp]
+    L.apemost_hip_samples_text_bound.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, _up, _up, _up]
+    L.apemost_hip_samples_text_read_async.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, vp,
+                                                      C.c_uint64, vp, C.c_uint64, _up, C.c_uint64]
+    L.apemost_hip_device_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
+    L.apemost_hip_device_free.argtypes = [vp, vp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

@@ -2,6 +2,7 @@
 // (declared in include/apemost_hip.h).  Written for MI355X only.
 #include "pt_kernels.h"
 #include "pt_summary.h"
+#include "pt_text.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -1768,6 +1769,154 @@ extern "C" int apemost_hip_summary_end(apemost_hip_sampler *s) {
     if (s->copy_stream)
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     summary_free(s);
+    return APEMOST_HIP_OK;
+}
+
+// ---- the reference's text dumps, formatted on the device (pt_text.h) ----
+// One batch shape: its streams, the host text buffer (every line at its longest) and the device scratch
+// (the regions below, each 256-byte aligned).
+struct TextLayout {
+    u64 kept, n_streams, n_lines, n_tiles, text_bytes;
+    u64 at_slots, at_lens, at_sum, at_off, at_offsets, at_out, scratch_bytes;
+};
+
+static u64 text_align(u64 x) { return (x + 255) & ~(u64)255; }
+
+static TextLayout text_layout(const apemost_hip_sampler *s, u64 n_steps, u64 skip, u64 thin, int n_param_chains) {
+    TextLayout t;
+    const u64 head = (u64)n_param_chains * s->cfg.n_par, n = (u64)s->cfg.n_chains;
+    t.kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    t.n_streams = head + n;
+    t.n_lines = t.kept * t.n_streams;
+    t.n_tiles = (t.n_lines + kTextThreads - 1) / kTextThreads;
+    t.text_bytes = t.kept * (head * kTextParamLine + n * kTextProbLine);
+    u64 at = 0;
+    t.at_slots = at;
+    at += text_align(t.n_lines * kTextSlot);
+    t.at_lens = at;
+    at += text_align(t.n_lines);
+    t.at_sum = at;
+    at += text_align(t.n_tiles * sizeof(u64));
+    t.at_off = at;
+    at += text_align(t.n_tiles * sizeof(u64));
+    t.at_offsets = at;
+    at += text_align((t.n_streams + 1) * sizeof(u64));
+    t.at_out = at;
+    at += text_align(t.text_bytes);
+    t.scratch_bytes = at;
+    return t;
+}
+
+static int text_check(const apemost_hip_sampler *s, u64 n_steps, u64 skip, u64 thin, int32_t n_param_chains,
+                      const char *what) {
+    if (thin < 1 || n_param_chains < 0 || n_param_chains > s->cfg.n_chains)
+        return fail(APEMOST_HIP_ERR_INVALID, "%s: bad arguments", what);
+    // at most 2^36 lines per call: every size and offset stays far inside 64 bits, the grid inside 2^31
+    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    const u64 streams = (u64)n_param_chains * s->cfg.n_par + (u64)s->cfg.n_chains;
+    if (kept > ((u64)1 << 36) / streams)
+        return fail(APEMOST_HIP_ERR_INVALID, "%s: %llu kept steps of %llu lines: too many for one call", what,
+                    (unsigned long long)kept, (unsigned long long)streams);
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_samples_text_bound(apemost_hip_sampler *s, uint64_t n_steps, uint64_t skip, uint64_t thin,
+                                              int32_t n_param_chains, uint64_t *n_streams, uint64_t *text_bytes,
+                                              uint64_t *scratch_bytes) {
+    CHECK_S(s);
+    const int rc = text_check(s, n_steps, skip, thin, n_param_chains, "samples_text_bound");
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const TextLayout t = text_layout(s, n_steps, skip, thin, n_param_chains);
+    if (n_streams)
+        *n_streams = t.n_streams;
+    if (text_bytes)
+        *text_bytes = t.text_bytes;
+    if (scratch_bytes)
+        *scratch_bytes = t.scratch_bytes;
+    return APEMOST_HIP_OK;
+}
+
+// Queued on copy_stream behind everything launched so far on the sampler's stream, like
+// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
+extern "C" int apemost_hip_samples_text_read_async(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                                   uint64_t skip, uint64_t thin, int32_t n_param_chains,
+                                                   void *d_scratch, uint64_t scratch_bytes, char *host_text,
+                                                   uint64_t text_capacity, uint64_t *host_offsets, uint64_t n_offsets) {
+    CHECK_S(s);
+    int rc = text_check(s, n_steps, skip, thin, n_param_chains, "samples_text_read_async");
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const TextLayout t = text_layout(s, n_steps, skip, thin, n_param_chains);
+    if (!host_offsets || n_offsets < t.n_streams + 1)
+        return fail(APEMOST_HIP_ERR_INVALID, "samples_text_read_async: offsets hold %llu entries, the batch needs %llu",
+                    (unsigned long long)n_offsets, (unsigned long long)(t.n_streams + 1));
+    if (t.kept > 0 && (!d_samples || !d_scratch || !host_text))
+        return fail(APEMOST_HIP_ERR_INVALID, "samples_text_read_async: bad arguments");
+    if (t.kept > 0 && scratch_bytes < t.scratch_bytes)
+        return fail(APEMOST_HIP_ERR_INVALID, "samples_text_read_async: device scratch of %llu bytes, the batch needs %llu",
+                    (unsigned long long)scratch_bytes, (unsigned long long)t.scratch_bytes);
+    if (t.kept > 0 && text_capacity < t.text_bytes)
+        return fail(APEMOST_HIP_ERR_INVALID, "samples_text_read_async: host text buffer of %llu bytes, the batch needs %llu",
+                    (unsigned long long)text_capacity, (unsigned long long)t.text_bytes);
+    rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    // the error word of the launches so far rides on the sampler's stream, as for the other reads
+    HIP_TRY(hipMemcpyAsync(s->h_word, s->d.timeout_word(), sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    if (t.kept == 0) {
+        for (u64 i = 0; i <= t.n_streams; i++)
+            host_offsets[i] = 0;
+        return APEMOST_HIP_OK;
+    }
+    char *base = (char *)d_scratch;
+    TextArgs a;
+    a.rows = d_samples;
+    a.n_chains = s->cfg.n_chains;
+    a.n_par = s->cfg.n_par;
+    a.n_param_chains = n_param_chains;
+    a.skip = skip;
+    a.thin = thin;
+    a.n_kept = t.kept;
+    a.n_lines = t.n_lines;
+    a.n_tiles = t.n_tiles;
+    a.slots = base + t.at_slots;
+    a.lens = (unsigned char *)(base + t.at_lens);
+    a.tile_sum = (unsigned long long *)(base + t.at_sum);
+    a.tile_off = (unsigned long long *)(base + t.at_off);
+    a.offsets = (unsigned long long *)(base + t.at_offsets);
+    a.out = base + t.at_out;
+    hipLaunchKernelGGL(text_format_kernel, dim3((unsigned)t.n_tiles), dim3(kTextThreads), 0, s->copy_stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(kTextScanThreads), 0, s->copy_stream, a,
+                       (unsigned long long)t.n_streams);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(text_compact_kernel, dim3((unsigned)t.n_tiles), dim3(kTextThreads), 0, s->copy_stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host_offsets, a.offsets, (t.n_streams + 1) * sizeof(u64), hipMemcpyDeviceToHost,
+                           s->copy_stream));
+    // (the whole bound: the length of the text is known on the device only)
+    HIP_TRY(hipMemcpyAsync(host_text, a.out, t.text_bytes, hipMemcpyDeviceToHost, s->copy_stream));
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_device_alloc(apemost_hip_sampler *s, uint64_t bytes, void **d) {
+    CHECK_S(s);
+    if (!d || bytes == 0)
+        return fail(APEMOST_HIP_ERR_INVALID, "device_alloc: bad arguments");
+    HIP_TRY(hipMalloc(d, bytes));
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_device_free(apemost_hip_sampler *s, void *d) {
+    CHECK_S(s);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (d)
+        HIP_TRY(hipFree(d));
     return APEMOST_HIP_OK;
 }
 

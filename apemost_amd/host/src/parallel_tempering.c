@@ -203,8 +203,9 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *   summary  fold the kept rows on the device into summary.bin (run_summary.h): what `analyse` prints,
  *            without the sample files.  On its own (summary, summary,thin:N) no sample file is written;
  *            with text or binary[:all] those are written as well
- * The reference prints one line per chain per step, which at device speed is the whole run time
- * (SURVEY 8 f1); binary and thinned sinks are the additive options for that. */
+ * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
+ * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
+ * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
 #define SINK_MAGIC "APEMOSTB"
 #ifndef NBINS
 #define NBINS 200 /* the analyse phase's histogram bins (analyse.c) */
@@ -217,7 +218,7 @@ typedef struct {
     int binary;               /* 0 text, 1 binary, 2 binary with every chain's parameters */
     int summary;              /* summary.bin from the device (APEMOST_DUMP token `summary`) */
     int files;                /* sample files are written (not so for `summary` alone) */
-    unsigned int n_param_chains; /* binary: chains 0..n-1 carry their parameter vectors */
+    unsigned int n_param_chains; /* chains 0..n-1 have parameter files (text) / carry their parameter vectors (binary) */
     double *pack;             /* binary: one batch, packed */
     size_t pack_capacity;
     unsigned long thin;
@@ -289,15 +290,15 @@ static void sink_open(sample_sink *k, mcmc **chains, unsigned int n_beta, unsign
     k->n_param_chains = 0;
     if (!k->files)
         return;
+    /* the chains with parameter files (chain 0; all with -DDUMP_ALL_CHAINS) come first in the ladder */
+    while (k->n_param_chains < n_beta && chains[k->n_param_chains]->files != NULL)
+        k->n_param_chains++;
     if (k->binary) {
         unsigned char header[64];
         uint32_t u32[4], u32b;
         uint64_t u64v = k->thin;
         FILE *probe = mode[0] == 'w' ? NULL : fopen("samples.bin", "rb");
         const int fresh = probe == NULL;
-        /* the chains the text sink would write parameter files for come first in the ladder */
-        while (k->n_param_chains < n_beta && chains[k->n_param_chains]->files != NULL)
-            k->n_param_chains++;
         if (k->binary == 2)
             k->n_param_chains = n_beta;
         u32b = k->n_param_chains;
@@ -327,104 +328,87 @@ static void sink_open(sample_sink *k, mcmc **chains, unsigned int n_beta, unsign
     }
 }
 
-/* rows of iterations first+1 .. first+n_steps.  The rows arrive per shard: h[j] =
- * [n_steps][chains of shard j][n_par+2], shard j holding chains [lo[j], lo[j+1]) */
-static void sink_write(sample_sink *k, mcmc **chains, double *const *h, const unsigned int *lo, unsigned int n_shards,
+/* the binary sink, rows of iterations first+1 .. first+n_steps of a sharded ladder.  The rows arrive per
+ * shard: h[j] = [n_steps][chains of shard j][n_par+2], shard j holding chains [lo[j], lo[j+1]) */
+static void sink_write(sample_sink *k, double *const *h, const unsigned int *lo, unsigned int n_shards,
                        unsigned long first, unsigned long n_steps) {
     const unsigned int n_par = k->n_par;
     /* first kept step of this batch: iteration numbers count from 1 */
     const unsigned long skip = (k->thin - (first % k->thin) - 1) % k->thin;
+    /* one record per kept iteration: params of chains 0..n_param_chains-1, then (prob, prob - prior)
+     * of every chain; packed for the whole batch, written with one call */
+    const size_t record = (size_t)k->n_param_chains * n_par + 2 * (size_t)k->n_beta;
+    const size_t kept = skip < n_steps ? (n_steps - skip + k->thin - 1) / k->thin : 0;
     unsigned long step;
+    unsigned int i, j;
+    double *out;
+    if (kept * record > k->pack_capacity) {
+        free(k->pack);
+        k->pack_capacity = kept * record;
+        k->pack = (double *)malloc(k->pack_capacity * sizeof(double));
+        assert(k->pack != NULL);
+    }
+    out = k->pack;
+    for (step = skip; step < n_steps; step += k->thin) {
+        double *probs = out + (size_t)k->n_param_chains * n_par;
+        for (j = 0; j < n_shards; j++) {
+            const size_t row = (size_t)(lo[j + 1] - lo[j]) * (n_par + 2);
+            const double *r = h[j] + step * row;
+            for (i = lo[j]; i < lo[j + 1]; i++, r += n_par + 2) {
+                if (i < k->n_param_chains)
+                    memcpy(out + (size_t)i * n_par, r, n_par * sizeof(double));
+                probs[2 * i] = r[n_par];
+                probs[2 * i + 1] = r[n_par + 1];
+            }
+        }
+        out += record;
+    }
+    fwrite(k->pack, sizeof(double), kept * record, k->bin);
+    k->batches++;
+}
+
+/* the binary sink when the device has already packed the batch (apemost_hip_samples_pack_read_async; one
+ * shard): the pinned buffer is written as it is */
+static void sink_write_packed(sample_sink *k, const double *packed, unsigned long kept) {
+    const size_t record = (size_t)k->n_param_chains * k->n_par + 2 * (size_t)k->n_beta;
+    fwrite(packed, sizeof(double), kept * record, k->bin);
+    k->batches++;
+}
+
+/* chains of shard j, [lo[j], lo[j+1]), that have parameter files */
+static unsigned int sink_shard_param_chains(const sample_sink *k, const unsigned int *lo, unsigned int j) {
+    if (k->n_param_chains <= lo[j])
+        return 0;
+    return k->n_param_chains < lo[j + 1] ? k->n_param_chains - lo[j] : lo[j + 1] - lo[j];
+}
+
+/* the text sink: the batch as the device formatted it, per shard (apemost_hip_samples_text_read_async):
+ * stream c*n_par + p is parameter p of the shard's chain c, for its chains with parameter files, and the
+ * stream after those is the prob-chain file of each of its chains.  One fwrite per stream; ladders beyond
+ * the descriptor limit (the reference asserts n_beta < 100) open, append to and close one prob file at a time */
+static void sink_write_text(sample_sink *k, mcmc **chains, char *const *text, uint64_t *const *offsets,
+                            const unsigned int *lo, unsigned int n_shards) {
+    const unsigned int n_par = k->n_par;
     unsigned int i, j, p;
     char name[100];
-    if (k->binary) {
-        /* one record per kept iteration: params of chains 0..n_param_chains-1, then (prob, prob - prior)
-         * of every chain; packed for the whole batch, written with one call */
-        const size_t record = (size_t)k->n_param_chains * n_par + 2 * (size_t)k->n_beta;
-        const size_t kept = skip < n_steps ? (n_steps - skip + k->thin - 1) / k->thin : 0;
-        double *out;
-        if (kept * record > k->pack_capacity) {
-            free(k->pack);
-            k->pack_capacity = kept * record;
-            k->pack = (double *)malloc(k->pack_capacity * sizeof(double));
-            assert(k->pack != NULL);
-        }
-        out = k->pack;
-        for (step = skip; step < n_steps; step += k->thin) {
-            double *probs = out + (size_t)k->n_param_chains * n_par;
-            for (j = 0; j < n_shards; j++) {
-                const size_t row = (size_t)(lo[j + 1] - lo[j]) * (n_par + 2);
-                const double *r = h[j] + step * row;
-                for (i = lo[j]; i < lo[j + 1]; i++, r += n_par + 2) {
-                    if (i < k->n_param_chains)
-                        memcpy(out + (size_t)i * n_par, r, n_par * sizeof(double));
-                    probs[2 * i] = r[n_par];
-                    probs[2 * i + 1] = r[n_par + 1];
-                }
-            }
-            out += record;
-        }
-        fwrite(k->pack, sizeof(double), kept * record, k->bin);
-        k->batches++;
-        return;
-    }
-    /* chain-major: one file at a time stays hot, and ladders beyond the descriptor limit
-     * (the reference asserts n_beta < 100) open, append to and close one prob file at a time */
     for (j = 0; j < n_shards; j++) {
-        const size_t row = (size_t)(lo[j + 1] - lo[j]) * (n_par + 2);
-        for (i = lo[j]; i < lo[j + 1]; i++) {
+        const unsigned int n_head = sink_shard_param_chains(k, lo, j);
+        const uint64_t *off = offsets[j];
+        size_t s = 0;
+        for (i = lo[j]; i < lo[j] + n_head; i++)
+            for (p = 0; p < n_par; p++, s++)
+                if (chains[i]->files != NULL && chains[i]->files[p] != NULL)
+                    fwrite(text[j] + off[s], 1, off[s + 1] - off[s], chains[i]->files[p]);
+        for (i = lo[j]; i < lo[j + 1]; i++, s++) {
             FILE *pf = k->prob_files ? k->prob_files[i] : NULL;
-            FILE **vf = chains[i]->files;
             if (pf == NULL) {
                 sprintf(name, "prob-chain%d.dump", i);
                 pf = open_or_die(name, k->batches == 0 ? k->mode : "a");
             }
-            for (step = skip; step < n_steps; step += k->thin) {
-                const double *r = h[j] + step * row + (size_t)(i - lo[j]) * (n_par + 2);
-                if (vf != NULL)
-                    for (p = 0; p < n_par; p++)
-                        if (vf[p] != NULL)
-                            fprintf(vf[p], DUMP_FORMAT "\n", r[p]);
-                fprintf(pf, "%6e\t%6e\n", r[n_par], r[n_par + 1]);
-            }
+            fwrite(text[j] + off[s], 1, off[s + 1] - off[s], pf);
             if (k->prob_files == NULL)
                 fclose(pf);
         }
-    }
-    k->batches++;
-}
-
-/* the same batch when the device has already packed it (apemost_hip_samples_pack_read_async; one
- * shard): binary sinks write the pinned buffer as it is, the thinned text sink finds the kept rows
- * [kept][n_beta][n_par+2] */
-static void sink_write_packed(sample_sink *k, mcmc **chains, const double *packed, unsigned long kept) {
-    const unsigned int n_par = k->n_par;
-    unsigned long step;
-    unsigned int i, p;
-    char name[100];
-    if (k->binary) {
-        const size_t record = (size_t)k->n_param_chains * n_par + 2 * (size_t)k->n_beta;
-        fwrite(packed, sizeof(double), kept * record, k->bin);
-        k->batches++;
-        return;
-    }
-    for (i = 0; i < k->n_beta; i++) {
-        FILE *pf = k->prob_files ? k->prob_files[i] : NULL;
-        FILE **vf = chains[i]->files;
-        if (pf == NULL) {
-            sprintf(name, "prob-chain%d.dump", i);
-            pf = open_or_die(name, k->batches == 0 ? k->mode : "a");
-        }
-        for (step = 0; step < kept; step++) {
-            const double *r = packed + (step * k->n_beta + i) * (size_t)(n_par + 2);
-            if (vf != NULL)
-                for (p = 0; p < n_par; p++)
-                    if (vf[p] != NULL)
-                        fprintf(vf[p], DUMP_FORMAT "\n", r[p]);
-            fprintf(pf, "%6e\t%6e\n", r[n_par], r[n_par + 1]);
-        }
-        if (k->prob_files == NULL)
-            fclose(pf);
     }
     k->batches++;
 }
@@ -570,8 +554,13 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     double *d_samples[2][APEMOST_MAX_SHARDS], *h_samples[2][APEMOST_MAX_SHARDS];
     uint64_t *h_counts[2][APEMOST_MAX_SHARDS];
     double *d_packed[2] = {NULL, NULL};
+    /* the text sink, double-buffered per shard: device scratch, pinned text and stream offsets, and their sizes */
+    void *d_text[2][APEMOST_MAX_SHARDS];
+    char *h_text[2][APEMOST_MAX_SHARDS];
+    uint64_t *h_offsets[2][APEMOST_MAX_SHARDS];
+    uint64_t text_streams[APEMOST_MAX_SHARDS], text_bytes[APEMOST_MAX_SHARDS], text_scratch[APEMOST_MAX_SHARDS];
     unsigned int lo[APEMOST_MAX_SHARDS + 1], n_shards, i, j;
-    int k = 0, device_pack, rows_on_host;
+    int k = 0, device_pack, rows_on_host, text_sink;
     run_summary summary;
 
     if (max_rounds < 1)
@@ -594,26 +583,42 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     n_shards = apemost_ladder_shards(l);
     for (j = 0; j <= n_shards; j++)
         lo[j] = apemost_ladder_shard_first(l, j);
+    /* The text sink: the device formats each batch into the files' lines, so that only the text crosses
+     * PCIe and the host writes it.  The binary sink with one shard: the device packs each batch into its
+     * records, written as they arrive; with several shards the rows come to the host and are packed there. */
+    text_sink = sink.files && !sink.binary;
+    device_pack = sink.files && sink.binary && n_shards == 1;
+    rows_on_host = sink.files && sink.binary && n_shards > 1;
+    for (j = 0; j < n_shards && text_sink; j++) /* (the largest batch: max_rounds rounds, thinned from its start) */
+        apemost_hip_or_die(apemost_hip_samples_text_bound(apemost_ladder_shard(l, j), max_rounds * n_swap, 0, sink.thin,
+                                                          (int32_t)sink_shard_param_chains(&sink, lo, j), &text_streams[j],
+                                                          &text_bytes[j], &text_scratch[j]),
+                           "samples_text_bound");
     for (i = 0; i < 2; i++)
         for (j = 0; j < n_shards; j++) {
             apemost_hip_sampler *s = apemost_ladder_shard(l, j);
             const size_t n_local = lo[j + 1] - lo[j];
             void *p = NULL;
             apemost_hip_or_die(apemost_hip_samples_alloc(s, max_rounds * n_swap, &d_samples[i][j]), "samples_alloc");
-            p = NULL; /* (a summary alone brings no rows to the host) */
-            if (sink.files)
+            p = NULL; /* (the text sink and a summary alone bring no rows to the host) */
+            if (device_pack || rows_on_host)
                 apemost_hip_or_die(apemost_hip_host_alloc(max_rounds * n_swap * n_local * (n_par + 2) * sizeof(double), &p),
                                    "host_alloc");
             h_samples[i][j] = (double *)p;
             /* (+ n_par doubles: chain 0's latest point behind the counters of a packed read) */
             apemost_hip_or_die(apemost_hip_host_alloc((2 * n_local + n_par) * sizeof(uint64_t), &p), "host_alloc");
             h_counts[i][j] = (uint64_t *)p;
+            d_text[i][j] = NULL;
+            h_text[i][j] = NULL;
+            h_offsets[i][j] = NULL;
+            if (text_sink) {
+                apemost_hip_or_die(apemost_hip_device_alloc(s, text_scratch[j], &d_text[i][j]), "device_alloc");
+                apemost_hip_or_die(apemost_hip_host_alloc(text_bytes[j] > 0 ? text_bytes[j] : 1, &p), "host_alloc");
+                h_text[i][j] = (char *)p;
+                apemost_hip_or_die(apemost_hip_host_alloc((text_streams[j] + 1) * sizeof(uint64_t), &p), "host_alloc");
+                h_offsets[i][j] = (uint64_t *)p;
+            }
         }
-    /* One shard and a sink that does not want every row as it is (binary records, thinning): the
-     * device packs each batch into what will be written, so that only that crosses PCIe and the host
-     * writes the pinned buffer without touching it. */
-    device_pack = sink.files && n_shards == 1 && (sink.binary || sink.thin > 1);
-    rows_on_host = sink.files && !device_pack;
     memset(&summary, 0, sizeof summary);
     if (sink.summary)
         summary_open(&summary, l, chains, lo, n_shards, n_swap, iter, max_iterations, sink.thin, mode);
@@ -647,20 +652,29 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         if (device_pack)
             apemost_hip_or_die(apemost_hip_samples_pack_read_async(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
                                                                    (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin,
-                                                                   (int32_t)sink.n_param_chains, sink.binary ? 0 : 1, d_packed[k],
+                                                                   (int32_t)sink.n_param_chains, 0, d_packed[k],
                                                                    h_samples[k][0], h_counts[k][0], &kept),
                                "samples_pack_read_async");
         for (j = 0; j < n_shards && rows_on_host; j++)
             apemost_hip_or_die(apemost_hip_samples_read_async(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
                                                               h_samples[k][j], h_counts[k][j]),
                                "samples_read_async");
+        /* the text lines are formatted on the device, on the stream of those reads (the wait below covers it) */
+        for (j = 0; j < n_shards && text_sink; j++)
+            apemost_hip_or_die(apemost_hip_samples_text_read_async(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
+                                                                   (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin,
+                                                                   (int32_t)sink_shard_param_chains(&sink, lo, j), d_text[k][j],
+                                                                   text_scratch[j], h_text[k][j], text_bytes[j],
+                                                                   h_offsets[k][j], text_streams[j] + 1),
+                               "samples_text_read_async");
         /* the summary folds the batch on the device, on the stream of those reads (the wait below covers it) */
         for (j = 0; j < n_shards && sink.summary; j++)
             apemost_hip_or_die(apemost_hip_summary_accumulate(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
                                                               (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
                                "summary_accumulate");
-        /* no sample files: only the counters and chain 0's latest point cross (a packed read that keeps no step) */
-        for (j = 0; j < n_shards && !sink.files; j++)
+        /* no rows on the host (the text sink, or no sample files): only the counters and chain 0's latest point
+         * cross (a packed read that keeps no step) */
+        for (j = 0; j < n_shards && !device_pack && !rows_on_host; j++)
             apemost_hip_or_die(apemost_hip_samples_pack_read_async(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
                                                                    n_steps, 1, 0, 1, d_samples[k][j], (double *)h_counts[k][j],
                                                                    h_counts[k][j], NULL),
@@ -671,9 +685,11 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         for (j = 0; j < n_shards; j++)
             apemost_hip_or_die(apemost_hip_samples_wait(apemost_ladder_shard(l, j)), "samples_wait");
         if (device_pack)
-            sink_write_packed(&sink, chains, h_samples[k][0], (unsigned long)kept);
+            sink_write_packed(&sink, h_samples[k][0], (unsigned long)kept);
         else if (rows_on_host)
-            sink_write(&sink, chains, h_samples[k], lo, n_shards, iter, n_steps);
+            sink_write(&sink, h_samples[k], lo, n_shards, iter, n_steps);
+        else if (text_sink)
+            sink_write_text(&sink, chains, h_text[k], h_offsets[k], lo, n_shards);
         iter = iter_after;
         apemost_swap_round += rounds_now;
         if (iter % PRINT_PROB_INTERVAL == 0) {
@@ -717,6 +733,9 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             apemost_hip_samples_free(apemost_ladder_shard(l, j), d_samples[i][j]);
             apemost_hip_host_free(h_samples[i][j]);
             apemost_hip_host_free(h_counts[i][j]);
+            apemost_hip_device_free(apemost_ladder_shard(l, j), d_text[i][j]);
+            apemost_hip_host_free(h_text[i][j]);
+            apemost_hip_host_free(h_offsets[i][j]);
         }
     for (i = 0; i < 2; i++)
         if (d_packed[i] != NULL)

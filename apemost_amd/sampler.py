@@ -255,6 +255,38 @@ class HipSampler:
     def summary_end(self):
         capi.check(self.L.apemost_hip_summary_end(self._h))
 
+    # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------
+    def samples_text_bound(self, n_steps, skip=0, thin=1, n_param_chains=1):
+        """(streams, host text bytes, device scratch bytes) of one samples_text batch"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        capi.check(self.L.apemost_hip_samples_text_bound(self._h, n_steps, skip, thin, n_param_chains,
+                                                         *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def samples_text(self, d_samples, n_steps, skip=0, thin=1, n_param_chains=1):
+        """the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2] as the lines of
+        the reference's text dumps, formatted on the device: one bytes object per file -- "%.15e\\n" of parameter
+        p of chain c at index c*n_par + p for the chains 0 .. n_param_chains-1, then "%6e\\t%6e\\n" (prob,
+        prob - prior) of every chain.  Synchronous."""
+        import sys
+        torch = sys.modules.get("torch")        # rows that torch has just written must be complete
+        if torch is not None and torch.cuda.is_available():
+            torch.cuda.current_stream().synchronize()
+        n_streams, text_bytes, scratch_bytes = self.samples_text_bound(n_steps, skip, thin, n_param_chains)
+        scratch = C.c_void_p()
+        capi.check(self.L.apemost_hip_device_alloc(self._h, scratch_bytes, C.byref(scratch)))
+        text = np.zeros(max(text_bytes, 1), dtype=np.uint8)
+        offsets = np.zeros(n_streams + 1, dtype=np.uint64)
+        try:
+            capi.check(self.L.apemost_hip_samples_text_read_async(
+                self._h, d_samples, n_steps, skip, thin, n_param_chains, scratch, scratch_bytes,
+                text.ctypes.data, text_bytes, offsets.ctypes.data_as(capi._up), n_streams + 1))
+            capi.check(self.L.apemost_hip_samples_wait(self._h))
+        finally:
+            capi.check(self.L.apemost_hip_device_free(self._h, scratch))
+        raw = text.tobytes()
+        return [raw[int(offsets[i]):int(offsets[i + 1])] for i in range(n_streams)]
+
     def edge_export(self, side, d_buf):
         capi.check(self.L.apemost_hip_edge_export(self._h, side, d_buf))
 

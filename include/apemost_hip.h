@@ -325,6 +325,30 @@ int apemost_hip_samples_pack_read_async(apemost_hip_sampler *s, const double *d_
                                         uint64_t skip, uint64_t thin, int32_t n_param_chains, int32_t layout,
                                         double *d_packed, double *host_packed, uint64_t *counters, uint64_t *n_kept);
 int apemost_hip_samples_wait(apemost_hip_sampler *s);
+/* The kept steps skip, skip + thin, ... of d_samples as the reference's text dump lines, formatted ON THE DEVICE,
+ * byte for byte what glibc's printf gives: "%.15e\n" for the parameter files of chains 0 .. n_param_chains-1 and
+ * "%6e\t%6e\n" (prob, prob - prior) for the prob-chain files of every chain.  One byte stream per file, in this
+ * order: stream c*n_par + p holds parameter p of chain c (c < n_param_chains), stream n_param_chains*n_par + c
+ * the prob-chain lines of chain c.  Stream i is host_text[host_offsets[i], host_offsets[i+1]), and
+ * host_offsets[n_streams] is the batch's total.
+ * The sizing call gives, for a batch shape, n_streams, the host text buffer it needs (text_bytes: every line at
+ * its longest) and the DEVICE scratch it needs (scratch_bytes); any of the three pointers may be NULL.
+ * The read is queued like apemost_hip_summary_accumulate, behind the launches issued so far on the stream of
+ * apemost_hip_samples_read_async: launches issued afterwards overlap with it, and host_text / host_offsets
+ * (pinned: apemost_hip_host_alloc) hold the batch once apemost_hip_samples_wait has returned.  scratch_bytes,
+ * text_capacity and n_offsets (at least n_streams + 1) are the sizes of the buffers given: one that is too
+ * small gives APEMOST_HIP_ERR_INVALID, and then nothing is queued or copied. */
+int apemost_hip_samples_text_bound(apemost_hip_sampler *s, uint64_t n_steps, uint64_t skip, uint64_t thin,
+                                   int32_t n_param_chains, uint64_t *n_streams, uint64_t *text_bytes,
+                                   uint64_t *scratch_bytes);
+int apemost_hip_samples_text_read_async(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                        uint64_t skip, uint64_t thin, int32_t n_param_chains, void *d_scratch,
+                                        uint64_t scratch_bytes, char *host_text, uint64_t text_capacity,
+                                        uint64_t *host_offsets, uint64_t n_offsets);
+/* device memory on the sampler's device (the scratch of the text read); the free waits for the sampler's
+ * streams */
+int apemost_hip_device_alloc(apemost_hip_sampler *s, uint64_t bytes, void **d);
+int apemost_hip_device_free(apemost_hip_sampler *s, void *d);
 /* page-locked host memory for those reads */
 int apemost_hip_host_alloc(size_t bytes, void **p);
 int apemost_hip_host_free(void *p);
