@@ -18,6 +18,7 @@ FLAG_PROPOSAL_LOGISTIC, FLAG_PROPOSAL_UNIFORM, FLAG_RANDOMSWAP, FLAG_ADAPT = 8, 
 FLAG_TEST_REFUSE_COOPERATIVE, FLAG_TEST_WITHHOLD_PUBLISH = 128, 256   # test hooks (include/apemost_hip.h)
 FLAG_RWM = 512
 FLAG_USER_ONE_BARRIER = 1024   # APEMOST_MODEL_USER in the one-barrier kernels (include/apemost_hip.h)
+FLAG_SWAP_EVEN_ODD = 2048      # even-odd swap sweeps: every pair of the sweep's parity each round (include/apemost_hip.h)
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_RUNTIME, ERR_UNSUPPORTED, ERR_CALIBRATION = 0, -1, -2, -3, -4, -5
 
 _dp = C.POINTER(C.c_double)

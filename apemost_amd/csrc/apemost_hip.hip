@@ -313,8 +313,10 @@ struct apemost_hip_sampler {
         hipFunction_t round[9], calibrate[9], calc_model[9], loglike[9];
         hipFunction_t round_ob[9], calibrate_ob[9]; // (calibrate_ob: not for the variant instantiations)
     } user;
-    double *edge_out, *edge_in;  // edge records for in-process shard exchanges (created on first use)
-    hipEvent_t ev_exported, ev_imported;
+    // edge records for in-process shard exchanges (created on first use), one set per side (0 = lower edge,
+    // 1 = upper edge): under the even-odd schedule an interior shard exchanges on both edges before one launch
+    double *edge_out[2], *edge_in[2];
+    hipEvent_t ev_exported[2], ev_imported[2];
     hipStream_t copy_stream; // drains sample rows while the next launch runs (created on first use)
     hipEvent_t ev_copy;
     u64 *h_word;             // pinned copy of the launch error word, refreshed by every async read
@@ -479,10 +481,12 @@ static void release(apemost_hip_sampler *s) {
     summary_free(s); // (its kernels ran on copy_stream)
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
-    if (s->ev_exported)
-        hipEventDestroy(s->ev_exported);
-    if (s->ev_imported)
-        hipEventDestroy(s->ev_imported);
+    for (int k = 0; k < 2; k++) {
+        if (s->ev_exported[k])
+            hipEventDestroy(s->ev_exported[k]);
+        if (s->ev_imported[k])
+            hipEventDestroy(s->ev_imported[k]);
+    }
     if (s->h_word)
         hipHostFree(s->h_word);
     if (s->ev0)
@@ -773,8 +777,10 @@ static int create_body(apemost_hip_sampler *s) {
     s->sh.variant |= (int)((unsigned)cfg->n_cols << 16);
     if (cfg->flags & APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH)
         s->sh.variant |= kVariantTestWithhold;
+    if (cfg->flags & APEMOST_HIP_FLAG_SWAP_EVEN_ODD)
+        s->sh.variant |= kVariantEvenOdd;
     s->kmodel = cfg->model + ((cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
-                                             APEMOST_HIP_FLAG_RANDOMSWAP))
+                                             APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD))
                                   ? kVariantModel
                                   : 0);
     s->sh.x_abs_max = INFINITY; // until set_data
@@ -874,8 +880,11 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
                        APEMOST_HIP_FLAG_TWO_BARRIER_STEP | APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC |
                        APEMOST_HIP_FLAG_PROPOSAL_UNIFORM | APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_ADAPT |
                        APEMOST_HIP_FLAG_TEST_REFUSE_COOPERATIVE | APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH | APEMOST_HIP_FLAG_RWM |
-                       APEMOST_HIP_FLAG_USER_ONE_BARRIER))
+                       APEMOST_HIP_FLAG_USER_ONE_BARRIER | APEMOST_HIP_FLAG_SWAP_EVEN_ODD))
         return fail(APEMOST_HIP_ERR_INVALID, "unknown bits in flags: 0x%x", (unsigned)cfg->flags);
+    if ((cfg->flags & APEMOST_HIP_FLAG_SWAP_EVEN_ODD) &&
+        (cfg->flags & (APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH)))
+        return fail(APEMOST_HIP_ERR_INVALID, "SWAP_EVEN_ODD excludes RANDOMSWAP and TEST_WITHHOLD_PUBLISH");
     if ((cfg->flags & APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC) && (cfg->flags & APEMOST_HIP_FLAG_PROPOSAL_UNIFORM))
         return fail(APEMOST_HIP_ERR_INVALID, "PROPOSAL_LOGISTIC and PROPOSAL_UNIFORM are alternatives");
     if (!(cfg->adapt_target >= 0 && cfg->adapt_target < 1e300))
@@ -933,8 +942,10 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
     s->ev0 = s->ev1 = nullptr;
     s->copy_stream = nullptr;
     s->ev_copy = nullptr;
-    s->edge_out = s->edge_in = nullptr;
-    s->ev_exported = s->ev_imported = nullptr;
+    for (int k = 0; k < 2; k++) {
+        s->edge_out[k] = s->edge_in[k] = nullptr;
+        s->ev_exported[k] = s->ev_imported[k] = nullptr;
+    }
     s->h_word = nullptr;
     s->handoff_failed = false;
     s->waves = choose_waves(*cfg);
@@ -943,7 +954,7 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
     s->in_rwm = false;
     s->sum = {};
     if (s->waves == 6 && (cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
-                                        APEMOST_HIP_FLAG_RANDOMSWAP))) {
+                                        APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD))) {
         delete s;
         return fail(APEMOST_HIP_ERR_INVALID, "the proposal / swap variants are built for 1, 2, 4 or 8 waves per chain");
     }
@@ -1972,6 +1983,8 @@ extern "C" int64_t apemost_hip_swap_pair(uint64_t seed, uint64_t round, int64_t 
 extern "C" int64_t apemost_hip_sampler_swap_pair(const apemost_hip_sampler *s, uint64_t round) {
     if (!s || s->cfg.n_chains_global <= 1)
         return -1;
+    if (s->cfg.flags & APEMOST_HIP_FLAG_SWAP_EVEN_ODD) // the lowest lower chain of sweep `round`
+        return (int64_t)(round % 2) <= s->cfg.n_chains_global - 2 ? (int64_t)(round % 2) : -1;
     if (!(s->cfg.flags & APEMOST_HIP_FLAG_RANDOMSWAP))
         return apemost_hip_swap_pair(s->cfg.seed, round, s->cfg.n_chains_global);
     const uint64_t sub = APEMOST_HIP_SWAP_SUBSEQUENCE;
@@ -1992,6 +2005,15 @@ extern "C" int64_t apemost_hip_rounds_within_shard(const apemost_hip_sampler *s,
     if (lo == 0 && hi == n) // the whole ladder: no edge to straddle
         return max_rounds;
     int64_t k = 0;
+    if (s->cfg.flags & APEMOST_HIP_FLAG_SWAP_EVEN_ODD) {
+        // the edge between chains o-1 and o is straddled by the sweeps of the parity of o-1: at most two rounds
+        for (; k < max_rounds; k++) {
+            const int64_t par = (int64_t)((first_round + (uint64_t)k) % 2);
+            if ((lo > 0 && (lo - 1) % 2 == par) || (hi < n && (hi - 1) % 2 == par))
+                break;
+        }
+        return k;
+    }
     for (; k < max_rounds; k++) {
         const int64_t a = apemost_hip_sampler_swap_pair(s, first_round + (uint64_t)k);
         if (a >= 0 && (a == lo - 1 || (a == hi - 1 && a + 1 < n)))
@@ -2025,19 +2047,23 @@ extern "C" int apemost_hip_edge_import(apemost_hip_sampler *s, int side, const d
 }
 
 static int edge_buffers(apemost_hip_sampler *s) {
-    if (s->edge_out)
+    if (s->edge_out[0])
         return APEMOST_HIP_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
     const size_t n = (size_t)apemost_hip_edge_doubles(s->cfg.n_par);
     int rc;
-    if ((rc = dev_alloc(s, &s->edge_out, n)) || (rc = dev_alloc(s, &s->edge_in, n)))
-        return rc;
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_exported, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_imported, hipEventDisableTiming));
+    for (int k = 0; k < 2; k++) {
+        if ((rc = dev_alloc(s, &s->edge_out[k], n)) || (rc = dev_alloc(s, &s->edge_in[k], n)))
+            return rc;
+        HIP_TRY(hipEventCreateWithFlags(&s->ev_exported[k], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&s->ev_imported[k], hipEventDisableTiming));
+    }
     HIP_TRY(hipStreamSynchronize(s->stream));
     // recorded once so that the first exchange has something to wait on
-    HIP_TRY(hipEventRecord(s->ev_exported, s->stream));
-    HIP_TRY(hipEventRecord(s->ev_imported, s->stream));
+    for (int k = 0; k < 2; k++) {
+        HIP_TRY(hipEventRecord(s->ev_exported[k], s->stream));
+        HIP_TRY(hipEventRecord(s->ev_imported[k], s->stream));
+    }
     return APEMOST_HIP_OK;
 }
 
@@ -2054,31 +2080,43 @@ extern "C" int apemost_hip_edge_exchange(apemost_hip_sampler *lower, apemost_hip
     const size_t bytes = (size_t)apemost_hip_edge_doubles(lower->cfg.n_par) * sizeof(double);
     apemost_hip_sampler *side[2] = {lower, upper};
     // 1. each shard packs its edge chain, once its neighbour has finished reading the previous record
+    // (the lower shard works with the buffers and events of its upper edge, the upper shard with those of its
+    // lower edge: the two edges of an interior shard do not share any)
     for (int k = 0; k < 2; k++) {
         apemost_hip_sampler *me = side[k], *other = side[k ^ 1];
+        const int mine = k == 0 ? 1 : 0, theirs = mine ^ 1;
         HIP_TRY(hipSetDevice(me->cfg.device));
-        HIP_TRY(hipStreamWaitEvent(me->stream, other->ev_imported, 0));
-        if ((rc = apemost_hip_edge_export(me, k == 0 ? 1 : 0, me->edge_out)))
+        HIP_TRY(hipStreamWaitEvent(me->stream, other->ev_imported[theirs], 0));
+        if ((rc = apemost_hip_edge_export(me, mine, me->edge_out[mine])))
             return rc;
-        HIP_TRY(hipEventRecord(me->ev_exported, me->stream));
+        HIP_TRY(hipEventRecord(me->ev_exported[mine], me->stream));
     }
     // 2. each shard pulls the neighbour's record into its halo row
     for (int k = 0; k < 2; k++) {
         apemost_hip_sampler *me = side[k], *other = side[k ^ 1];
+        const int mine = k == 0 ? 1 : 0, theirs = mine ^ 1;
         HIP_TRY(hipSetDevice(me->cfg.device));
-        HIP_TRY(hipStreamWaitEvent(me->stream, other->ev_exported, 0));
-        HIP_TRY(hipMemcpyPeerAsync(me->edge_in, me->cfg.device, other->edge_out, other->cfg.device, bytes, me->stream));
-        HIP_TRY(hipEventRecord(me->ev_imported, me->stream));
-        if ((rc = apemost_hip_edge_import(me, k == 0 ? 1 : 0, me->edge_in)))
+        HIP_TRY(hipStreamWaitEvent(me->stream, other->ev_exported[theirs], 0));
+        HIP_TRY(hipMemcpyPeerAsync(me->edge_in[mine], me->cfg.device, other->edge_out[theirs], other->cfg.device, bytes,
+                                   me->stream));
+        HIP_TRY(hipEventRecord(me->ev_imported[mine], me->stream));
+        if ((rc = apemost_hip_edge_import(me, mine, me->edge_in[mine])))
             return rc;
     }
     return APEMOST_HIP_OK;
 }
 
-// the shard pair (j, j+1) the swap attempt `index` straddles, or -1
-static int straddled_edge(apemost_hip_sampler **sh, int n_shards, u64 index) {
+// the first shard pair (j, j+1), j >= from, the swap attempt `index` straddles, or -1.  The reference's schedules
+// pick one pair; an even-odd sweep straddles every edge whose lower chain has the sweep's parity.
+static int straddled_edge(apemost_hip_sampler **sh, int n_shards, u64 index, int from = 0) {
+    if (sh[0]->cfg.flags & APEMOST_HIP_FLAG_SWAP_EVEN_ODD) {
+        for (int j = from; j + 1 < n_shards; j++)
+            if ((u64)(sh[j]->cfg.chain_offset + sh[j]->cfg.n_chains - 1) % 2 == index % 2)
+                return j;
+        return -1;
+    }
     const int64_t a = apemost_hip_sampler_swap_pair(sh[0], index);
-    for (int j = 0; a >= 0 && j + 1 < n_shards; j++)
+    for (int j = from; a >= 0 && j + 1 < n_shards; j++)
         if (a == sh[j]->cfg.chain_offset + sh[j]->cfg.n_chains - 1)
             return j;
     return -1;
@@ -2092,9 +2130,10 @@ extern "C" int apemost_hip_run_shards(apemost_hip_sampler **sh, int32_t n_shards
     for (int j = 0; j < n_shards; j++) {
         if (!sh[j] || sh[j]->cfg.chain_offset != next || sh[j]->cfg.n_chains_global != sh[0]->cfg.n_chains_global ||
             sh[j]->cfg.seed != sh[0]->cfg.seed || sh[j]->round != sh[0]->round ||
-            sh[j]->swap_pending != sh[0]->swap_pending)
+            sh[j]->swap_pending != sh[0]->swap_pending ||
+            ((sh[j]->cfg.flags ^ sh[0]->cfg.flags) & (APEMOST_HIP_FLAG_SWAP_EVEN_ODD | APEMOST_HIP_FLAG_RANDOMSWAP)))
             return fail(APEMOST_HIP_ERR_INVALID, "run_shards: shard %d does not continue the ladder (offset, seed, "
-                                                 "ladder size and swap position must agree)", j);
+                                                 "ladder size, swap schedule and swap position must agree)", j);
         next += sh[j]->cfg.n_chains;
     }
     if (next != sh[0]->cfg.n_chains_global)
@@ -2119,11 +2158,10 @@ extern "C" int apemost_hip_run_shards(apemost_hip_sampler **sh, int32_t n_shards
         uint64_t k = 1;
         while (k < limit && straddled_edge(sh, n_shards, first_inside + k - 1) < 0)
             k++;
-        if (pending) {
-            const int j = straddled_edge(sh, n_shards, sh[0]->round);
-            if (j >= 0 && (rc = apemost_hip_edge_exchange(sh[j], sh[j + 1])))
-                return rc;
-        }
+        if (pending) // (an even-odd sweep: each straddled edge; an interior shard can have both of its edges in it)
+            for (int j = straddled_edge(sh, n_shards, sh[0]->round); j >= 0; j = straddled_edge(sh, n_shards, sh[0]->round, j + 1))
+                if ((rc = apemost_hip_edge_exchange(sh[j], sh[j + 1])))
+                    return rc;
         for (int j = 0; j < n_shards; j++) {
             const size_t row = (size_t)sh[j]->cfg.n_chains * (sh[j]->cfg.n_par + 2);
             double *out = (d_samples && d_samples[j] && !finalise) ? d_samples[j] + r * n_swap * row : nullptr;

@@ -223,13 +223,37 @@ __device__ __forceinline__ long long swap_draws(const ChainShape &sh, u64 swap_i
     return (int)(nb * 1000 * u) % (nb - 1);
 }
 
+// APEMOST_HIP_FLAG_SWAP_EVEN_ODD (variant instantiations only): swap attempt r is sweep r, every pair
+// (a, a+1) of the global ladder with a % 2 == r % 2.  The partner of chain g comes from parity alone:
+// the lower chain of g's pair in that sweep, or -1 where g sits the sweep out (chain 0 in odd sweeps,
+// the top chain where the parity leaves it alone).
+__device__ __forceinline__ long long even_odd_lower(const ChainShape &sh, long long g, u64 swap_index) {
+    const long long a = g - (long long)(((u64)g ^ swap_index) & 1);
+    return (a < 0 || a + 1 >= sh.n_global) ? -1 : a;
+}
+// the pair of swap attempt `swap_index` as chain g sees it: its lower chain (-1: no attempt, or none
+// that involves g under the even-odd schedule) and the uniform of its acceptance test.  Even-odd: the
+// pair's own uniform, word 0 of block swap_index of subsequence APEMOST_HIP_SWAP_SUBSEQUENCE + 1 + a --
+// both chains of the pair, every shard and every rank derive the same word.
+template <bool VARIANTS>
+__device__ __forceinline__ long long swap_pair_of(const ChainShape &sh, long long g, u64 swap_index, double &u_accept) {
+    if (VARIANTS && (sh.variant & kVariantEvenOdd)) {
+        const long long a = even_odd_lower(sh, g, swap_index);
+        u_accept = 1;
+        if (a >= 0)
+            u_accept = u32_to_uniform(philox_block(sh.seed, APEMOST_HIP_SWAP_SUBSEQUENCE + 1 + (u64)a, swap_index).x);
+        return a;
+    }
+    return swap_draws<VARIANTS>(sh, swap_index, u_accept);
+}
+
 template <class E>
 __device__ __forceinline__ int swap_apply(E &e, const DevArrays &d, const ChainShape &sh, int c, int half,
                                           u64 swap_index, bool shared) {
     double u_accept;
-    const long long a = swap_draws<E::kVariants>(sh, swap_index, u_accept);
-    const double lc = log(u_accept);
     const long long g = sh.chain_offset + c;
+    const long long a = swap_pair_of<E::kVariants>(sh, g, swap_index, u_accept);
+    const double lc = log(u_accept);
     if (a < 0 || (g != a && g != a + 1))
         return -1;
     const int n = sh.n_par;
@@ -291,14 +315,21 @@ __device__ __forceinline__ void swap_at_launch_start(E &e, const DevArrays &d, c
 // records into half `half`, wait for each other, then decide (Guideline 16: payload and flag
 // are agent-scope sc1 stores drained by the storing wave; the consumer polls the flag relaxed,
 // takes one agent acquire, and reads the payload with agent-scope loads)
+// Even-odd sweeps: every chain hands off in every round, alternately with its upper and its lower neighbour.
+// Sweep r uses one half of the state block and sweep r+1 the other, so within a launch a half always serves the
+// same partner: memo(half) names the reader of two sweeps ago, whose ack is awaited before the row is written
+// again, and wait_for_reader at the launch's end waits for the latest reader of the half that chain_store fills.
+// No cycle of waits can form: a chain at the lowest sweep of the launch never waits for a chain behind it -- the
+// ack it needs is of two sweeps ago, which its partner (at the same sweep or ahead) has given, and the publish it
+// needs is of this sweep, which that partner makes after a wait of the same kind only.
 template <class E>
 __device__ __forceinline__ void swap_in_launch(E &e, const DevArrays &d, const ChainShape &sh, int c, int half,
                                                u64 swap_index, SwapMemo &memo) {
     if (sh.n_global <= 1 || e.wave != 0)
         return;
     double u_accept;
-    const long long a = swap_draws<E::kVariants>(sh, swap_index, u_accept);
     const long long g = sh.chain_offset + c;
+    const long long a = swap_pair_of<E::kVariants>(sh, g, swap_index, u_accept);
     if (a < 0 || (g != a && g != a + 1))
         return;
     const int partner = (g == a) ? c + 1 : c - 1;
@@ -440,10 +471,15 @@ __device__ __forceinline__ u64 rounds_restarting(const E &e, const RoundArgs &a,
     bool involved = false;
     const unsigned r = base + (unsigned)e.lane;
     if (a.sh.n_global > 1 && r >= 1 && r < a.n_rounds) {
-        double u_accept;
-        const long long pair = swap_draws<E::kVariants>(a.sh, a.round + r - (a.apply_swap ? 0 : 1), u_accept);
         const long long g = a.sh.chain_offset + c;
-        involved = pair >= 0 && (g == pair || g == pair + 1);
+        if (E::kVariants && (a.sh.variant & kVariantEvenOdd)) {
+            // even-odd sweeps: every round whose opening sweep gives this chain a partner; no Philox block
+            involved = even_odd_lower(a.sh, g, a.round + r - (a.apply_swap ? 0 : 1)) >= 0;
+        } else {
+            double u_accept;
+            const long long pair = swap_draws<E::kVariants>(a.sh, a.round + r - (a.apply_swap ? 0 : 1), u_accept);
+            involved = pair >= 0 && (g == pair || g == pair + 1);
+        }
     }
     return __ballot(involved) | (base == 0 ? 1ull : 0ull);
 }

@@ -27,6 +27,10 @@ class ShardedLadder:
        `HipShardEngine` below is the product engine; the gloo tests plug in an oracle-backed one."""
 
     def __init__(self, engine, n_global, chain_offset, n_local, rank, world, dist=None):
+        # (2048 = capi.FLAG_SWAP_EVEN_ODD: a sweep can straddle both edges of a shard; _exchange_if_edge serves one pair)
+        if getattr(engine, "flags", 0) & 2048:
+            raise ValueError("ShardedLadder drives one pair per swap attempt: it does not run the even-odd swap "
+                             "schedule (FLAG_SWAP_EVEN_ODD); use in-process shards (apemost_hip_run_shards)")
         self.e, self.n_global, self.lo, self.hi = engine, n_global, chain_offset, chain_offset + n_local
         self.rank, self.world, self.dist = rank, world, dist
         self.round = 0
@@ -199,6 +203,10 @@ class HipShardEngine:
         self.n_rec = 3 + 2 * sampler.n_par
         # (torch None: a single rank without torch in the process -- bench.py --no-torch; no exchange ever happens)
         self._ext = torch.cuda.ExternalStream(sampler.stream) if torch is not None else None
+
+    @property
+    def flags(self):
+        return self.s.cfg.flags
 
     def swap_pair(self, round_):
         return self.s.swap_pair(round_)

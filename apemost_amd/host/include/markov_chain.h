@@ -25,6 +25,11 @@
 #if defined(PROPOSAL_LOGISTIC) && defined(PROPOSAL_UNIFORM)
 #error "PROPOSAL_LOGISTIC and PROPOSAL_UNIFORM are alternatives"
 #endif
+/* -DSWAP_EVEN_ODD (not in the reference): every neighbour pair of the round's parity attempts a swap each round,
+ * APEMOST_HIP_FLAG_SWAP_EVEN_ODD in include/apemost_hip.h; a swap schedule of its own, not a RANDOMSWAP variety */
+#if defined(SWAP_EVEN_ODD) && defined(RANDOMSWAP)
+#error "SWAP_EVEN_ODD and RANDOMSWAP are alternatives"
+#endif
 /* -DRWM (src/parallel_tempering.c:268-281, src/markov_chain.c:342-367): carried as APEMOST_HIP_FLAG_RWM since
  * round 4 -- the reference's own call site does not compile (a two-argument call of markov_chain_step);
  * include/apemost_hip.h states the semantics the engine gives it.  MINIMAL_STEPWIDTH / MAXIMAL_STEPWIDTH keep

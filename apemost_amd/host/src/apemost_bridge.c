@@ -174,6 +174,9 @@ static apemost_hip_sampler *create_sampler(const mcmc *m, int model, unsigned in
 #ifdef RANDOMSWAP
     cfg.flags |= APEMOST_HIP_FLAG_RANDOMSWAP;
 #endif
+#ifdef SWAP_EVEN_ODD /* not in the reference: even-odd swap sweeps (include/apemost_hip.h) */
+    cfg.flags |= APEMOST_HIP_FLAG_SWAP_EVEN_ODD;
+#endif
 #ifdef ADAPT
     if (run_ladder)
         cfg.flags |= APEMOST_HIP_FLAG_ADAPT;

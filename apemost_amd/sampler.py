@@ -180,6 +180,17 @@ class HipSampler:
         """lower chain of the pair swap attempt `round_` picks under this sampler's swap schedule"""
         return int(self.L.apemost_hip_sampler_swap_pair(self._h, round_))
 
+    def swap_attempts(self, pair, first_round, n_rounds):
+        """how often the pair (pair, pair + 1) of the global ladder is attempted in the swap attempts first_round ..
+        first_round + n_rounds - 1: a pure function of the schedule, so that swapcount / attempts is the per-pair
+        swap rate a ladder is tuned with.  Even-odd sweeps: the sweeps of the pair's parity."""
+        if not 0 <= pair <= self.n_chains_global - 2 or n_rounds <= 0:
+            return 0
+        if self.cfg.flags & capi.FLAG_SWAP_EVEN_ODD:
+            first = first_round + ((pair - first_round) % 2)     # the first sweep of the pair's parity
+            return max(0, (first_round + n_rounds - first + 1) // 2)
+        return sum(1 for r in range(first_round, first_round + n_rounds) if self.swap_pair(r) == pair)
+
     def rounds_within_shard(self, first_round, max_rounds):
         """how many swap attempts from `first_round` on (at most max_rounds) do not straddle an edge of this shard"""
         return int(self.L.apemost_hip_rounds_within_shard(self._h, first_round, max_rounds))

@@ -80,7 +80,9 @@ enum {
  * attempt q of parameter p's proposal at tick t = block (t<<24)|q of slot p, words 0,1;
  * accept uniform of tick t = word 0 of block t<<24 of slot n_par; swap attempt number r =
  * block r of the swap subsequence (word 0 pair choice, word 1 accept; with
- * APEMOST_HIP_FLAG_RANDOMSWAP words 1 and 2, word 0 being the swap_probability draw).
+ * APEMOST_HIP_FLAG_RANDOMSWAP words 1 and 2, word 0 being the swap_probability draw; with
+ * APEMOST_HIP_FLAG_SWAP_EVEN_ODD pair a of sweep r reads word 0 of block r of subsequence
+ * APEMOST_HIP_SWAP_SUBSEQUENCE + 1 + a).
  * Non-Gaussian proposals read word 0 of the attempt's block. */
 #define APEMOST_HIP_STREAMS_PER_CHAIN 256
 #define APEMOST_HIP_TICK_SHIFT 24
@@ -148,7 +150,32 @@ enum {
      * likelihood wave and the chain's wave call apemost_user_finish() and apply the reference's check_accept to its
      * result: the same decisions, bit for bit, as the two-phase kernels, if finish() keeps the contract stated in
      * include/apemost_device_model.h.  hiprtc compiles four more kernels at create time. */
-    APEMOST_HIP_FLAG_USER_ONE_BARRIER = 1024
+    APEMOST_HIP_FLAG_USER_ONE_BARRIER = 1024,
+    /* Even-odd swap sweeps (deterministic even-odd, Okabe 2001 / Syed 2019), not in the reference:
+     * "swap attempt r" -- swap-stream position r, what apemost_hip_set_round / get_round count -- is SWEEP r: every
+     * pair (a, a+1) of the GLOBAL ladder with a % 2 == r % 2, 0 <= a <= n_chains_global - 2, is attempted.  The
+     * pairs of a sweep are disjoint, so their order does not matter; a chain without a partner in sweep r sits it
+     * out (chain 0 in odd sweeps, the top chain where the parity leaves it alone).
+     * Each pair is decided and applied by the reference's own primitives, unchanged: check_swap_probability
+     * (r = beta_a p_b / beta_b + beta_b p_a / beta_a - (p_a + p_b), swap iff r > ln U, ln 0 = -inf) and
+     * parallel_tempering_do_swap with its quirks (prob is not exchanged; the larger prob_best and its point are
+     * copied over; swapcount of the lower chain counts), src/parallel_tempering_interaction.c:25-42, 99-123.
+     * Only the schedule is new.
+     * RNG: the uniform U of pair a in sweep r is word 0 of Philox block r of subsequence
+     * APEMOST_HIP_SWAP_SUBSEQUENCE + 1 + a (a = global index of the lower chain).  Chain streams use subsequences
+     * below 2^63 and the reference schedules' swap stream is 2^63 itself: nothing collides.  Both chains of a pair,
+     * every shard and every rank derive the same word; results do not depend on launch boundaries, waves per chain
+     * or the number of shards.
+     * Limits: excludes APEMOST_HIP_FLAG_RANDOMSWAP and APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH
+     * (APEMOST_HIP_ERR_INVALID); combines with the proposal-law bits, with ADAPT and RWM (every round is then a
+     * launch of its own) and with a user-supplied model (hiprtc compiles the variant kernels).  Runs in the variant
+     * kernel instantiations, like RANDOMSWAP: 1, 2, 4 or 8 waves per chain.  The calibration has no swaps: its
+     * results are the same with and without the flag.  apemost_hip_sampler_swap_pair gives the lowest lower chain
+     * of sweep r (r % 2, or -1 when that is not a pair of the ladder); on a sharded ladder an edge between chains
+     * o-1 and o is straddled by the sweeps with r % 2 == (o-1) % 2, so apemost_hip_rounds_within_shard gives at
+     * most two rounds, and apemost_hip_run_shards exchanges on every straddled edge before such a launch.  The
+     * torch.distributed driver (distributed.ShardedLadder) does not run this schedule. */
+    APEMOST_HIP_FLAG_SWAP_EVEN_ODD = 2048
 };
 
 typedef struct {
@@ -357,11 +384,13 @@ int apemost_hip_host_free(void *p);
  * `round` (parallel_tempering_decide_swap_now, interaction.c:87-97); -1 if n_global==1 */
 int64_t apemost_hip_swap_pair(uint64_t seed, uint64_t round, int64_t n_chains_global);
 /* the same for this sampler's ladder and swap schedule (with APEMOST_HIP_FLAG_RANDOMSWAP the pair
- * comes from word 1 of the block) */
+ * comes from word 1 of the block; with APEMOST_HIP_FLAG_SWAP_EVEN_ODD the lowest lower chain of sweep
+ * `round`: round % 2 if that is <= n_chains_global - 2, else -1) */
 int64_t apemost_hip_sampler_swap_pair(const apemost_hip_sampler *s, uint64_t round);
 /* how many of the swap attempts first_round, first_round + 1, ... (at most max_rounds) pick a pair
  * that lies inside this sampler's shard or outside it altogether, i.e. stops at the first pair that
- * straddles one of the shard's edges: the rounds a sharded ladder may put into one launch */
+ * straddles one of the shard's edges: the rounds a sharded ladder may put into one launch (even-odd
+ * sweeps: stops at the first sweep whose parity puts a pair across one of the edges) */
 int64_t apemost_hip_rounds_within_shard(const apemost_hip_sampler *s, uint64_t first_round, int64_t max_rounds);
 
 /* sharded ladders: the swap partner across a shard edge.  side 0 = lower
