@@ -86,6 +86,7 @@ EXPORTS = [
     "apemost_hip_summary_set", "apemost_hip_summary_end",
     "apemost_hip_samples_text_bound", "apemost_hip_samples_text_read_async", "apemost_hip_device_alloc",
     "apemost_hip_device_free",
+    "apemost_hip_create_batch", "apemost_hip_n_ladders", "apemost_hip_set_data_ladder",
 ]
 
 _lib = None
@@ -121,6 +122,9 @@ def lib():
     L.apemost_hip_device_count.argtypes = [C.POINTER(C.c_int)]
     L.apemost_hip_device_info.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), _up]
     L.apemost_hip_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
+    L.apemost_hip_create_batch.argtypes = [C.POINTER(Config), C.c_int32, _up, C.POINTER(vp)]
+    L.apemost_hip_n_ladders.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.apemost_hip_set_data_ladder.argtypes = [vp, C.c_int32, _dp]
     L.apemost_hip_destroy.argtypes = [vp]
     L.apemost_hip_synchronize.argtypes = [vp]
     L.apemost_hip_stream.argtypes = [vp, C.POINTER(vp)]

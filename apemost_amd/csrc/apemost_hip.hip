@@ -332,6 +332,12 @@ struct apemost_hip_sampler {
     double *rwm_keep;            // APEMOST_HIP_FLAG_RWM: what the extra step of a round must not be seen to change
     bool in_rwm;
     // the run summary (apemost_hip_summary_begin .. end): accumulated by summary_kernel on copy_stream
+    // a ladder batch (apemost_hip_create_batch): n_ladders independent ladders of `per_ladder` chains in one grid;
+    // cfg.n_chains = cfg.n_chains_global = their product, sh.n_global = per_ladder, cfg.seed = seeds[0]
+    bool batch;
+    int n_ladders, per_ladder;
+    std::vector<u64> seeds;        // [n_ladders] (empty for an ordinary sampler)
+    std::vector<double> x_abs_max; // [n_ladders] of each ladder's data
     struct {
         bool open;
         int n_hist, nbins;
@@ -732,6 +738,18 @@ static int user_model_build(apemost_hip_sampler *s) {
     return rc;
 }
 
+// the two words per ladder a batch keeps behind its counters (DevArrays::ladder_words)
+static int ladder_words_upload(apemost_hip_sampler *s) {
+    std::vector<u64> w(2 * (size_t)s->n_ladders);
+    for (int b = 0; b < s->n_ladders; b++) {
+        w[2 * b] = s->seeds[b];
+        memcpy(&w[2 * b + 1], &s->x_abs_max[b], sizeof(double));
+    }
+    HIP_TRY(hipMemcpyAsync(s->d.ladder_words(), w.data(), w.size() * sizeof(u64), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return APEMOST_HIP_OK;
+}
+
 // the part of apemost_hip_create that can fail after the sampler object exists
 static int create_body(apemost_hip_sampler *s) {
     const apemost_hip_config *cfg = &s->cfg;
@@ -755,16 +773,18 @@ static int create_body(apemost_hip_sampler *s) {
     d.n = cfg->n_chains;
     d.np = cfg->n_par;
     double *data = nullptr;
-    if ((rc = dev_alloc(s, &d.f, d.f_count())) || (rc = dev_alloc(s, &d.u, d.u_count())) ||
-        (rc = dev_alloc(s, &data, (size_t)cfg->n_cols * cfg->n_data)))
+    if ((rc = dev_alloc(s, &d.f, d.f_count())) || (rc = dev_alloc(s, &d.u, d.u_count() + (s->batch ? 2 * (size_t)s->n_ladders : 0))) ||
+        (rc = dev_alloc(s, &data, (size_t)cfg->n_cols * cfg->n_data * s->n_ladders)))
         return rc;
     d.data = data;
+    if (s->batch && (rc = ladder_words_upload(s)))
+        return rc;
 
     s->sh.n_par = cfg->n_par;
     s->sh.n_data = cfg->n_data;
     s->sh.n_chains = cfg->n_chains;
     s->sh.chain_offset = cfg->chain_offset;
-    s->sh.n_global = cfg->n_chains_global;
+    s->sh.n_global = s->batch ? s->per_ladder : cfg->n_chains_global;
     s->sh.seed = cfg->seed;
     s->sh.consts.sigma = cfg->sigma;
     s->sh.consts.hmin = cfg->hmin;
@@ -779,8 +799,10 @@ static int create_body(apemost_hip_sampler *s) {
         s->sh.variant |= kVariantTestWithhold;
     if (cfg->flags & APEMOST_HIP_FLAG_SWAP_EVEN_ODD)
         s->sh.variant |= kVariantEvenOdd;
-    s->kmodel = cfg->model + ((cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
-                                             APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD))
+    if (s->batch)
+        s->sh.variant |= kVariantBatch;
+    s->kmodel = cfg->model + (((cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
+                                              APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD)) || s->batch)
                                   ? kVariantModel
                                   : 0);
     s->sh.x_abs_max = INFINITY; // until set_data
@@ -856,10 +878,10 @@ static int create_body(apemost_hip_sampler *s) {
     return APEMOST_HIP_OK;
 }
 
-extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sampler **out) {
-    if (!cfg || !out)
-        return fail(APEMOST_HIP_ERR_INVALID, "cfg/out is NULL");
-    *out = nullptr;
+// seeds == nullptr: an ordinary sampler; else a batch of n_ladders ladders of per_ladder chains, *cfg already
+// describing the whole grid (apemost_hip_create_batch)
+static int create_impl(const apemost_hip_config *cfg, int n_ladders, int per_ladder, const uint64_t *seeds,
+                       apemost_hip_sampler **out) {
     if (cfg->abi_version != APEMOST_HIP_ABI_VERSION)
         return fail(APEMOST_HIP_ERR_INVALID, "ABI version %d, library has %d", cfg->abi_version,
                     APEMOST_HIP_ABI_VERSION);
@@ -953,10 +975,17 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
     s->rwm_keep = nullptr;
     s->in_rwm = false;
     s->sum = {};
-    if (s->waves == 6 && (cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
-                                        APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD))) {
+    s->batch = seeds != nullptr;
+    s->n_ladders = n_ladders;
+    s->per_ladder = per_ladder;
+    if (seeds) {
+        s->seeds.assign(seeds, seeds + n_ladders);
+        s->x_abs_max.assign(n_ladders, INFINITY); // until set_data
+    }
+    if (s->waves == 6 && (s->batch || (cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
+                                                     APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD)))) {
         delete s;
-        return fail(APEMOST_HIP_ERR_INVALID, "the proposal / swap variants are built for 1, 2, 4 or 8 waves per chain");
+        return fail(APEMOST_HIP_ERR_INVALID, "the proposal / swap variants and ladder batches are built for 1, 2, 4 or 8 waves per chain");
     }
     rc = create_body(s);
     if (rc != APEMOST_HIP_OK) {
@@ -964,6 +993,60 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
         return rc;
     }
     *out = s;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sampler **out) {
+    if (!cfg || !out)
+        return fail(APEMOST_HIP_ERR_INVALID, "cfg/out is NULL");
+    *out = nullptr;
+    return create_impl(cfg, 1, cfg->n_chains, nullptr, out);
+}
+
+// A ladder batch: what it cannot do is refused here, before any device is touched, so that nothing runs
+// silently as a single ladder (the list: include/apemost_hip.h).
+extern "C" int apemost_hip_create_batch(const apemost_hip_config *cfg, int32_t n_ladders, const uint64_t *seeds,
+                                        apemost_hip_sampler **out) {
+    if (!cfg || !out)
+        return fail(APEMOST_HIP_ERR_INVALID, "cfg/out is NULL");
+    *out = nullptr;
+    if (!seeds || n_ladders < 1)
+        return fail(APEMOST_HIP_ERR_INVALID, "create_batch: n_ladders %d needs that many seeds", n_ladders);
+    if (cfg->abi_version != APEMOST_HIP_ABI_VERSION)
+        return fail(APEMOST_HIP_ERR_INVALID, "ABI version %d, library has %d", cfg->abi_version, APEMOST_HIP_ABI_VERSION);
+    if (cfg->model == APEMOST_MODEL_USER)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "create_batch: a user-supplied device model does not run in ladder batches");
+    const struct {
+        int bit;
+        const char *name;
+    } refused[] = {{APEMOST_HIP_FLAG_RANDOMSWAP, "RANDOMSWAP"},
+                   {APEMOST_HIP_FLAG_ADAPT, "ADAPT"},
+                   {APEMOST_HIP_FLAG_RWM, "RWM"},
+                   {APEMOST_HIP_FLAG_TEST_REFUSE_COOPERATIVE, "TEST_REFUSE_COOPERATIVE"},
+                   {APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH, "TEST_WITHHOLD_PUBLISH"},
+                   {APEMOST_HIP_FLAG_COOPERATIVE_LAUNCH, "COOPERATIVE_LAUNCH"},
+                   {APEMOST_HIP_FLAG_USER_ONE_BARRIER, "USER_ONE_BARRIER"}};
+    for (const auto &r : refused)
+        if (cfg->flags & r.bit)
+            return fail(APEMOST_HIP_ERR_UNSUPPORTED, "create_batch: APEMOST_HIP_FLAG_%s does not run in ladder batches", r.name);
+    if (cfg->chain_offset != 0 || cfg->n_chains_global != cfg->n_chains)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED,
+                    "create_batch: ladder batches are not sharded (chain_offset %lld, n_chains_global %lld, n_chains %d)",
+                    (long long)cfg->chain_offset, (long long)cfg->n_chains_global, cfg->n_chains);
+    if (cfg->n_chains < 1 || (long long)cfg->n_chains * n_ladders > 2000000)
+        return fail(APEMOST_HIP_ERR_INVALID, "create_batch: %d ladders of %d chains: 1 .. 2000000 chains in all", n_ladders,
+                    cfg->n_chains);
+    apemost_hip_config grid = *cfg; // the whole grid: what the geometry, the residency check and every view index
+    grid.n_chains = cfg->n_chains * n_ladders;
+    grid.n_chains_global = grid.n_chains;
+    grid.seed = seeds[0];
+    return create_impl(&grid, n_ladders, cfg->n_chains, seeds, out);
+}
+
+extern "C" int apemost_hip_n_ladders(apemost_hip_sampler *s, int32_t *n_ladders) {
+    if (!s || !n_ladders)
+        return fail(APEMOST_HIP_ERR_INVALID, "sampler / n_ladders is NULL");
+    *n_ladders = s->n_ladders;
     return APEMOST_HIP_OK;
 }
 
@@ -1048,6 +1131,8 @@ extern "C" int apemost_hip_launch_policy(apemost_hip_sampler *s, int32_t *one_ba
 
 extern "C" int apemost_hip_set_chain_offset(apemost_hip_sampler *s, int64_t chain_offset) {
     CHECK_S(s);
+    if (s->batch)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "set_chain_offset: ladder batches are not sharded");
     if (chain_offset < 0 || chain_offset + s->cfg.n_chains > s->cfg.n_chains_global)
         return fail(APEMOST_HIP_ERR_INVALID, "chain offset %lld outside the ladder", (long long)chain_offset);
     s->cfg.chain_offset = chain_offset;
@@ -1055,8 +1140,8 @@ extern "C" int apemost_hip_set_chain_offset(apemost_hip_sampler *s, int64_t chai
     return APEMOST_HIP_OK;
 }
 
-extern "C" int apemost_hip_set_data(apemost_hip_sampler *s, const double *data_rowmajor) {
-    CHECK_S(s);
+// ladder < 0: every ladder gets the matrix
+static int set_data_impl(apemost_hip_sampler *s, int ladder, const double *data_rowmajor) {
     if (!data_rowmajor)
         return fail(APEMOST_HIP_ERR_INVALID, "data is NULL");
     const int n = s->cfg.n_data, nc = s->cfg.n_cols;
@@ -1069,11 +1154,35 @@ extern "C" int apemost_hip_set_data(apemost_hip_sampler *s, const double *data_r
         if (!(ax <= x_abs_max)) // also catches NaN
             x_abs_max = std::isfinite(ax) ? ax : INFINITY;
     }
-    s->sh.x_abs_max = x_abs_max;
-    HIP_TRY(hipMemcpyAsync((void *)s->d.data, col.data(), col.size() * sizeof(double),
-                           hipMemcpyHostToDevice, s->stream));
+    for (int b = ladder < 0 ? 0 : ladder; b < (ladder < 0 ? s->n_ladders : ladder + 1); b++) {
+        HIP_TRY(hipMemcpyAsync((void *)(s->d.data + (size_t)b * col.size()), col.data(), col.size() * sizeof(double),
+                               hipMemcpyHostToDevice, s->stream));
+        if (s->batch)
+            s->x_abs_max[b] = x_abs_max;
+    }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    return APEMOST_HIP_OK;
+    if (!s->batch) {
+        s->sh.x_abs_max = x_abs_max;
+        return APEMOST_HIP_OK;
+    }
+    // (the batch kernels take each ladder's own figure from its ladder words; the shared one is the largest)
+    s->sh.x_abs_max = 0;
+    for (double x : s->x_abs_max)
+        if (!(x <= s->sh.x_abs_max))
+            s->sh.x_abs_max = x;
+    return ladder_words_upload(s);
+}
+
+extern "C" int apemost_hip_set_data(apemost_hip_sampler *s, const double *data_rowmajor) {
+    CHECK_S(s);
+    return set_data_impl(s, -1, data_rowmajor);
+}
+
+extern "C" int apemost_hip_set_data_ladder(apemost_hip_sampler *s, int32_t ladder, const double *data_rowmajor) {
+    CHECK_S(s);
+    if (ladder < 0 || ladder >= s->n_ladders)
+        return fail(APEMOST_HIP_ERR_INVALID, "set_data_ladder: ladder %d outside [0,%d)", ladder, s->n_ladders);
+    return set_data_impl(s, ladder, data_rowmajor);
 }
 
 // copy one [n_chains][width] field between host and the interior rows of a device array
@@ -1285,7 +1394,21 @@ extern "C" int apemost_hip_calc_model(apemost_hip_sampler *s, int32_t first, int
     a.n_rounds = 0;
     a.round = 0;
     a.samples = nullptr;
-    return launch(s, K_CALC, count, &a, false);
+    if (!s->batch)
+        return launch(s, K_CALC, count, &a, false);
+    // a batch: the model-only kernel knows nothing of ladders (it uses no seed), so each ladder the range
+    // touches gets a launch of its own with that ladder's data
+    for (int b = first / s->per_ladder; b * s->per_ladder < first + count; b++) {
+        const int lo = b * s->per_ladder > first ? b * s->per_ladder : first;
+        const int hi = (b + 1) * s->per_ladder < first + count ? (b + 1) * s->per_ladder : first + count;
+        a.d.data = s->d.data + (size_t)b * s->cfg.n_cols * s->cfg.n_data;
+        a.sh.x_abs_max = s->x_abs_max[b];
+        a.first = lo;
+        const int rc = launch(s, K_CALC, hi - lo, &a, false);
+        if (rc)
+            return rc;
+    }
+    return APEMOST_HIP_OK;
 }
 
 static int loglike_on_device(apemost_hip_sampler *s, int32_t n, const double *params, const double *beta,
@@ -1318,6 +1441,8 @@ extern "C" int apemost_hip_loglike(apemost_hip_sampler *s, int32_t n, const doub
     CHECK_S(s);
     if (n < 1 || !params || !beta || !prob)
         return fail(APEMOST_HIP_ERR_INVALID, "loglike: bad arguments");
+    if (s->batch && s->n_ladders > 1)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "loglike: a batch of %d ladders has no single data matrix", s->n_ladders);
     const size_t np = s->cfg.n_par;
     // one scratch block: params [n][np], beta [n], prob [n], prior [n]
     double *scratch = nullptr;
@@ -1983,6 +2108,8 @@ extern "C" int64_t apemost_hip_swap_pair(uint64_t seed, uint64_t round, int64_t 
 extern "C" int64_t apemost_hip_sampler_swap_pair(const apemost_hip_sampler *s, uint64_t round) {
     if (!s || s->cfg.n_chains_global <= 1)
         return -1;
+    if (s->batch) // every ladder has a pair of its own: apemost_hip_swap_pair(seed_b, round, n_chains) answers per ladder
+        return fail(APEMOST_HIP_ERR_INVALID, "sampler_swap_pair is ambiguous on a ladder batch");
     if (s->cfg.flags & APEMOST_HIP_FLAG_SWAP_EVEN_ODD) // the lowest lower chain of sweep `round`
         return (int64_t)(round % 2) <= s->cfg.n_chains_global - 2 ? (int64_t)(round % 2) : -1;
     if (!(s->cfg.flags & APEMOST_HIP_FLAG_RANDOMSWAP))
@@ -2028,6 +2155,8 @@ extern "C" int apemost_hip_edge_export(apemost_hip_sampler *s, int side, double 
     CHECK_S(s);
     if (!d_buf || (side != 0 && side != 1))
         return fail(APEMOST_HIP_ERR_INVALID, "edge_export: bad arguments");
+    if (s->batch)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_export: ladder batches are not sharded");
     const int row = side == 0 ? 1 : s->cfg.n_chains;
     hipLaunchKernelGGL(edge_export_kernel, dim3(1), dim3(kWave), 0, s->stream, s->d, s->cfg.n_par, s->cur, row,
                        d_buf);
@@ -2039,6 +2168,8 @@ extern "C" int apemost_hip_edge_import(apemost_hip_sampler *s, int side, const d
     CHECK_S(s);
     if (!d_buf || (side != 0 && side != 1))
         return fail(APEMOST_HIP_ERR_INVALID, "edge_import: bad arguments");
+    if (s->batch)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_import: ladder batches are not sharded");
     const int row = side == 0 ? 0 : s->cfg.n_chains + 1;
     hipLaunchKernelGGL(edge_import_kernel, dim3(1), dim3(kWave), 0, s->stream, s->d, s->cfg.n_par, s->cur, row,
                        d_buf);
@@ -2070,6 +2201,8 @@ static int edge_buffers(apemost_hip_sampler *s) {
 extern "C" int apemost_hip_edge_exchange(apemost_hip_sampler *lower, apemost_hip_sampler *upper) {
     if (!lower || !upper || lower == upper)
         return fail(APEMOST_HIP_ERR_INVALID, "edge_exchange: two different samplers are needed");
+    if (lower->batch || upper->batch)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_exchange: ladder batches are not sharded");
     if (lower->cfg.n_par != upper->cfg.n_par || lower->cfg.n_chains_global != upper->cfg.n_chains_global ||
         lower->cfg.seed != upper->cfg.seed ||
         lower->cfg.chain_offset + lower->cfg.n_chains != upper->cfg.chain_offset)
@@ -2126,6 +2259,9 @@ extern "C" int apemost_hip_run_shards(apemost_hip_sampler **sh, int32_t n_shards
                                       double **d_samples) {
     if (!sh || n_shards < 1)
         return fail(APEMOST_HIP_ERR_INVALID, "run_shards: no shards");
+    for (int j = 0; j < n_shards; j++)
+        if (sh[j] && sh[j]->batch)
+            return fail(APEMOST_HIP_ERR_UNSUPPORTED, "run_shards: shard %d is a ladder batch; batches are not sharded", j);
     int64_t next = 0;
     for (int j = 0; j < n_shards; j++) {
         if (!sh[j] || sh[j]->cfg.chain_offset != next || sh[j]->cfg.n_chains_global != sh[0]->cfg.n_chains_global ||

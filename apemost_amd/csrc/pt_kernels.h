@@ -96,6 +96,31 @@ __device__ __forceinline__ void engine_setup(Engine<MODEL, WAVES, LDS_DATA, PROD
     }
 }
 
+// A ladder batch (kVariantBatch; the variant instantiations only, so the default kernels carry no test for
+// it): local chain c of the grid is chain c % n_global of ladder b = c / n_global.  The workgroup sees the
+// arguments of a stand-alone sampler of that ladder: the ladder's Philox key, its data matrix, and a chain
+// offset that turns the local index into the index inside the ladder (chain_offset + c = c % n_global), which
+// is what every RNG address and the swap schedule are made of.  Rows, counters, hand-off words and sample
+// rows stay indexed by the local chain; a pair (a, a + 1) has a + 1 < n_global, so partner rows never leave
+// the ladder.  Args: RoundArgs or CalibArgs.
+template <int MODEL, class Args>
+__device__ __forceinline__ std::conditional_t<(MODEL >= kVariantModel), Args, const Args &> ladder_view(const Args &grid, int c) {
+    if constexpr (MODEL >= kVariantModel) {
+        Args a = grid;
+        if (a.sh.variant & kVariantBatch) {
+            const int per = (int)a.sh.n_global, b = c / per;
+            const u64 *w = a.d.ladder_words() + 2 * (size_t)b;
+            a.sh.seed = w[0];
+            a.sh.x_abs_max = __longlong_as_double((long long)w[1]);
+            a.sh.chain_offset = -(long long)b * per;
+            a.d.data += (size_t)b * ((unsigned)a.sh.variant >> 16) * (size_t)a.sh.n_data;
+        }
+        return a;
+    } else {
+        return grid; // (the default kernels: the launch's own argument block, untouched)
+    }
+}
+
 // Load the chain into wave 0's registers from the read half of the state.
 template <class E>
 __device__ __forceinline__ void chain_load(E &e, const DevArrays &d, const ChainShape &sh, int c,
@@ -368,10 +393,11 @@ __device__ __forceinline__ void swap_in_launch(E &e, const DevArrays &d, const C
 constexpr int round_min_waves(int model, int waves) { return model % kVariantModel == APEMOST_MODEL_PULSE && waves == 1 ? APEMOST_PULSE_MIN_WAVES : 1; }
 template <int MODEL, int WAVES, bool LDS_DATA, bool PROD>
 __global__ __launch_bounds__(block_threads(WAVES, PROD)) __attribute__((amdgpu_waves_per_eu(round_min_waves(MODEL, WAVES), 8)))
-void pt_round_kernel(const RoundArgs a) {
+void pt_round_kernel(const RoundArgs grid) {
     extern __shared__ __align__(16) double lds[];
     Engine<MODEL, WAVES, LDS_DATA, PROD> e;
     const int c = blockIdx.x;
+    decltype(auto) a = ladder_view<MODEL>(grid, c);
     engine_setup(e, a.d, a.sh, c, lds);
     chain_load(e, a.d, a.sh, c, a.cur);
     e.pin_uniforms();
@@ -485,10 +511,11 @@ __device__ __forceinline__ u64 rounds_restarting(const E &e, const RoundArgs &a,
 }
 
 template <int MODEL, int LW, bool LDS_DATA, bool HELPER>
-__global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_per_eu(ob_waves_per_eu(LW, HELPER)))) void pt_round_ob_kernel(const RoundArgs a) {
+__global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_per_eu(ob_waves_per_eu(LW, HELPER)))) void pt_round_ob_kernel(const RoundArgs grid) {
     extern __shared__ __align__(16) double lds[];
     ObEngine<MODEL, LW, LDS_DATA, HELPER> e;
     const int c = blockIdx.x;
+    decltype(auto) a = ladder_view<MODEL>(grid, c);
     e.setup_common(a.d, a.sh, c, lds);
 #if APEMOST_OB_HELPER_SIMD
     if (HELPER && e.hw > LW + 3 && !e.is_helper())
@@ -906,7 +933,7 @@ __device__ __forceinline__ void calib_log_progress(const E &e, const CalibArgs &
 // 2048 chains wants both of its waves per SIMD resident)
 template <int MODEL, int WAVES, bool LDS_DATA, bool PROD>
 __global__ __launch_bounds__(block_threads(WAVES, PROD)) __attribute__((amdgpu_waves_per_eu(APEMOST_CALIB_MIN_WAVES(WAVES), 8)))
-void pt_calibrate_kernel(const CalibArgs a) {
+void pt_calibrate_kernel(const CalibArgs grid) {
     extern __shared__ __align__(16) double lds[];
     // The state machine's record lives in LDS, in the six control doubles behind the fail flag: it is
     // looked at between blocks only, and as registers it cost the one-wave kernels their second wave
@@ -915,8 +942,9 @@ void pt_calibrate_kernel(const CalibArgs a) {
     static_assert(sizeof(CalibRec) == 6 * sizeof(double), "the record fills the control words of the LDS carve");
     volatile CalibRec &r = *(volatile CalibRec *)(lds + 2 * kWave + 32 + 2);
     Engine<MODEL, WAVES, LDS_DATA, PROD> e;
-    const int slot = a.list[blockIdx.x];
-    const int c = a.first + slot;
+    const int slot = grid.list[blockIdx.x];
+    const int c = grid.first + slot;
+    decltype(auto) a = ladder_view<MODEL>(grid, c);
     const int n = a.sh.n_par;
     engine_setup(e, a.d, a.sh, c, lds);
     chain_load(e, a.d, a.sh, c, a.cur);

@@ -31,6 +31,8 @@ class ShardedLadder:
         if getattr(engine, "flags", 0) & 2048:
             raise ValueError("ShardedLadder drives one pair per swap attempt: it does not run the even-odd swap "
                              "schedule (FLAG_SWAP_EVEN_ODD); use in-process shards (apemost_hip_run_shards)")
+        if getattr(engine, "n_ladders", 1) > 1:
+            raise ValueError("ShardedLadder drives one ladder: a ladder batch (HipSampler.batch) is not sharded")
         self.e, self.n_global, self.lo, self.hi = engine, n_global, chain_offset, chain_offset + n_local
         self.rank, self.world, self.dist = rank, world, dist
         self.round = 0
@@ -207,6 +209,10 @@ class HipShardEngine:
     @property
     def flags(self):
         return self.s.cfg.flags
+
+    @property
+    def n_ladders(self):
+        return getattr(self.s, "n_ladders", 1)
 
     def swap_pair(self, round_):
         return self.s.swap_pair(round_)

@@ -54,11 +54,33 @@ def calc_beta_0(state, chain, stepwidth_factors):
     return float(np.max(r)) ** -0.5
 
 
+def ladder_view(arr, b, n_ladders):
+    """ladder b's part of a ladder-major array of a batch: the chain axis -- axis 1 of sample rows
+    [n_steps][n_ladders * n_chains][n_par + 2], axis 0 of everything else ([n_ladders * n_chains] or
+    [n_ladders * n_chains][n_par]) -- cut into n_ladders equal blocks.  A view, not a copy."""
+    arr = np.asarray(arr)
+    axis = 1 if arr.ndim == 3 else 0
+    total = arr.shape[axis]
+    if n_ladders < 1 or total % n_ladders or not 0 <= b < n_ladders:
+        raise ValueError("ladder %r of %r in an axis of %d chains" % (b, n_ladders, total))
+    per = total // n_ladders
+    return arr[:, b * per:(b + 1) * per] if axis == 1 else arr[b * per:(b + 1) * per]
+
+
 class HipSampler:
     def __init__(self, model, n_par, n_chains, data, seed=0, device=0, chain_offset=0,
                  n_chains_global=None, waves_per_chain=0, sigma=0.5, hmin=1e-6, lds_policy=0, circular_params=0,
-                 flags=0, adapt_target=0.0, device_model_source=None):
+                 flags=0, adapt_target=0.0, device_model_source=None, seeds=None):
+        """seeds=None: one ladder (a shard of it) of n_chains chains under `seed`.  seeds=[...]: a ladder batch
+        (include/apemost_hip.h, apemost_hip_create_batch; HipSampler.batch reads better): len(seeds) independent
+        ladders of n_chains chains EACH in one sampler, ladder b under seeds[b]; `data` is one matrix for every
+        ladder or [n_ladders][n_data][n_cols]; self.n_chains is then the total, self.chains_per_ladder the rest."""
         data = np.ascontiguousarray(data, dtype=np.float64)
+        if seeds is not None:
+            self._init_batch(model, n_par, n_chains, data, [int(x) for x in seeds], device, chain_offset, n_chains_global,
+                             waves_per_chain, sigma, hmin, lds_policy, circular_params, flags, adapt_target,
+                             device_model_source)
+            return
         assert data.ndim == 2
         self.cfg = capi.Config(abi_version=capi.ABI_VERSION, device=device, model=model, n_par=n_par,
                                n_chains=n_chains, n_data=data.shape[0], n_cols=data.shape[1],
@@ -75,6 +97,54 @@ class HipSampler:
         self.n_chains_global = self.cfg.n_chains_global
         self.chain_offset = chain_offset
         self.seed = seed
+        self.n_ladders, self.chains_per_ladder, self.seeds = 1, n_chains, [seed]
+
+    def _init_batch(self, model, n_par, n_chains, data, seeds, device, chain_offset, n_chains_global, waves_per_chain,
+                    sigma, hmin, lds_policy, circular_params, flags, adapt_target, device_model_source):
+        n_ladders = len(seeds)
+        if data.ndim not in (2, 3) or (data.ndim == 3 and data.shape[0] != n_ladders):
+            raise ValueError("data: [n_data][n_cols], or [n_ladders][n_data][n_cols] with one matrix per ladder")
+        self.cfg = capi.Config(abi_version=capi.ABI_VERSION, device=device, model=model, n_par=n_par,
+                               n_chains=n_chains, n_data=data.shape[-2], n_cols=data.shape[-1],
+                               waves_per_chain=waves_per_chain, lds_policy=lds_policy, chain_offset=chain_offset,
+                               n_chains_global=n_chains if n_chains_global is None else n_chains_global,
+                               seed=0, sigma=sigma, hmin=hmin, circular_params=circular_params, flags=flags,
+                               adapt_target=adapt_target,
+                               device_model_source=None if device_model_source is None else str(device_model_source).encode())
+        self._h = C.c_void_p()
+        self.L = capi.lib()
+        arr = (C.c_uint64 * max(n_ladders, 1))(*seeds)
+        capi.check(self.L.apemost_hip_create_batch(C.byref(self.cfg), n_ladders, arr, C.byref(self._h)))
+        self.n_par, self.n_chains = n_par, n_chains * n_ladders
+        self.n_chains_global = n_chains            # of the swap schedule: per ladder
+        self.chain_offset = 0
+        self.seed = seeds[0]
+        self.n_ladders, self.chains_per_ladder, self.seeds = n_ladders, n_chains, seeds
+        if data.ndim == 2:
+            self.set_data(data)
+        else:
+            for b in range(n_ladders):
+                self.set_data(data[b], ladder=b)
+
+    @classmethod
+    def batch(cls, model, n_par, n_chains, data, seeds, **kw):
+        """a ladder batch: len(seeds) independent ladders of n_chains chains each, stepped by one launch"""
+        return cls(model, n_par, n_chains, data, seeds=seeds, **kw)
+
+    def set_data(self, data, ladder=None):
+        """the data matrix [n_data][n_cols] of every ladder (ladder=None) or of one ladder of a batch"""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if data.shape != (self.cfg.n_data, self.cfg.n_cols):
+            raise ValueError("data must be [%d][%d]" % (self.cfg.n_data, self.cfg.n_cols))
+        p = data.ctypes.data_as(C.POINTER(C.c_double))
+        if ladder is None:
+            capi.check(self.L.apemost_hip_set_data(self._h, p))
+        else:
+            capi.check(self.L.apemost_hip_set_data_ladder(self._h, int(ladder), p))
+
+    def ladder_view(self, arr, b):
+        """ladder b's part of a ladder-major array or of sample rows of this sampler (module-level ladder_view)"""
+        return ladder_view(arr, b, self.n_ladders)
 
     def close(self):
         if self._h:
@@ -176,20 +246,30 @@ class HipSampler:
         self._adopt(d_samples)
         capi.check(self.L.apemost_hip_launch_rounds(self._h, n_rounds, n_steps, int(apply_swap), d_samples))
 
-    def swap_pair(self, round_):
-        """lower chain of the pair swap attempt `round_` picks under this sampler's swap schedule"""
-        return int(self.L.apemost_hip_sampler_swap_pair(self._h, round_))
+    def swap_pair(self, round_, ladder=None):
+        """lower chain of the pair swap attempt `round_` picks under this sampler's swap schedule; on a batch the
+        pair inside ladder `ladder` (each ladder draws its own)"""
+        if self.n_ladders == 1 and ladder is None:
+            return int(self.L.apemost_hip_sampler_swap_pair(self._h, round_))
+        if ladder is None or not 0 <= ladder < self.n_ladders:
+            raise ValueError("swap_pair on a batch of %d ladders needs ladder=" % self.n_ladders)
+        if self.chains_per_ladder <= 1:
+            return -1
+        if self.cfg.flags & capi.FLAG_SWAP_EVEN_ODD:
+            return round_ % 2 if round_ % 2 <= self.chains_per_ladder - 2 else -1
+        return capi.swap_pair(self.seeds[ladder], round_, self.chains_per_ladder)
 
-    def swap_attempts(self, pair, first_round, n_rounds):
+    def swap_attempts(self, pair, first_round, n_rounds, ladder=None):
         """how often the pair (pair, pair + 1) of the global ladder is attempted in the swap attempts first_round ..
         first_round + n_rounds - 1: a pure function of the schedule, so that swapcount / attempts is the per-pair
-        swap rate a ladder is tuned with.  Even-odd sweeps: the sweeps of the pair's parity."""
+        swap rate a ladder is tuned with.  Even-odd sweeps: the sweeps of the pair's parity.  On a batch: the pair
+        (pair, pair + 1) inside ladder `ladder`, under that ladder's seed."""
         if not 0 <= pair <= self.n_chains_global - 2 or n_rounds <= 0:
             return 0
         if self.cfg.flags & capi.FLAG_SWAP_EVEN_ODD:
             first = first_round + ((pair - first_round) % 2)     # the first sweep of the pair's parity
             return max(0, (first_round + n_rounds - first + 1) // 2)
-        return sum(1 for r in range(first_round, first_round + n_rounds) if self.swap_pair(r) == pair)
+        return sum(1 for r in range(first_round, first_round + n_rounds) if self.swap_pair(r, ladder) == pair)
 
     def rounds_within_shard(self, first_round, max_rounds):
         """how many swap attempts from `first_round` on (at most max_rounds) do not straddle an edge of this shard"""
@@ -369,6 +449,6 @@ class HipSampler:
                        skip_calibrate_allchains=False):
         """calibrate_rest() for a whole ladder on this device.  Entry state: chain 0 carries the
         calibrated steps/params (read_calibration_file(chains, 1)), every beta = 1."""
-        assert self.n_chains == self.n_chains_global and self.chain_offset == 0
+        assert self.n_ladders == 1 and self.n_chains == self.n_chains_global and self.chain_offset == 0
         from .distributed import calibrate_rest_sharded
         return calibrate_rest_sharded(self, self.n_chains, 0, cfg, ladder_kind, beta_0, skip_calibrate_allchains)

@@ -70,6 +70,37 @@ def bin_of(v, lo, hi, e):
     return b
 
 
+def gelman_rubin(rows, n_ladders, chain=0):
+    """R-hat per parameter (Gelman & Rubin 1992, the classic between/within form) of chain `chain` (0: beta = 1)
+    of every ladder of a replica batch.  rows: sample rows [n][n_ladders * n_chains][n_par + 2], ladder-major, already
+    cut to the part to judge (burn-in dropped).  With m = n_ladders sequences of n draws: W = the mean of the
+    sequences' sample variances, B / n = the sample variance of their means, var+ = (n - 1) / n * W + B / n,
+    R-hat = sqrt(var+ / W)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    n, total, w = rows.shape
+    if n_ladders < 2 or total % n_ladders or n < 2:
+        raise ValueError("gelman_rubin needs at least two ladders of equal size and two samples")
+    per = total // n_ladders
+    if not 0 <= chain < per:
+        raise ValueError("chain %d outside a ladder of %d chains" % (chain, per))
+    x = rows[:, chain::per, :w - 2]                   # [n][m][n_par]
+    within = x.var(axis=0, ddof=1).mean(axis=0)       # W
+    b_over_n = x.mean(axis=0).var(axis=0, ddof=1)     # B / n
+    return np.sqrt(((n - 1) / n * within + b_over_n) / within)
+
+
+def ladder_evidences(prob_sum, n, betas, n_ladders):
+    """ln p(D|M,I) of every ladder of a batch from a summary's ladder-major prob_sum and betas (RunSummary.evidence,
+    the integrator of analyse_data_probability, ladder by ladder): the spread over replicas is its error bar"""
+    prob_sum, betas = np.asarray(prob_sum, dtype=np.float64), np.asarray(betas, dtype=np.float64)
+    if n_ladders < 1 or len(prob_sum) % n_ladders or len(betas) != len(prob_sum):
+        raise ValueError("prob_sum and betas must hold n_ladders equal ladders")
+    per = len(prob_sum) // n_ladders
+    empty = np.zeros((0, 0, 0))
+    return np.array([RunSummary(n, prob_sum[b * per:(b + 1) * per], empty, empty, 0, [], [], 1).evidence(
+        betas[b * per:(b + 1) * per]) for b in range(n_ladders)])
+
+
 class RunSummary:
     def __init__(self, n, prob_sum, hist, batch_sums, n_batches, lo, hi, batch_size, thin=1):
         self.n = int(n)
@@ -147,6 +178,10 @@ class RunSummary:
             logprob += mean[j] * (betas[j] - previous)
             previous = betas[j]
         return logprob
+
+    def evidence_per_ladder(self, betas, n_ladders):
+        """evidence() of every ladder of a batch (prob_sum and betas ladder-major)"""
+        return ladder_evidences(self.prob_sum, self.n, betas, n_ladders)
 
     def histogram_density(self, p, h=0):
         """(edges, density, mean, sigma) of parameter p of chain h: counts * width / total, and the

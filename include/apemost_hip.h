@@ -251,6 +251,46 @@ int apemost_hip_device_info(int device, char *name, size_t name_len, int *comput
 
 /* ---- lifetime ------------------------------------------------------------- */
 int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sampler **out);
+/* ---- ladder batches: many independent ladders in one sampler and one launch -------------------
+ * apemost_hip_create_batch makes ONE sampler that holds n_ladders independent ladders of cfg->n_chains chains each
+ * (cfg->n_chains is the number PER LADDER; cfg->seed is ignored, ladder b runs under seeds[b]).  All ladders share
+ * the model, n_par, n_data, n_cols, the flags, n_swap and the round counter; each has its own seed, its own data
+ * matrix and its own state.  One launch steps all n_ladders * n_chains chains, one workgroup per chain, and swaps
+ * happen inside a ladder only.
+ * Indexing: local chain c of the sampler is chain a = c % n_chains of ladder b = c / n_chains (ladder-major).  Every
+ * RNG address of the header's scheme is taken with chain = a under the key seeds[b]: the chain streams, the swap
+ * stream (subsequence APEMOST_HIP_SWAP_SUBSEQUENCE) and, with APEMOST_HIP_FLAG_SWAP_EVEN_ODD, the pair streams
+ * (+ 1 + a); the swap schedule's n_chains_global is the per-ladder n_chains.  Streams do not depend on the launch
+ * shape, so ladder b is, bit for bit, the chain a stand-alone sampler with seed seeds[b], ladder b's data and the
+ * same waves_per_chain produces (the summation order of the likelihood follows the wave count, and a count left to
+ * the engine is chosen for the whole grid).
+ * Geometry -- waves per chain, LDS staging, the one-barrier kernels and their helper wavefront, the residency check
+ * behind multi-round launches, the calibration's segment shapes -- follows the TOTAL number of chains, which is what
+ * occupies the chip: 16 ladders of 8 chains are launched like one ladder of 128.
+ * The existing calls on a batch:
+ *   apemost_hip_set_data gives every ladder the same matrix (replicas); apemost_hip_set_data_ladder one ladder its own;
+ *   state views, sample rows ([n_steps][n_ladders * n_chains][n_par+2]), the summary's prob_sum, the packed and text
+ *   sample reads, calc_model / calibrate_* (first, count) and launch_round_for index chains 0 .. n_ladders * n_chains
+ *   - 1, ladder-major; a range may span ladders;
+ *   apemost_hip_sampler_swap_pair is ambiguous and returns APEMOST_HIP_ERR_INVALID (= -1, with a last_error text):
+ *   apemost_hip_swap_pair(seeds[b], round, n_chains) answers per ladder;
+ *   n_ladders = 1 is legal and equals an ordinary sampler with that seed.
+ * Supported: the four built-in models, the default swap schedule and APEMOST_HIP_FLAG_SWAP_EVEN_ODD, both proposal-law
+ * flags, SINGLE_ROUND_LAUNCHES, TWO_BARRIER_STEP, circular parameters, waves_per_chain 0, 1, 2, 4 or 8.  Batches run
+ * in the variant kernel instantiations (like the proposal laws): the default kernels carry no test for them.
+ * Refused by apemost_hip_create_batch with APEMOST_HIP_ERR_UNSUPPORTED, before any device is touched -- nothing runs
+ * silently as a single ladder: APEMOST_MODEL_USER; the flags RANDOMSWAP, ADAPT, RWM, TEST_REFUSE_COOPERATIVE,
+ * TEST_WITHHOLD_PUBLISH, COOPERATIVE_LAUNCH (the engine still takes cooperative launches by itself where it would
+ * for a ladder of as many chains) and USER_ONE_BARRIER; chain_offset != 0 or n_chains_global != n_chains (batches
+ * are not sharded).  Refused on a batch with APEMOST_HIP_ERR_UNSUPPORTED: apemost_hip_run_shards,
+ * apemost_hip_edge_export / import / exchange, apemost_hip_set_chain_offset, and apemost_hip_loglike when
+ * n_ladders > 1 (no single data matrix).  waves_per_chain = 6 is APEMOST_HIP_ERR_INVALID, as for every variant. */
+int apemost_hip_create_batch(const apemost_hip_config *cfg, int32_t n_ladders, const uint64_t *seeds,
+                             apemost_hip_sampler **out);
+/* 1 for an ordinary sampler */
+int apemost_hip_n_ladders(apemost_hip_sampler *s, int32_t *n_ladders);
+/* row-major [n_data][n_cols] host matrix for ladder `ladder` alone (ladder 0 of an ordinary sampler: its data) */
+int apemost_hip_set_data_ladder(apemost_hip_sampler *s, int32_t ladder, const double *data_rowmajor);
 int apemost_hip_destroy(apemost_hip_sampler *s);
 int apemost_hip_synchronize(apemost_hip_sampler *s);
 /* the HIP stream (hipStream_t) every launch of this sampler goes to */
