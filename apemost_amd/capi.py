@@ -19,6 +19,7 @@ FLAG_TEST_REFUSE_COOPERATIVE, FLAG_TEST_WITHHOLD_PUBLISH = 128, 256   # test hoo
 FLAG_RWM = 512
 FLAG_USER_ONE_BARRIER = 1024   # APEMOST_MODEL_USER in the one-barrier kernels (include/apemost_hip.h)
 FLAG_SWAP_EVEN_ODD = 2048      # even-odd swap sweeps: every pair of the sweep's parity each round (include/apemost_hip.h)
+FLAG_TRACK_REPLICAS = 4096     # replica-flow tracking: round trips and up / down moves per rung (include/apemost_hip.h)
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_RUNTIME, ERR_UNSUPPORTED, ERR_CALIBRATION = 0, -1, -2, -3, -4, -5
 
 _dp = C.POINTER(C.c_double)
@@ -65,6 +66,11 @@ class SummaryView(C.Structure):
     _fields_ = [("n", _up), ("prob_sum", _dp), ("hist", _up), ("batch_sums", _dp), ("n_batches", _up)]
 
 
+class ReplicaFlowView(C.Structure):
+    _fields_ = [("replica", C.POINTER(C.c_uint32)), ("heading", C.POINTER(C.c_uint32)), ("n_up", _up), ("n_down", _up),
+                ("attempts", _up), ("round_trips", _up)]
+
+
 # every symbol include/apemost_hip.h declares
 EXPORTS = [
     "apemost_hip_last_error", "apemost_hip_abi_version", "apemost_hip_device_count",
@@ -87,6 +93,7 @@ EXPORTS = [
     "apemost_hip_samples_text_bound", "apemost_hip_samples_text_read_async", "apemost_hip_device_alloc",
     "apemost_hip_device_free",
     "apemost_hip_create_batch", "apemost_hip_n_ladders", "apemost_hip_set_data_ladder",
+    "apemost_hip_replica_flow_get", "apemost_hip_replica_flow_set", "apemost_hip_replica_flow_reset",
 ]
 
 _lib = None
@@ -189,6 +196,9 @@ def lib():
                                                       C.c_uint64, vp, C.c_uint64, _up, C.c_uint64]
     L.apemost_hip_device_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.apemost_hip_device_free.argtypes = [vp, vp]
+    L.apemost_hip_replica_flow_get.argtypes = [vp, C.POINTER(ReplicaFlowView)]
+    L.apemost_hip_replica_flow_set.argtypes = [vp, C.POINTER(ReplicaFlowView)]
+    L.apemost_hip_replica_flow_reset.argtypes = [vp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

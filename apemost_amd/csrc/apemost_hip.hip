@@ -335,6 +335,7 @@ struct apemost_hip_sampler {
     // a ladder batch (apemost_hip_create_batch): n_ladders independent ladders of `per_ladder` chains in one grid;
     // cfg.n_chains = cfg.n_chains_global = their product, sh.n_global = per_ladder, cfg.seed = seeds[0]
     bool batch;
+    bool track; // APEMOST_HIP_FLAG_TRACK_REPLICAS: the flow words behind the ladder words exist
     int n_ladders, per_ladder;
     std::vector<u64> seeds;        // [n_ladders] (empty for an ordinary sampler)
     std::vector<double> x_abs_max; // [n_ladders] of each ladder's data
@@ -750,6 +751,25 @@ static int ladder_words_upload(apemost_hip_sampler *s) {
     return APEMOST_HIP_OK;
 }
 
+// Replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS): the rung words go to the device three times -- the word the
+// rung's workgroup works on and its hand-off copy in either half of the state -- so that whichever half the next
+// launch reads holds them.  replica == nullptr: labels to identity and headings to the initial state, per ladder;
+// zero_counters: the four counter arrays too.
+static int flow_upload(apemost_hip_sampler *s, const uint32_t *replica, const uint32_t *heading, bool zero_counters) {
+    const size_t n = s->cfg.n_chains, per = s->per_ladder;
+    std::vector<u64> w(3 * n);
+    for (size_t c = 0; c < n; c++) {
+        const size_t a = c % per;
+        u64 label = replica ? replica[c] : a, head = heading ? heading[c] : (per == 1 ? 0 : a == 0 ? 1 : a == per - 1 ? 2 : 0);
+        w[c] = w[n + c] = w[2 * n + c] = label << 2 | head;
+    }
+    HIP_TRY(hipMemcpyAsync(s->d.flow_word(), w.data(), w.size() * sizeof(u64), hipMemcpyHostToDevice, s->stream));
+    if (zero_counters)
+        HIP_TRY(hipMemsetAsync(s->d.flow_up(), 0, 4 * n * sizeof(u64), s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return APEMOST_HIP_OK;
+}
+
 // the part of apemost_hip_create that can fail after the sampler object exists
 static int create_body(apemost_hip_sampler *s) {
     const apemost_hip_config *cfg = &s->cfg;
@@ -773,11 +793,13 @@ static int create_body(apemost_hip_sampler *s) {
     d.n = cfg->n_chains;
     d.np = cfg->n_par;
     double *data = nullptr;
-    if ((rc = dev_alloc(s, &d.f, d.f_count())) || (rc = dev_alloc(s, &d.u, d.u_count() + (s->batch ? 2 * (size_t)s->n_ladders : 0))) ||
+    if ((rc = dev_alloc(s, &d.f, d.f_count())) || (rc = dev_alloc(s, &d.u, d.u_count() + (s->track ? d.flow_count() : s->batch ? 2 * (size_t)s->n_ladders : 0))) ||
         (rc = dev_alloc(s, &data, (size_t)cfg->n_cols * cfg->n_data * s->n_ladders)))
         return rc;
     d.data = data;
     if (s->batch && (rc = ladder_words_upload(s)))
+        return rc;
+    if (s->track && (rc = flow_upload(s, nullptr, nullptr, true)))
         return rc;
 
     s->sh.n_par = cfg->n_par;
@@ -801,8 +823,11 @@ static int create_body(apemost_hip_sampler *s) {
         s->sh.variant |= kVariantEvenOdd;
     if (s->batch)
         s->sh.variant |= kVariantBatch;
+    if (s->track)
+        s->sh.variant |= kVariantTrack;
     s->kmodel = cfg->model + (((cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
-                                              APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD)) || s->batch)
+                                              APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD |
+                                              APEMOST_HIP_FLAG_TRACK_REPLICAS)) || s->batch)
                                   ? kVariantModel
                                   : 0);
     s->sh.x_abs_max = INFINITY; // until set_data
@@ -902,8 +927,13 @@ static int create_impl(const apemost_hip_config *cfg, int n_ladders, int per_lad
                        APEMOST_HIP_FLAG_TWO_BARRIER_STEP | APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC |
                        APEMOST_HIP_FLAG_PROPOSAL_UNIFORM | APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_ADAPT |
                        APEMOST_HIP_FLAG_TEST_REFUSE_COOPERATIVE | APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH | APEMOST_HIP_FLAG_RWM |
-                       APEMOST_HIP_FLAG_USER_ONE_BARRIER | APEMOST_HIP_FLAG_SWAP_EVEN_ODD))
+                       APEMOST_HIP_FLAG_USER_ONE_BARRIER | APEMOST_HIP_FLAG_SWAP_EVEN_ODD | APEMOST_HIP_FLAG_TRACK_REPLICAS))
         return fail(APEMOST_HIP_ERR_INVALID, "unknown bits in flags: 0x%x", (unsigned)cfg->flags);
+    // (seeds: a batch, whose create_batch has refused sharding already and whose *cfg describes the whole grid)
+    if ((cfg->flags & APEMOST_HIP_FLAG_TRACK_REPLICAS) && !seeds && (cfg->chain_offset != 0 || cfg->n_chains_global != cfg->n_chains))
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED,
+                    "TRACK_REPLICAS: replica flow is not tracked over a sharded ladder (chain_offset %lld, n_chains_global %lld, "
+                    "n_chains %d)", (long long)cfg->chain_offset, (long long)cfg->n_chains_global, cfg->n_chains);
     if ((cfg->flags & APEMOST_HIP_FLAG_SWAP_EVEN_ODD) &&
         (cfg->flags & (APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_TEST_WITHHOLD_PUBLISH)))
         return fail(APEMOST_HIP_ERR_INVALID, "SWAP_EVEN_ODD excludes RANDOMSWAP and TEST_WITHHOLD_PUBLISH");
@@ -976,6 +1006,7 @@ static int create_impl(const apemost_hip_config *cfg, int n_ladders, int per_lad
     s->in_rwm = false;
     s->sum = {};
     s->batch = seeds != nullptr;
+    s->track = (cfg->flags & APEMOST_HIP_FLAG_TRACK_REPLICAS) != 0;
     s->n_ladders = n_ladders;
     s->per_ladder = per_ladder;
     if (seeds) {
@@ -983,7 +1014,8 @@ static int create_impl(const apemost_hip_config *cfg, int n_ladders, int per_lad
         s->x_abs_max.assign(n_ladders, INFINITY); // until set_data
     }
     if (s->waves == 6 && (s->batch || (cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
-                                                     APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD)))) {
+                                                     APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD |
+                                                     APEMOST_HIP_FLAG_TRACK_REPLICAS)))) {
         delete s;
         return fail(APEMOST_HIP_ERR_INVALID, "the proposal / swap variants and ladder batches are built for 1, 2, 4 or 8 waves per chain");
     }
@@ -1133,6 +1165,8 @@ extern "C" int apemost_hip_set_chain_offset(apemost_hip_sampler *s, int64_t chai
     CHECK_S(s);
     if (s->batch)
         return fail(APEMOST_HIP_ERR_UNSUPPORTED, "set_chain_offset: ladder batches are not sharded");
+    if (s->track)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "set_chain_offset: replica flow is not tracked over a sharded ladder");
     if (chain_offset < 0 || chain_offset + s->cfg.n_chains > s->cfg.n_chains_global)
         return fail(APEMOST_HIP_ERR_INVALID, "chain offset %lld outside the ladder", (long long)chain_offset);
     s->cfg.chain_offset = chain_offset;
@@ -1278,6 +1312,88 @@ extern "C" int apemost_hip_set_state(apemost_hip_sampler *s, const apemost_hip_s
 extern "C" int apemost_hip_get_state(apemost_hip_sampler *s, const apemost_hip_state_view *v) {
     int rc = xfer_state(s, v, false);
     return rc ? rc : check_handoff(s);
+}
+
+// ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS) ----
+static int flow_check(apemost_hip_sampler *s, const char *what) {
+    CHECK_S(s);
+    if (!s->track)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "%s: the sampler was created without APEMOST_HIP_FLAG_TRACK_REPLICAS", what);
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_replica_flow_get(apemost_hip_sampler *s, const apemost_hip_replica_flow_view *v) {
+    int rc = flow_check(s, "replica_flow_get");
+    if (rc)
+        return rc;
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "replica_flow_get: the view is NULL");
+    const size_t n = s->cfg.n_chains;
+    std::vector<u64> w(n);
+    HIP_TRY(hipMemcpyAsync(w.data(), s->d.flow_word(), n * sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+    uint64_t *const host[4] = {v->n_up, v->n_down, v->attempts, v->round_trips};
+    for (int k = 0; k < 4; k++)
+        if (host[k])
+            HIP_TRY(hipMemcpyAsync(host[k], s->d.flow_up() + k * n, n * sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (size_t c = 0; c < n; c++) {
+        if (v->replica)
+            v->replica[c] = (uint32_t)(w[c] >> 2);
+        if (v->heading)
+            v->heading[c] = (uint32_t)(w[c] & 3);
+    }
+    return check_handoff(s); // the flow of a void launch is void like its state
+}
+
+extern "C" int apemost_hip_replica_flow_set(apemost_hip_sampler *s, const apemost_hip_replica_flow_view *v) {
+    int rc = flow_check(s, "replica_flow_set");
+    if (rc)
+        return rc;
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "replica_flow_set: the view is NULL");
+    const size_t n = s->cfg.n_chains, per = s->per_ladder;
+    if (v->replica) {
+        std::vector<char> seen(n, 0);
+        for (size_t c = 0; c < n; c++) {
+            const size_t base = c - c % per;
+            if (v->replica[c] >= per || seen[base + v->replica[c]]++)
+                return fail(APEMOST_HIP_ERR_INVALID, "replica_flow_set: the labels of ladder %zu are not a permutation of 0 .. %zu",
+                            c / per, per - 1);
+        }
+    }
+    for (size_t c = 0; v->heading && c < n; c++)
+        if (v->heading[c] > 2)
+            return fail(APEMOST_HIP_ERR_INVALID, "replica_flow_set: heading %u of chain %zu is not 0, 1 or 2", v->heading[c], c);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    std::vector<uint32_t> replica(n), heading(n);
+    if (!v->replica || !v->heading) { // the half of the word that does not come with this view stays
+        std::vector<u64> w(n);
+        HIP_TRY(hipMemcpy(w.data(), s->d.flow_word(), n * sizeof(u64), hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < n; c++) {
+            replica[c] = (uint32_t)(w[c] >> 2);
+            heading[c] = (uint32_t)(w[c] & 3);
+        }
+    }
+    if (v->replica)
+        replica.assign(v->replica, v->replica + n);
+    if (v->heading)
+        heading.assign(v->heading, v->heading + n);
+    if ((rc = flow_upload(s, replica.data(), heading.data(), false)))
+        return rc;
+    const uint64_t *const host[4] = {v->n_up, v->n_down, v->attempts, v->round_trips};
+    for (int k = 0; k < 4; k++)
+        if (host[k])
+            HIP_TRY(hipMemcpyAsync(s->d.flow_up() + k * n, host[k], n * sizeof(u64), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_replica_flow_reset(apemost_hip_sampler *s) {
+    int rc = flow_check(s, "replica_flow_reset");
+    if (rc)
+        return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return flow_upload(s, nullptr, nullptr, true);
 }
 
 extern "C" int apemost_hip_set_round(apemost_hip_sampler *s, uint64_t round, int swap_pending) {
@@ -2157,6 +2273,8 @@ extern "C" int apemost_hip_edge_export(apemost_hip_sampler *s, int side, double 
         return fail(APEMOST_HIP_ERR_INVALID, "edge_export: bad arguments");
     if (s->batch)
         return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_export: ladder batches are not sharded");
+    if (s->track)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_export: replica flow is not tracked over a sharded ladder");
     const int row = side == 0 ? 1 : s->cfg.n_chains;
     hipLaunchKernelGGL(edge_export_kernel, dim3(1), dim3(kWave), 0, s->stream, s->d, s->cfg.n_par, s->cur, row,
                        d_buf);
@@ -2170,6 +2288,8 @@ extern "C" int apemost_hip_edge_import(apemost_hip_sampler *s, int side, const d
         return fail(APEMOST_HIP_ERR_INVALID, "edge_import: bad arguments");
     if (s->batch)
         return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_import: ladder batches are not sharded");
+    if (s->track)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_import: replica flow is not tracked over a sharded ladder");
     const int row = side == 0 ? 0 : s->cfg.n_chains + 1;
     hipLaunchKernelGGL(edge_import_kernel, dim3(1), dim3(kWave), 0, s->stream, s->d, s->cfg.n_par, s->cur, row,
                        d_buf);
@@ -2203,6 +2323,8 @@ extern "C" int apemost_hip_edge_exchange(apemost_hip_sampler *lower, apemost_hip
         return fail(APEMOST_HIP_ERR_INVALID, "edge_exchange: two different samplers are needed");
     if (lower->batch || upper->batch)
         return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_exchange: ladder batches are not sharded");
+    if (lower->track || upper->track)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "edge_exchange: replica flow is not tracked over a sharded ladder");
     if (lower->cfg.n_par != upper->cfg.n_par || lower->cfg.n_chains_global != upper->cfg.n_chains_global ||
         lower->cfg.seed != upper->cfg.seed ||
         lower->cfg.chain_offset + lower->cfg.n_chains != upper->cfg.chain_offset)
@@ -2262,6 +2384,9 @@ extern "C" int apemost_hip_run_shards(apemost_hip_sampler **sh, int32_t n_shards
     for (int j = 0; j < n_shards; j++)
         if (sh[j] && sh[j]->batch)
             return fail(APEMOST_HIP_ERR_UNSUPPORTED, "run_shards: shard %d is a ladder batch; batches are not sharded", j);
+    for (int j = 0; j < n_shards; j++)
+        if (sh[j] && sh[j]->track)
+            return fail(APEMOST_HIP_ERR_UNSUPPORTED, "run_shards: shard %d tracks replica flow, which is not sharded", j);
     int64_t next = 0;
     for (int j = 0; j < n_shards; j++) {
         if (!sh[j] || sh[j]->cfg.chain_offset != next || sh[j]->cfg.n_chains_global != sh[0]->cfg.n_chains_global ||

@@ -272,6 +272,53 @@ __device__ __forceinline__ long long swap_pair_of(const ChainShape &sh, long lon
     return swap_draws<VARIANTS>(sh, swap_index, u_accept);
 }
 
+// APEMOST_HIP_FLAG_TRACK_REPLICAS (variant instantiations only): what swap attempt (a, a+1) does to the flow words
+// of rung g, by the five rules of apemost_hip.h, run by one lane of the rung's own workgroup.  Both chains of the
+// pair took the same decision from the same numbers; each moves its own rung's word and counters, and the round
+// trips of a ladder are only ever written by the workgroup of its rung 0: one writer per word, plain stores.
+// The partner's word comes from its hand-off copy in half `half`, like its prob: published inside this launch
+// (`shared`) or stored by the previous one.  Nothing is carried in registers between two attempts.
+// The arrays as the flow code addresses them.  The chain count goes through an empty asm so that every address
+// that is built on it is made where it is used: as loop invariants the compiler moves them in front of the step
+// loops and holds them in scalar registers, which these kernels spill.
+__device__ __forceinline__ DevArrays flow_arrays(const DevArrays &d) {
+    DevArrays f = d;
+    asm volatile("" : "+s"(f.n));
+    return f;
+}
+__device__ __forceinline__ void flow_update(const DevArrays &arrays, const ChainShape &sh, int c, long long g, long long a,
+                                            int partner, int half, bool swapped, bool shared) {
+    const DevArrays d = flow_arrays(arrays);
+    u64 w = d.flow_word()[c];
+    if (swapped) // the label follows params
+        w = shared ? ld_agent(d.flow_pub(half) + partner) : d.flow_pub(half)[partner];
+    if (g == 0) { // (then g == a) the bottom end: a replica that comes from the top closes a round trip
+        if ((w & 3) == 2)
+            d.flow_round_trips()[(size_t)c + (size_t)(w >> 2)] += 1; // c = the ladder's rung 0
+        w = (w & ~(u64)3) | 1;
+    }
+    if (g == sh.n_global - 1) // (then g == a + 1) the top end
+        w = (w & ~(u64)3) | 2;
+    if ((w & 3) == 1)
+        d.flow_up()[c] += 1;
+    if ((w & 3) == 2)
+        d.flow_down()[c] += 1;
+    if (g == a)
+        d.flow_attempts()[c] += 1;
+    d.flow_word()[c] = w;
+}
+// a launch leaves the rung's word in the half its chain_store fills, where the next launch's fused swap-in
+// reads it (after wait_for_reader, like the row itself)
+template <class E>
+__device__ __forceinline__ void flow_store(const E &e, const DevArrays &arrays, const ChainShape &sh, int c, int dst) {
+    if constexpr (E::kVariants) {
+        if ((sh.variant & kVariantTrack) && e.wave == 0 && e.lane == 0) {
+            const DevArrays d = flow_arrays(arrays);
+            d.flow_pub(dst)[c] = d.flow_word()[c];
+        }
+    }
+}
+
 template <class E>
 __device__ __forceinline__ int swap_apply(E &e, const DevArrays &d, const ChainShape &sh, int c, int half,
                                           u64 swap_index, bool shared) {
@@ -307,6 +354,10 @@ __device__ __forceinline__ int swap_apply(E &e, const DevArrays &d, const ChainS
             e.prob_best = a_wins ? a_best : b_best;
         if (g == a && e.lane == 0)
             d.swapcount()[c] += 1; // inc_swapcount(chains[candidate])
+    }
+    if constexpr (E::kVariants) {
+        if ((sh.variant & kVariantTrack) && e.lane == 0)
+            flow_update(d, sh, c, g, a, partner - 1, half, r > lc, shared);
     }
     return partner - 1;
 }
@@ -371,6 +422,12 @@ __device__ __forceinline__ void swap_in_launch(E &e, const DevArrays &d, const C
     if (e.lane == 63) {
         st_agent(d.prob(half) + row, e.prob);
         st_agent(d.prob_best(half) + row, e.prob_best);
+    }
+    if constexpr (E::kVariants) {
+        if ((sh.variant & kVariantTrack) && e.lane == 0) { // the rung's flow word: one more field of the record
+            const DevArrays f = flow_arrays(d);
+            st_agent(f.flow_pub(half) + c, f.flow_word()[c]);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every payload store of this wave has left
     // (test hook: the lower chain of the pair keeps the publish of swap attempt 3 to itself, so its
@@ -447,6 +504,7 @@ void pt_round_kernel(const RoundArgs grid) {
         a.d.n_iter()[c] += (u64)a.n_steps * a.n_rounds; // mcmc_append_current_parameters, src/mcmc_calculate.c:30-33
     if (e.wave == 0)
         wait_for_reader<decltype(e)>(a.d, a.sh, memo, a.cur ^ 1);
+    flow_store(e, a.d, a.sh, c, a.cur ^ 1);
     if (e.tid == 0 && *e.fail_flag())
         st_agent(a.d.timeout_word(), 3);
     chain_store(e, a.d, a.sh, c, a.cur ^ 1, false);
@@ -739,6 +797,7 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
         if (e.lane == 0)
             a.d.n_iter()[c] += (u64)a.n_steps * a.n_rounds;
         wait_for_reader<decltype(e)>(a.d, a.sh, memo, a.cur ^ 1);
+        flow_store(e, a.d, a.sh, c, a.cur ^ 1);
         if (e.lane == 0 && *e.fail_flag())
             st_agent(a.d.timeout_word(), 3);
         chain_store(e, a.d, a.sh, c, a.cur ^ 1, false);

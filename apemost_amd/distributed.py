@@ -31,6 +31,10 @@ class ShardedLadder:
         if getattr(engine, "flags", 0) & 2048:
             raise ValueError("ShardedLadder drives one pair per swap attempt: it does not run the even-odd swap "
                              "schedule (FLAG_SWAP_EVEN_ODD); use in-process shards (apemost_hip_run_shards)")
+        # (4096 = capi.FLAG_TRACK_REPLICAS: the label word does not travel in the edge record)
+        if getattr(engine, "flags", 0) & 4096:
+            raise ValueError("ShardedLadder does not track replica flow (FLAG_TRACK_REPLICAS): the rung's label is not "
+                             "part of the edge record; track on a whole ladder")
         if getattr(engine, "n_ladders", 1) > 1:
             raise ValueError("ShardedLadder drives one ladder: a ladder batch (HipSampler.batch) is not sharded")
         self.e, self.n_global, self.lo, self.hi = engine, n_global, chain_offset, chain_offset + n_local

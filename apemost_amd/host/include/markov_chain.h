@@ -30,6 +30,10 @@
 #if defined(SWAP_EVEN_ODD) && defined(RANDOMSWAP)
 #error "SWAP_EVEN_ODD and RANDOMSWAP are alternatives"
 #endif
+/* -DTRACK_REPLICAS (not in the reference): the run phase follows every replica over the rungs of the ladder and writes
+ * replica_flow.dump at its end -- round trips, up / down moves and swap attempts per rung,
+ * APEMOST_HIP_FLAG_TRACK_REPLICAS in include/apemost_hip.h.  Whole ladders on one device only: with APEMOST_DEVICES
+ * the engine refuses the sharded ladder. */
 /* -DRWM (src/parallel_tempering.c:268-281, src/markov_chain.c:342-367): carried as APEMOST_HIP_FLAG_RWM since
  * round 4 -- the reference's own call site does not compile (a two-argument call of markov_chain_step);
  * include/apemost_hip.h states the semantics the engine gives it.  MINIMAL_STEPWIDTH / MAXIMAL_STEPWIDTH keep

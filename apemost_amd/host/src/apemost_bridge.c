@@ -177,6 +177,11 @@ static apemost_hip_sampler *create_sampler(const mcmc *m, int model, unsigned in
 #ifdef SWAP_EVEN_ODD /* not in the reference: even-odd swap sweeps (include/apemost_hip.h) */
     cfg.flags |= APEMOST_HIP_FLAG_SWAP_EVEN_ODD;
 #endif
+#ifdef TRACK_REPLICAS /* not in the reference: replica-flow tracking (include/apemost_hip.h); whole ladders only, so the
+                       * one-chain twin, which sits at an offset of a long ladder, goes without it */
+    if (run_ladder)
+        cfg.flags |= APEMOST_HIP_FLAG_TRACK_REPLICAS;
+#endif
 #ifdef ADAPT
     if (run_ladder)
         cfg.flags |= APEMOST_HIP_FLAG_ADAPT;
@@ -573,10 +578,51 @@ int apemost_ladder_calibrate(apemost_ladder *l, unsigned int first, unsigned int
     return rc;
 }
 
+/* -DTRACK_REPLICAS: replica_flow.dump from a ladder that has just been downloaded -- one line per rung (beta,
+ * replica, heading, attempts, swapcount, n_up, n_down), then one line per replica with its round trips: the format
+ * of apemost_amd/replica_flow.py, ReplicaFlow.write / read */
+void apemost_write_replica_flow(apemost_ladder *l) {
+    apemost_hip_replica_flow_view f;
+    const size_t n = l->n;
+    unsigned int c;
+    FILE *out;
+    f.replica = (uint32_t *)calloc(n, sizeof(uint32_t));
+    f.heading = (uint32_t *)calloc(n, sizeof(uint32_t));
+    f.n_up = (uint64_t *)calloc(n, sizeof(uint64_t));
+    f.n_down = (uint64_t *)calloc(n, sizeof(uint64_t));
+    f.attempts = (uint64_t *)calloc(n, sizeof(uint64_t));
+    f.round_trips = (uint64_t *)calloc(n, sizeof(uint64_t));
+    apemost_hip_or_die(apemost_hip_replica_flow_get(l->s[0], &f), "replica_flow.dump");
+    out = fopen("replica_flow.dump", "w");
+    if (out == NULL) {
+        fprintf(stderr, "could not open replica_flow.dump\n");
+        exit(1);
+    }
+    for (c = 0; c < l->n; c++)
+        fprintf(out, "%.17g\t%lu\t%lu\t%lu\t%lu\t%lu\t%lu\n", l->v.beta[c], (unsigned long)f.replica[c],
+                (unsigned long)f.heading[c], (unsigned long)f.attempts[c], (unsigned long)l->v.swapcount[c],
+                (unsigned long)f.n_up[c], (unsigned long)f.n_down[c]);
+    for (c = 0; c < l->n; c++)
+        fprintf(out, "%lu\n", (unsigned long)f.round_trips[c]);
+    fclose(out);
+    free(f.replica);
+    free(f.heading);
+    free(f.n_up);
+    free(f.n_down);
+    free(f.attempts);
+    free(f.round_trips);
+}
+
 /* n_rounds x {n_swap steps per chain, one swap attempt} on the whole ladder (asynchronous);
  * d_samples[k]: device rows of shard k or NULL.  n_rounds = 0 with a pending swap attempt applies
  * just that attempt. */
 void apemost_ladder_run(apemost_ladder *l, unsigned long n_rounds, unsigned int n_swap, double **d_samples) {
+#ifdef TRACK_REPLICAS /* a tracked sampler is a whole ladder and refuses apemost_hip_run_shards: its own run_sampler() */
+    if (l->n_shards == 1) {
+        apemost_hip_or_die(apemost_hip_run(l->s[0], n_rounds, n_swap, d_samples ? d_samples[0] : NULL), "run_sampler");
+        return;
+    }
+#endif
     apemost_hip_or_die(apemost_hip_run_shards(l->s, (int)l->n_shards, n_rounds, n_swap, d_samples), "run_sampler");
 }
 

@@ -726,6 +726,9 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     }
 #undef PLAN_BATCH
     apemost_ladder_download(l);
+#ifdef TRACK_REPLICAS
+    apemost_write_replica_flow(l);
+#endif
     if (sink.summary)
         summary_close(&summary, l, lo, n_shards);
     for (i = 0; i < 2; i++)

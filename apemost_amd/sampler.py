@@ -290,6 +290,38 @@ class HipSampler:
         self._adopt(d_samples)
         capi.check(self.L.apemost_hip_run(self._h, n_rounds, n_swap, d_samples))
 
+    # -- replica flow (apemost_amd/replica_flow.py; flags=capi.FLAG_TRACK_REPLICAS) -----------
+    def replica_flow(self, ladder=None):
+        """the replica flow so far as a ReplicaFlow, with the chains' betas and swap counts (synchronises like
+        get_state).  A batch gives a list, one per ladder, or the one of ladder `ladder`."""
+        from .replica_flow import FIELDS, ReplicaFlow
+        a = {k: np.zeros(self.n_chains, dtype=t) for k, t in FIELDS}
+        v = capi.ReplicaFlowView(**{k: a[k].ctypes.data_as(C.POINTER(C.c_uint32 if t == np.uint32 else C.c_uint64))
+                                    for k, t in FIELDS})
+        capi.check(self.L.apemost_hip_replica_flow_get(self._h, C.byref(v)))
+        st = self.get_state(fields=("beta", "swapcount"))
+        flows = [ReplicaFlow(beta=self.ladder_view(st.beta, b).copy(), swapcount=self.ladder_view(st.swapcount, b).copy(),
+                             **{k: self.ladder_view(a[k], b).copy() for k, _ in FIELDS}) for b in range(self.n_ladders)]
+        if ladder is not None:
+            return flows[ladder]
+        return flows[0] if self.n_ladders == 1 else flows
+
+    def replica_flow_set(self, rf):
+        """load a ReplicaFlow (a list of them, one per ladder, on a batch) saved by replica_flow(): a resumed run.
+        betas and swap counts are state and travel with set_state."""
+        from .replica_flow import FIELDS
+        flows = list(rf) if isinstance(rf, (list, tuple)) else [rf]
+        if len(flows) != self.n_ladders or any(len(f.replica) != self.chains_per_ladder for f in flows):
+            raise ValueError("replica_flow_set: %d ladders of %d chains are needed" % (self.n_ladders, self.chains_per_ladder))
+        a = {k: np.ascontiguousarray(np.concatenate([getattr(f, k) for f in flows]), dtype=t) for k, t in FIELDS}
+        v = capi.ReplicaFlowView(**{k: a[k].ctypes.data_as(C.POINTER(C.c_uint32 if t == np.uint32 else C.c_uint64))
+                                    for k, t in FIELDS})
+        capi.check(self.L.apemost_hip_replica_flow_set(self._h, C.byref(v)))
+
+    def replica_flow_reset(self):
+        """labels to identity, headings and counters to the initial state (after burn-in)"""
+        capi.check(self.L.apemost_hip_replica_flow_reset(self._h))
+
     # -- run summary (apemost_amd/summary.py) ------------------------------------------------
     def summary_begin(self, lo=None, hi=None, n_hist_chains=1, nbins=200, batch_size=1, max_batches=0, thin=1):
         """start an on-device summary: prob - prior sums of every chain, and histograms over [lo, hi] and

@@ -175,7 +175,39 @@ enum {
      * o-1 and o is straddled by the sweeps with r % 2 == (o-1) % 2, so apemost_hip_rounds_within_shard gives at
      * most two rounds, and apemost_hip_run_shards exchanges on every straddled edge before such a launch.  The
      * torch.distributed driver (distributed.ShardedLadder) does not run this schedule. */
-    APEMOST_HIP_FLAG_SWAP_EVEN_ODD = 2048
+    APEMOST_HIP_FLAG_SWAP_EVEN_ODD = 2048,
+    /* Replica-flow tracking, not in the reference: follows which replica sits at which rung through every swap
+     * attempt, inside the kernels that take the decision, and counts round trips and up / down moves -- what tells
+     * whether a ladder works and how its betas should be re-spaced (round-trip rate and up-moving fraction:
+     * Katzgraber 2006; equal-rejection spacing: Syed 2019).  Read with apemost_hip_replica_flow_get.
+     * "Rung" = a chain's index a inside its ladder (0 = the beta = 1 end, n-1 = the last chain).  A replica is a
+     * point travelling over rungs; replicas are labelled 0 .. n-1.
+     * State.  Per rung: replica[a], the label of the replica whose params sit at the rung; heading[a] in {0 none,
+     * 1 from-bottom: the last end visited was rung 0, 2 from-top: the last end visited was rung n-1}; the counters
+     * n_up[a], n_down[a], attempts[a].  Per replica: round_trips[label].  Initially replica[a] = a, heading[0] = 1,
+     * heading[n-1] = 2, all others 0 (n = 1: heading 0, and nothing ever changes), counters 0.
+     * For every swap attempt of any schedule -- pair (a, a+1), decided and applied by the unchanged primitives --
+     * in this order:
+     *   1. if the swap was accepted, rungs a and a+1 exchange (replica, heading): the label follows params, as
+     *      parallel_tempering_do_swap moves them, not the best point, which its quirk copies;
+     *   2. if a = 0 and the replica now at rung 0 has heading 2: round_trips[its label] += 1; then its heading = 1;
+     *   3. if a+1 = n-1: the replica now at rung n-1 gets heading 2;
+     *   4. for both rungs of the pair: n_up += 1 if the rung's heading is now 1, n_down += 1 if it is 2;
+     *   5. attempts[a] += 1 (the lower rung only): swapcount[a] / attempts[a] is the pair's swap rate.
+     * Counters move only at attempts a rung takes part in: under the default schedule the pair is drawn
+     * independently of the state, so this is an unbiased subsample of the per-round up / down fraction; under
+     * even-odd sweeps it is nearly every sweep.  A RANDOMSWAP attempt that draws "no attempt" changes nothing.
+     * The (replica, heading) word of a rung is one more field of the swap hand-off record, so the flow, like every
+     * other result, does not depend on launch boundaries, waves per chain or kernel family, and the chain itself
+     * -- every sample row, every state field -- is bit for bit what it is without the flag.
+     * Runs in the variant kernel instantiations (1, 2, 4 or 8 waves per chain; 6 is APEMOST_HIP_ERR_INVALID); the
+     * default kernels carry no test for it.  Combines with every model (user-supplied ones included), every swap
+     * schedule, both proposal laws, ADAPT, RWM, both launch forms and kernel families, and ladder batches (labels
+     * are per ladder, every array is [n_ladders][n_chains]).
+     * Not sharded: apemost_hip_create with chain_offset != 0 or n_chains_global != n_chains is refused with
+     * APEMOST_HIP_ERR_UNSUPPORTED before any device is touched, and so are, on such a sampler,
+     * apemost_hip_run_shards, apemost_hip_edge_export / import / exchange and apemost_hip_set_chain_offset. */
+    APEMOST_HIP_FLAG_TRACK_REPLICAS = 4096
 };
 
 typedef struct {
@@ -550,6 +582,20 @@ int apemost_hip_summary_get(apemost_hip_sampler *s, const apemost_hip_summary_vi
 int apemost_hip_summary_set(apemost_hip_sampler *s, const apemost_hip_summary_view *v);
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_summary_end(apemost_hip_sampler *s);
+
+/* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
+ * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
+typedef struct {
+    uint32_t *replica, *heading;
+    uint64_t *n_up, *n_down, *attempts, *round_trips;
+} apemost_hip_replica_flow_view; /* host, [n_chains] each (grid-wide, ladder-major); any may be NULL */
+/* synchronises like apemost_hip_get_state; after a timed-out hand-off the flow is void like the rest of the launch,
+ * and the error is the one get_state gives */
+int apemost_hip_replica_flow_get(apemost_hip_sampler *s, const apemost_hip_replica_flow_view *v);
+/* a resumed run: every ladder's labels must be a permutation of 0 .. n-1 and headings <= 2 (APEMOST_HIP_ERR_INVALID) */
+int apemost_hip_replica_flow_set(apemost_hip_sampler *s, const apemost_hip_replica_flow_view *v);
+/* labels to identity, headings and counters to the initial state: after burn-in */
+int apemost_hip_replica_flow_reset(apemost_hip_sampler *s);
 
 /* ---- test hooks: device RNG conformance ------------------------------------ */
 /* n raw 32-bit outputs of rocRAND philox4x32_10 (seed, subsequence, offset) */

@@ -2,7 +2,8 @@
 """Diagnostic for the one-barrier round kernel: per wave of workgroup 0, the cycles per step between
 leaving a step's barrier and arriving at the next (the wave's own work); the wave with the largest
 figure is the one the others wait for.  Uses the -DAPEMOST_STAMPS twin of the library.
-    python tools/ob_profile.py [model] [n_chain] [n_data] [waves]"""
+    python tools/ob_profile.py [model] [n_chain] [n_data] [waves] [flags]
+flags: apemost_hip_config.flags of the sampler (default 0), e.g. 4096 for the variant kernels with replica-flow tracking."""
 import ctypes as C
 import os
 import sys
@@ -22,6 +23,7 @@ def main():
     n_chain = int(sys.argv[2]) if len(sys.argv) > 2 else 128
     n_data = int(sys.argv[3]) if len(sys.argv) > 3 else 1024
     waves = int(sys.argv[4]) if len(sys.argv) > 4 else 8
+    flags = int(sys.argv[5]) if len(sys.argv) > 5 else 0
     w = wl.by_name(name, n_data=n_data, n_chain=n_chain)
     st = LadderState.from_params(n_chain, w.start, w.pmin, w.pmax, w.step * 0.3)
     for i in range(n_chain):
@@ -29,7 +31,7 @@ def main():
         st.step[i] = np.minimum(st.step[i] * st.beta[i] ** -0.5, w.pmax - w.pmin)
     L = capi.lib()
     L.apemost_hip_debug_stamps.argtypes = [C.POINTER(C.c_uint64)]
-    s = HipSampler(w.model, w.n_par, n_chain, w.data, seed=1, waves_per_chain=waves)
+    s = HipSampler(w.model, w.n_par, n_chain, w.data, seed=1, waves_per_chain=waves, flags=flags)
     s.set_state(st)
     out = (C.c_uint64 * 16)()
     s.run_sampler(20, 15)
@@ -37,7 +39,7 @@ def main():
     n_steps = 200 * 15
     s.run_sampler(200, 15)
     L.apemost_hip_debug_stamps(out)
-    print("one-barrier kernel, %s, %d chains x %d points, %d likelihood waves: cycles per step (workgroup 0)" % (name, n_chain, n_data, waves))
+    print("one-barrier kernel, %s, %d chains x %d points, %d likelihood waves, flags %d: cycles per step (workgroup 0)" % (name, n_chain, n_data, waves, flags))
     print("   whole step (owner, barrier to barrier)  %7.0f" % (out[15] / n_steps))
     for hw in range(waves + 4):
         role = "likelihood" if hw < waves else "owner" if hw == waves else "producer"
