@@ -7,8 +7,8 @@
  *
  * Pinning: the mt19937 and Philox streams, the manual's eval example, the reference's parser fixtures and the
  * survey's recorded config-1 counters are reproduced (tests/test_oracle_pins.py, test_oracle_workflow.py).
- * PARITY UNPINNED by reference-held fixtures for sampler trajectories, swaps, calibration and the pulse
- * likelihoods: the reference holds none and cannot be built here (no GSL); DESIGN.md 2.
+ * Sampler trajectories, swaps, calibration, the pulse likelihoods and the -D variants are held byte for byte to
+ * recorded runs of the compiled reference (tests/test_reference_pins.py).
  */
 #include "apemost_oracle.h"
 

@@ -9,9 +9,10 @@
  * Pinning status (see oracle/README.md):
  *   pinned   : mt19937 stream (GSL rng KATs), simplesin likelihood (manual eval
  *              KAT), params/data parser fixtures, gsl_sf_log KATs, mod_double KATs.
- *   unpinned : sampler trajectories, calibration results, swap sequences -- the
- *              reference holds no fixture for them and cannot be built here
- *              (GSL absent).  "parity unpinned" for those.
+ *   pinned   : sampler trajectories, calibration results and progress, swap sequences, the pulse
+ *              likelihoods and the -D variants, byte for byte against recorded runs of the compiled
+ *              reference (oracle/ref_build.py, tests/golden/ref_runs/, tests/test_reference_pins.py).
+ *   limit    : the GSL under that reference is this project's gslcompat.c, not real GSL.
  *
  * Every function cites the reference file:line (relative to the APEMoST tree)
  * whose behaviour it restates.

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generates tests/golden/oracle_vectors.json from the CPU oracle (oracle/apemost_oracle.c).
 
-The reference cannot be run here (it needs GSL, absent in the image), so these vectors are
-outputs of the restatement, which is itself pinned by tests/test_oracle_pins.py and
+These vectors are outputs of the restatement, which is itself pinned by tests/test_reference_pins.py
+(recorded runs of the compiled reference: make_ref_runs.py), tests/test_oracle_pins.py and
 tests/test_oracle_workflow.py; they freeze it against regressions and give the GPU tests fixed
 expected values.  Inputs are fully specified below (no files are read), so the script can be
 re-run anywhere:  python tests/golden/make_golden.py
