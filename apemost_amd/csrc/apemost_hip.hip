@@ -1873,7 +1873,8 @@ extern "C" int apemost_hip_summary_begin(apemost_hip_sampler *s, const apemost_h
     if (cfg->n_hist_chains > 0 && (!cfg->lo || !cfg->hi))
         return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: histograms need lo and hi");
     for (int p = 0; p < np && cfg->lo && cfg->hi; p++)
-        if (!std::isfinite(cfg->lo[p]) || !std::isfinite(cfg->hi[p]) || !(cfg->lo[p] < cfg->hi[p]))
+        if (!std::isfinite(cfg->lo[p]) || !std::isfinite(cfg->hi[p]) || !(cfg->lo[p] < cfg->hi[p]) ||
+            !std::isfinite(cfg->hi[p] - cfg->lo[p])) // (a width that overflows: the bin guess divides by it)
             return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: parameter %d: range [%g, %g] invalid", p, cfg->lo[p],
                         cfg->hi[p]);
     const size_t n_hp = (size_t)cfg->n_hist_chains * np;

@@ -4,14 +4,21 @@
 // whatever the calls' boundaries are:
 //   prob_sum[c]      sum of column n_par+1 (prob - prior) of chain c, `sum += v` in sample order
 //                    (analyse_data_probability);
-//   hist[h][p][b]    counts of chain h's parameter p in the bins of marginal_distribution();
+//   hist[h][p][b]    counts of chain h's parameter p in the bins of marginal_distribution(), which are those of
+//                    the reference's create_hist(): GSL's gsl_histogram_set_ranges_uniform edges
+//                    ((n-b)/n)*lo + (b/n)*hi, the top one widened by (hi-lo)/10000, bin b = [e[b], e[b+1]);
 //   batch[h][p][k]   the batch sums of batch_means_error(): batch 0 holds bs-1 samples, every later one bs;
 //                    slot n_batches holds the running sum of the batch that is still open.
 // One launch per batch of rows.  Workgroups [0, n_hist*n_par) own one (h, p) each: its bins live in LDS
 // (ds_add_u32) and go to its own slice of `hist` with plain loads and stores; lane 0 walks the values in
 // sample order for the batch sums.  The workgroups behind them give one thread per chain for prob_sum.
 // No float atomics anywhere: every sum is one thread's sequential chain, so arrival order cannot change
-// a bit, and no multiply feeds an add (contraction is off as well).
+// a bit, and contraction is off (the edge formula's two products feed an add unfused, as on the host).
+// The edges were lo + (hi-lo)*b/n before; that differs from GSL's formula by up to one ulp at about a quarter of
+// the edges, so counts in a summary.bin written before this change were binned on edges up to one ulp away.
+// Each histogram workgroup now computes its nbins+1 edges once per launch into LDS (32 KB more) and bisects
+// them per value: ceil(log2 nbins) LDS reads and compares in place of a division, a multiply and two
+// recomputed edges.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,36 +44,39 @@ struct SummaryArgs {
     unsigned long long batch_stride; // max_batches + 1
 };
 
-// marginal_distribution()'s edges: lo + (hi-lo)*b/nbins, the top one widened by (hi-lo)/10000
+// gsl_histogram_set_ranges_uniform's edge b of n over [lo, hi], the top one widened as create_hist() does
 __device__ inline double summary_edge(double lo, double hi, int b, int nbins) {
 #pragma clang fp contract(off)
-    double e = lo + (hi - lo) * (double)b / (double)nbins;
+    const double f1 = (double)(nbins - b) / (double)nbins, f2 = (double)b / (double)nbins;
+    double e = f1 * lo + f2 * hi;
     if (b == nbins)
         e += (hi - lo) / 10000;
     return e;
 }
 
-// the bin of v, or -1 when v lies outside [edges[0], edges[nbins]) (NaN included)
-__device__ inline int summary_bin(double v, double lo, double hi, double e0, double en, int nbins) {
-#pragma clang fp contract(off)
-    if (!(v >= e0 && v < en))
+// the bin of v over the edges e[0 .. nbins], or -1 when v lies outside [e[0], e[nbins]) (NaN included):
+// gsl_histogram_increment's bisection, step for step as the host's (gslcompat.c).  GSL's uniform edges are not
+// always sorted -- over [1e15, 1e15+3] with 200 bins six of them step back by an ulp -- and there a guess from
+// the spacing followed by a walk settles in another bin than the host does; the same bisection cannot.
+__device__ inline int summary_bin(double v, const double *e, int nbins) {
+    if (!(v >= e[0] && v < e[nbins]))
         return -1;
-    int b = (int)((v - lo) / (hi - lo) * nbins);
-    if (b >= nbins)
-        b = nbins - 1;
-    if (b < 0)
-        b = 0;
-    while (b > 0 && v < summary_edge(lo, hi, b, nbins))
-        b--;
-    while (b < nbins - 1 && v >= summary_edge(lo, hi, b + 1, nbins))
-        b++;
-    return b;
+    int left = 0, right = nbins;
+    while (right - left > 1) { // e[left] <= v < e[right]
+        const int mid = (left + right) >> 1;
+        if (v >= e[mid])
+            left = mid;
+        else
+            right = mid;
+    }
+    return left;
 }
 
 __global__ void __launch_bounds__(kSummaryThreads) summary_kernel(SummaryArgs a) {
 #pragma clang fp contract(off)
     __shared__ unsigned int bins[kSummaryMaxBins];
     __shared__ double vals[kSummaryChunk];
+    __shared__ double edges[kSummaryMaxBins + 1];
     const int t = threadIdx.x;
     const size_t row = (size_t)a.n_chains * (a.n_par + 2);
     const int hp = blockIdx.x;
@@ -86,9 +96,10 @@ __global__ void __launch_bounds__(kSummaryThreads) summary_kernel(SummaryArgs a)
     }
     const int h = hp / a.n_par, p = hp - h * a.n_par;
     const double lo = a.lo[p], hi = a.hi[p];
-    const double e0 = summary_edge(lo, hi, 0, a.nbins), en = summary_edge(lo, hi, a.nbins, a.nbins);
     for (int b = t; b < a.nbins; b += kSummaryThreads)
         bins[b] = 0;
+    for (int b = t; b <= a.nbins; b += kSummaryThreads)
+        edges[b] = summary_edge(lo, hi, b, a.nbins);
     const double *src = a.rows + a.skip * row + (size_t)h * (a.n_par + 2) + p;
     const size_t stride = (size_t)a.thin * row;
     double *batch = a.batch + (size_t)hp * a.batch_stride;
@@ -103,7 +114,7 @@ __global__ void __launch_bounds__(kSummaryThreads) summary_kernel(SummaryArgs a)
         for (int i = t; i < len; i += kSummaryThreads) {
             const double v = src[(k0 + i) * stride];
             vals[i] = v;
-            const int b = summary_bin(v, lo, hi, e0, en, a.nbins);
+            const int b = summary_bin(v, edges, a.nbins);
             if (b >= 0)
                 atomicAdd(&bins[b], 1u);
         }

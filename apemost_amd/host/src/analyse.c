@@ -1,6 +1,6 @@
 /* `analyse` phase: post-processing of the run phase's dump files on the host (disk-bound work,
  * outside the GPU path).  Same inputs, outputs and formulas as reference
- * src/analyse.c:33-285 and its histogram helper (src/histogram.c:33-42): the thermodynamic
+ * src/analyse.c:33-285 and its histogram helper (src/histogram.c:33-42, create_hist): the thermodynamic
  * integral over beta of the mean log-likelihood, and per-parameter marginal histograms with a
  * batch-means Monte-Carlo error.  The reference's n_beta < 100 limit does not apply.
  * With `summary` in APEMOST_DUMP the same numbers come from summary.bin (run_summary.h), the sums the
@@ -13,6 +13,7 @@
 #include "utils.h"
 #include "debug.h"
 #include "run_summary.h"
+#include "histogram.h"
 
 #ifndef NBINS
 #define NBINS 200
@@ -136,13 +137,17 @@ static double batch_means_error(double mean, const char *filename, unsigned long
 }
 
 /* NBINS-bin density of one parameter's visited values (chain 0) over [min, max] of the prior box
- * (or of the data with -DHISTOGRAMS_MINMAX); the top edge is widened by 1e-4 of the range so the
- * maximum falls into the last bin.  Output: "<name>.histogram", lines "lower upper density". */
+ * (or of the data with -DHISTOGRAMS_MINMAX), on the reference's own histogram: create_hist() -- GSL's
+ * uniform edges ((n-b)/n)*min + (b/n)*max, the top one widened by 1e-4 of the range so the maximum falls
+ * into the last bin -- gsl_histogram_increment, _scale, _fprintf, _mean and _sigma, call for call as
+ * reference src/analyse.c:216-240.  With a run summary the counts come from it instead of the increments;
+ * the device binned them on the same edges.  Output: "<name>.histogram", lines "lower upper density". */
 static void marginal_distribution(mcmc **chains, unsigned int param, int find_minmax, const run_summary *summary) {
     const char *name = get_params_descr(chains[0])[param];
     double lo = get_params_min_for(chains[0], param), hi = get_params_max_for(chains[0], param);
-    double bins[NBINS], edges[NBINS + 1], v, total = 0, mean = 0, var = 0, width, err;
+    double v, total, mean, sigma, err;
     char in_name[300], out_name[300];
+    gsl_histogram *h;
     FILE *f;
     int b;
     sprintf(in_name, "%s-chain-%d.prob.dump", name, 0);
@@ -166,55 +171,23 @@ static void marginal_distribution(mcmc **chains, unsigned int param, int find_mi
         }
         fclose(f);
     }
-    for (b = 0; b <= NBINS; b++)
-        edges[b] = lo + (hi - lo) * b / NBINS;
-    edges[NBINS] += (hi - lo) / 10000;
-    memset(bins, 0, sizeof bins);
+    h = create_hist(NBINS, lo, hi);
     printf("reading values: chain %3d parameter %s   \r", 0, name);
     fflush(stdout);
     if (summary != NULL)
-        for (b = 0; b < NBINS; b++) {
-            bins[b] = (double)summary->hist[(size_t)param * NBINS + b];
-            total += bins[b];
-        }
-    f = summary != NULL ? NULL : openfile(in_name);
-    while (f != NULL && fscanf(f, "%lf", &v) == 1) {
-        if (v < edges[0] || v >= edges[NBINS])
-            continue;
-        b = (int)((v - lo) / (hi - lo) * NBINS);
-        if (b >= NBINS)
-            b = NBINS - 1;
-        while (b > 0 && v < edges[b])
-            b--;
-        while (b < NBINS - 1 && v >= edges[b + 1])
-            b++;
-        bins[b] += 1;
-        total += 1;
-    }
-    if (f != NULL)
-        fclose(f);
-    width = (hi - lo) / NBINS;
+        for (b = 0; b < NBINS; b++)
+            h->bin[b] = (double)summary->hist[(size_t)param * NBINS + b];
+    else
+        append_to_hists(&h, 1, in_name);
+    total = gsl_histogram_sum(h);
+    gsl_histogram_scale(h, (hi - lo) / NBINS / total);
     f = fopen(out_name, "w");
     assert(f != NULL);
-    for (b = 0; b < NBINS; b++) {
-        bins[b] *= width / total; /* the reference's scaling: (max-min)/nbins/iterations */
-        fprintf(f, DUMP_FORMAT " " DUMP_FORMAT " " DUMP_FORMAT "\n", edges[b], edges[b + 1], bins[b]);
-    }
+    gsl_histogram_fprintf(f, h, DUMP_FORMAT, DUMP_FORMAT);
     fclose(f);
-    {
-        double wsum = 0;
-        for (b = 0; b < NBINS; b++) { /* histogram mean and sigma from the bin centres */
-            const double centre = 0.5 * (edges[b] + edges[b + 1]);
-            wsum += bins[b];
-            mean += bins[b] * centre;
-        }
-        mean /= wsum;
-        for (b = 0; b < NBINS; b++) {
-            const double d = 0.5 * (edges[b] + edges[b + 1]) - mean;
-            var += bins[b] * d * d;
-        }
-        var /= wsum;
-    }
+    mean = gsl_histogram_mean(h);
+    sigma = gsl_histogram_sigma(h);
+    gsl_histogram_free(h);
     if (summary != NULL) {
         const unsigned long want = (unsigned long)sqrt(total);
         err = batch_means_error_summary(mean, summary->batch_sums + (size_t)param * (summary->max_batches + 1),
@@ -224,7 +197,7 @@ static void marginal_distribution(mcmc **chains, unsigned int param, int find_mi
                     (unsigned long)summary->bs, RUN_SUMMARY_FILE, total, want);
     } else
         err = batch_means_error(mean, in_name, (unsigned long)sqrt(total));
-    printf("mcmc error estimate of %s: %f %s\n", name, err, (err > sqrt(var) * 0.01 ? "** high!" : " (ok)"));
+    printf("mcmc error estimate of %s: %f %s\n", name, err, (err > sigma * 0.01 ? "** high!" : " (ok)"));
     printf("Note: Include a error estimate in your publication!\n");
 }
 

@@ -50,24 +50,26 @@ def batch_size_for(n_samples):
 
 
 def edges(lo, hi, nbins):
-    """marginal_distribution()'s bin edges: lo + (hi-lo)*b/nbins, the top one widened by (hi-lo)/10000"""
-    e = [lo + (hi - lo) * b / nbins for b in range(nbins + 1)]
+    """marginal_distribution()'s bin edges, which are the reference's create_hist(): GSL's
+    gsl_histogram_set_ranges_uniform, ((n-b)/n)*lo + (b/n)*hi, the top one widened by (hi-lo)/10000"""
+    e = [((nbins - b) / nbins) * lo + (b / nbins) * hi for b in range(nbins + 1)]
     e[nbins] += (hi - lo) / 10000
     return np.array(e)
 
 
 def bin_of(v, lo, hi, e):
-    """marginal_distribution()'s bin of v, or -1 outside [e[0], e[nbins]) (NaN included)"""
-    nbins = len(e) - 1
-    if not (v >= e[0] and v < e[nbins]):
+    """gsl_histogram_increment's bin of v over the edges e (bin b holds e[b] <= v < e[b+1]), or -1 outside
+    [e[0], e[nbins]) (NaN included): a bisection, as in the host's gslcompat.c"""
+    left, right = 0, len(e) - 1
+    if not (v >= e[0] and v < e[right]):
         return -1
-    b = int((v - lo) / (hi - lo) * nbins)
-    b = min(max(b, 0), nbins - 1)
-    while b > 0 and v < e[b]:
-        b -= 1
-    while b < nbins - 1 and v >= e[b + 1]:
-        b += 1
-    return b
+    while right - left > 1:
+        mid = (left + right) // 2
+        if v >= e[mid]:
+            left = mid
+        else:
+            right = mid
+    return left
 
 
 def gelman_rubin(rows, n_ladders, chain=0):
@@ -146,7 +148,7 @@ class RunSummary:
         batch = np.zeros((n_hist_chains, n_par, max_batches + 1))
         for h in range(n_hist_chains):
             for p in range(n_par):
-                e = edges(float(lo[p]), float(hi[p]), nbins)
+                e = edges(float(lo[p]), float(hi[p]), nbins).tolist()
                 part, nb = 0.0, 0
                 for i, v in enumerate(rows[:, h, p].tolist()):
                     b = bin_of(v, float(lo[p]), float(hi[p]), e)
@@ -184,8 +186,9 @@ class RunSummary:
         return ladder_evidences(self.prob_sum, self.n, betas, n_ladders)
 
     def histogram_density(self, p, h=0):
-        """(edges, density, mean, sigma) of parameter p of chain h: counts * width / total, and the
-        bin-centre mean and standard deviation of marginal_distribution()"""
+        """(edges, density, mean, sigma) of parameter p of chain h: counts * width / total (gsl_histogram_scale), and
+        the mean and standard deviation of the bin centres by the running recurrences of gsl_histogram_mean and
+        gsl_histogram_sigma, operation for operation"""
         lo, hi = float(self.lo[p]), float(self.hi[p])
         e = edges(lo, hi, self.nbins)
         counts = self.hist[h, p].astype(np.float64).tolist()
@@ -194,17 +197,18 @@ class RunSummary:
             total += c
         width = (hi - lo) / self.nbins
         dens = [c * (width / total) for c in counts]
+        el = e.tolist()
         wsum = mean = 0.0
         for b in range(self.nbins):
-            centre = 0.5 * (e[b] + e[b + 1])
-            wsum += dens[b]
-            mean += dens[b] * centre
-        mean /= wsum
-        var = 0.0
+            if dens[b] > 0:
+                wsum += dens[b]
+                mean += ((el[b + 1] + el[b]) / 2 - mean) * (dens[b] / wsum)
+        wsum = var = 0.0
         for b in range(self.nbins):
-            d = 0.5 * (e[b] + e[b + 1]) - mean
-            var += dens[b] * d * d
-        var /= wsum
+            if dens[b] > 0:
+                d = (el[b + 1] + el[b]) / 2 - mean
+                wsum += dens[b]
+                var += (d * d - var) * (dens[b] / wsum)
         return e, np.array(dens), mean, math.sqrt(var)
 
     def batch_means_error(self, p, h=0, mean=None):

@@ -9,11 +9,14 @@ wrote in that phase, byte for byte; acceptance_rate.dump and calibration_results
 (the dumps of runs of 1000 steps and more, most calibration_progress.data) is held by <phase>/digests.json --
 its SHA-256 and one per block of 100 lines -- and <name>.excerpt, its first and last lines
 (ref_build.to_fixture).  Ours are also case.json (what the case is), exit_status (one line per phase that
-ran) and points_*.txt (the stdin of eval_main).  The inputs `params` and `data` come from
+ran) and points_*.txt (the stdin of eval_main).  analyse/... are what the fourth phase left: every
+<name>.histogram (digested like the dumps), marginal_distributions.gnuplot and stdout, the latter without its
+carriage-return progress segments (ref_build.cut_progress); an analyse-only case (kind "analyse") holds nothing
+else, its run directory being that of the case it names with "of".  The inputs `params` and `data` come from
 apemost_amd/workloads.py and are not stored.  tests/test_reference_pins.py runs the same binaries again where
 the reference is present and asserts that nothing here has gone stale.
 
-Size: no case above MAX_FILE (the largest older fixture, testlc.dat), the whole set under 100 KB.
+Size: no case above MAX_FILE (the largest older fixture, testlc.dat), the whole set under 160 KB.
 """
 import json
 import os
@@ -31,9 +34,11 @@ MAX_FILE = 77622
 
 def case_json(case):
     c = rb.CASES[case]
-    return json.dumps(dict(kind=c["kind"], model=c["model"], n_data=c["n_data"], workload_seed=c["wl_seed"],
-                           macros=c["macros"], env=dict(GSL_RNG_SEED=str(c["gsl_seed"]), OMP_NUM_THREADS="1")),
-                      sort_keys=True) + "\n"
+    d = dict(kind=c["kind"], model=c["model"], n_data=c["n_data"], workload_seed=c["wl_seed"],
+             macros=c["macros"], env=dict(GSL_RNG_SEED=str(c["gsl_seed"]), OMP_NUM_THREADS="1"))
+    if "of" in c:
+        d["of"] = c["of"]
+    return json.dumps(d, sort_keys=True) + "\n"
 
 
 def fixture_files(case, workdir):
@@ -59,6 +64,8 @@ def main(cases):
     total = 0
     for case in cases or sorted(rb.CASES):
         rb.build_case(case)
+        if "of" in rb.CASES[case]:
+            rb.build_case(rb.CASES[case]["of"])
         with tempfile.TemporaryDirectory() as tmp:
             files = fixture_files(case, tmp)
         shutil.rmtree(os.path.join(OUT, case), ignore_errors=True)

@@ -12,9 +12,9 @@ import torch
 
 from apemost_amd import capi, workloads as wl
 from apemost_amd.sampler import HipSampler
-from apemost_amd.summary import RunSummary, batches_closed
+from apemost_amd.summary import RunSummary, batch_size_for, batches_closed
 from oracle import oracle as orc
-from tests import hostlib
+from tests import hostlib, summary_rows as sr
 from tests.helpers import make_pair
 
 pytestmark = pytest.mark.gpu
@@ -197,8 +197,10 @@ def test_invalid_arguments():
     inf_lo[0] = -np.inf
     nan_hi = hi.copy()
     nan_hi[1] = np.nan
-    for kw in (dict(hi_=bad_hi), dict(lo_=inf_lo), dict(hi_=nan_hi), dict(nbins=0), dict(nbins=4097),
-               dict(nh=-1), dict(nh=5), dict(bs=0)):
+    wide_lo, wide_hi = lo.copy(), hi.copy()
+    wide_lo[3], wide_hi[3] = -1e308, 1e308                   # both finite, hi - lo is not
+    for kw in (dict(hi_=bad_hi), dict(lo_=inf_lo), dict(hi_=nan_hi), dict(lo_=wide_lo, hi_=wide_hi), dict(nbins=0),
+               dict(nbins=4097), dict(nh=-1), dict(nh=5), dict(bs=0)):
         assert begin(**kw) == capi.ERR_INVALID, kw
     assert begin(nh=4, nbins=4096) == capi.OK
     assert begin(bs=4, mb=2) == capi.OK
@@ -215,6 +217,88 @@ def test_invalid_arguments():
     s.summary_end()
     assert L.apemost_hip_summary_get(s._h, C.byref(view)) == capi.ERR_INVALID
     s.close()
+
+
+# ---- hand-built rows against a restatement that shares nothing with the kernel (tests/summary_rows.py) ----------
+@pytest.mark.parametrize("box_set,nbins,bs", [("A", 1, 1000), ("B", 1, 1), ("A", 2, 1), ("B", 2, 1000), ("A", 200, 1000),
+                                              ("B", 200, 1), ("A", 200, 1), ("A", 4096, 1), ("B", 4096, 1000)])
+def test_summary_of_hand_built_rows(box_set, nbins, bs):
+    """Every edge of every parameter with its two neighbours, the box's corners, the widened top, zeros,
+    subnormals, infinities, NaN of both signs and values far outside, over boxes where the spacing guess is off by
+    one, a negative box and one of width 1e-300; 300 chains, all of them histogrammed (prob_sum spans two
+    workgroups); 2300 kept steps in the first call (three passes, the last ragged), then two thinned calls;
+    batch size 1 or 1000 (batch 1 straddles the first pass boundary).  Counts equal np.searchsorted over GSL's
+    edges, prob_sum and the batch sums equal sequential float additions, all exactly; a sum that is NaN on the
+    host (inf - inf in the columns that hold the non-finite values) must be NaN on the device."""
+    n_chains = 300
+    rows, boxes = sr.build_rows(box_set, nbins, n_chains)
+    w = wl.simplesin(n_data=16, n_chain=n_chains)
+    s = HipSampler(w.model, w.n_par, n_chains, w.data, seed=1)
+    d = torch.from_numpy(rows).cuda()
+    torch.cuda.synchronize()
+    n_kept = len(sr.kept_steps())
+    mb = batches_closed(n_kept, bs)
+    lo, hi = np.array([b[0] for b in boxes]), np.array([b[1] for b in boxes])
+    s.summary_begin(lo, hi, n_hist_chains=n_chains, nbins=nbins, batch_size=bs, max_batches=mb)
+    for first, n, skip, thin in sr.CALLS:
+        s.summary_accumulate(d[first:].data_ptr(), n, skip, thin)
+    got = s.summary()
+    s.close()
+    n, prob_sum, hist, batch = sr.expected(rows, boxes, nbins, bs, n_chains)
+    assert got.n == n == n_kept and got.n_batches == mb
+    assert got.prob_sum.tobytes() == prob_sum.tobytes()
+    bad = np.argwhere(got.hist != hist)
+    assert len(bad) == 0, "first of %d differing counts: chain %d parameter %d bin %d: %d, expected %d" % (
+        (len(bad),) + tuple(bad[0]) + (got.hist[tuple(bad[0])], hist[tuple(bad[0])]))
+    assert int(hist[1].sum()) > 0 and int(hist[:, :, nbins - 1].sum()) > 0
+    for (h, p), (closed, part) in batch.items():
+        want = np.array(closed + [part])
+        have = got.batch_sums[h, p, :mb + 1]
+        assert len(closed) == mb
+        if h % 3:                                            # the finite columns: bit for bit
+            assert have.tobytes() == want.tobytes(), (h, p)
+        else:
+            assert np.array_equal(np.isnan(have), np.isnan(want)), (h, p)
+            ok = ~np.isnan(want)
+            assert have[ok].tobytes() == want[ok].tobytes(), (h, p)
+
+
+# ---- the device against the recorded reference: kernel -> summary.bin -> analyse -> fixture -------------------------
+@pytest.mark.parametrize("case", ["simplesin", "pulse"])
+def test_device_summary_through_analyse_equals_the_reference(case, golden_dir, tmp_path, tmp_path_factory):
+    """rows parsed from the oracle-regenerated dump text of a recorded case, accumulated on the device in three
+    uneven pieces; `analyse` with APEMOST_DUMP=summary on the summary.bin written from the device's numbers
+    leaves the histogram files, the gnuplot file and the stdout that the compiled reference left, byte for byte"""
+    from tests import test_reference_analyse as ra
+    want, status = ra.fixture_analyse(golden_dir, case)
+    files = ra.run_dumps(case, tmp_path_factory)
+    rows = ra.parsed_rows(case, files)
+    _, lo, hi = ra.box(case, files)
+    n, n_beta, width = rows.shape
+    w = rb_workload(case)
+    s = HipSampler(w.model, w.n_par, n_beta, w.data, seed=1)
+    d = torch.from_numpy(rows).cuda()
+    torch.cuda.synchronize()
+    bs = batch_size_for(n)
+    s.summary_begin(np.array(lo), np.array(hi), n_hist_chains=1, nbins=NBINS, batch_size=bs, max_batches=batches_closed(n, bs))
+    off = 0
+    for piece in (7, 1031, n - 1038):
+        s.summary_accumulate(d[off:].data_ptr(), piece)
+        off += piece
+    got = s.summary()
+    s.close()
+    assert got.n == n
+    got.write(str(tmp_path / "summary.bin"))
+    ra.write_inputs(tmp_path, files, dumps=False)
+    r = ra.run_host_analyse(ra.host_exe(case, tmp_path_factory), tmp_path, case, summary=True)
+    assert r.returncode == status and r.stderr == b"", r.stderr.decode()
+    ra.assert_equals_fixture(case, files, ra.collect(case, tmp_path, r), want,
+                             "device summary -> analyse vs reference, case %s" % case)
+
+
+def rb_workload(case):
+    from oracle import ref_build as rb
+    return rb.workload(case)
 
 
 # ---- the C host: APEMOST_DUMP=summary ----------------------------------------------------------------------

@@ -183,6 +183,9 @@ def test_oracle_reproduces_the_reference_run(case, golden_dir, tmp_path):
     exit status of each phase (a failed calibration included: pulse_vrot_calibration_fails)."""
     want = _fixture(golden_dir, case)
     want.pop("case.json")
+    # the fourth phase's entries (analyse/..., its exit_status line) are tests/test_reference_analyse.py's
+    want = {n: b for n, b in want.items() if not n.startswith("analyse/")}
+    want["exit_status"] = b"".join(l for l in want["exit_status"].splitlines(True) if not l.startswith(b"analyse "))
     raw = _oracle_case(case, tmp_path)
     _assert_same_files(rb.to_fixture(case, raw), want, "oracle vs reference, case %s" % case, raw)
 
@@ -243,9 +246,10 @@ def test_fixture_equals_a_fresh_reference_run(case, golden_dir, tmp_path):
 
 def test_fixture_set_is_complete_and_small(golden_dir):
     """every case of the recipe has a fixture, nothing else lies there, no case above the older largest
-    fixture (testlc.dat) and the whole set stays under a hundred KB"""
+    fixture (testlc.dat) and the whole set stays under 160 KB (100 KB before the analyse phase was recorded:
+    seven cases gained 37 KB of histogram digests, excerpts, gnuplot files and stdout)"""
     root = os.path.join(str(golden_dir), "ref_runs")
     assert sorted(os.listdir(root)) == sorted(rb.CASES)
     limit = os.path.getsize(os.path.join(str(golden_dir), "testlc.dat"))
     sizes = [os.path.getsize(rb.fixture_path(golden_dir, case)) for case in rb.CASES]
-    assert max(sizes) <= limit and sum(sizes) <= 100 * 1024
+    assert max(sizes) <= limit and sum(sizes) <= 160 * 1024

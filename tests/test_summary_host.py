@@ -6,6 +6,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 from apemost_amd import build, capi, workloads as wl
 from apemost_amd.state import LadderState
@@ -191,3 +192,54 @@ def test_histograms_minmax_with_summary_is_refused(tmp_path):
     r = _run(exe, dirs["summary"], {"APEMOST_DUMP": "summary"})
     assert r.returncode == 1 and "HISTOGRAMS_MINMAX" in r.stderr, r.stderr
     assert _run(exe, dirs["text"], {}).returncode == 0
+
+
+# ---- the restatement that judges the kernel on hand-built rows (tests/summary_rows.py), checked on the CPU ----------
+_nbins_exe = {}
+
+
+@pytest.mark.parametrize("nbins", [1, 2, 200, 4096])
+@pytest.mark.parametrize("box_set", ["A", "B"])
+def test_restated_bins_equal_host_analyse_and_from_rows(box_set, nbins, tmp_path, tmp_path_factory):
+    """The finite values of the hand-built rows that "%.15e" holds exactly, as dump files of chain 0, through the
+    host's `analyse` in text mode (create_hist and gsl_histogram_increment in C): its counts are those of
+    np.searchsorted over GSL's edges (summary_rows.bins_of) and those of RunSummary.from_rows"""
+    from tests import summary_rows as sr
+    rows, boxes = sr.build_rows(box_set, nbins, n_chains=30)
+    if nbins not in _nbins_exe:
+        _nbins_exe[nbins] = hostlib.make(str(tmp_path_factory.mktemp("nbins%d" % nbins) / "sine.exe"),
+                                         ccflags="-DN_BETA=2 -DNBINS=%d" % nbins)
+    names = ["amplitude", "frequency", "phase", "offset"]
+    for p, (lo, hi) in enumerate(boxes):
+        assert float("%.15e" % lo) == lo and float("%.15e" % hi) == hi
+    (tmp_path / "params").write_text("".join("%.15e\t%.15e\t%.15e\t%s\t%.15e\n" % ((lo + hi) / 2, lo, hi, n, -1)
+                                             for (lo, hi), n in zip(boxes, names)))
+    (tmp_path / "data").write_text(wl.simplesin(n_data=16, n_chain=2).data_file_text())
+    st = LadderState.from_params(2, [(lo + hi) / 2 for lo, hi in boxes], [b[0] for b in boxes], [b[1] for b in boxes],
+                                 [-1.0] * 4)
+    st.beta[1] = 0.5
+    (tmp_path / "calibration_results").write_text(st.calibration_results_text())
+    for c in range(2):
+        (tmp_path / ("prob-chain%d.dump" % c)).write_text("%6e\t%6e\n" % (-50.0, -40.0))
+    kept = {}
+    for p, name in enumerate(names):
+        v = np.concatenate([rows[:, h, p] for h in range(30)])
+        v = v[np.isfinite(v)]
+        v = np.array([x for x in v.tolist() if float("%.15e" % x) == x])
+        assert len(v) > 1000
+        kept[p] = v
+        (tmp_path / ("%s-chain-0.prob.dump" % name)).write_text("".join("%.15e\n" % x for x in v))
+    r = _run(_nbins_exe[nbins], tmp_path, {})
+    assert r.returncode == 0, r.stderr
+    for p, name in enumerate(names):
+        lo, hi = boxes[p]
+        e = sr.gsl_edges(lo, hi, nbins)
+        want = sr.bins_of(kept[p], e)
+        total = float(want.sum())
+        assert 0 < total < len(kept[p])                      # some inside, some outside the box
+        lines = [l.split() for l in (tmp_path / (name + ".histogram")).read_text().splitlines()]
+        assert [l[0] for l in lines] == ["%.15e" % x for x in e[:-1]] and lines[-1][1] == "%.15e" % e[-1]
+        scale = (hi - lo) / nbins / total
+        assert [l[2] for l in lines] == ["%.15e" % (float(c) * scale) for c in want.tolist()], (name, nbins)
+        rs = RunSummary.from_rows(kept[p].reshape(-1, 1, 1).repeat(3, axis=2), 1, nbins, 1, len(kept[p]), [lo], [hi])
+        assert rs.hist[0, 0].tolist() == want.tolist(), (name, nbins)
