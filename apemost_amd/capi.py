@@ -66,6 +66,18 @@ class SummaryView(C.Structure):
     _fields_ = [("n", _up), ("prob_sum", _dp), ("hist", _up), ("batch_sums", _dp), ("n_batches", _up)]
 
 
+class PeaksConfig(C.Structure):
+    _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("capacity", C.c_uint64), ("lo", _dp), ("hi", _dp)]
+
+
+class PeaksView(C.Structure):
+    _fields_ = [("n", _up), ("n_values", _up), ("n_peaks", C.POINTER(C.c_uint32)), ("left", _up), ("right", _up),
+                ("q", _dp), ("q_set", C.POINTER(C.c_uint8))]
+
+
+PEAKS_MAX = 99   # peaks described per column (include/apemost_hip.h)
+
+
 class ReplicaFlowView(C.Structure):
     _fields_ = [("replica", C.POINTER(C.c_uint32)), ("heading", C.POINTER(C.c_uint32)), ("n_up", _up), ("n_down", _up),
                 ("attempts", _up), ("round_trips", _up)]
@@ -94,6 +106,8 @@ EXPORTS = [
     "apemost_hip_device_free",
     "apemost_hip_create_batch", "apemost_hip_n_ladders", "apemost_hip_set_data_ladder",
     "apemost_hip_replica_flow_get", "apemost_hip_replica_flow_set", "apemost_hip_replica_flow_reset",
+    "apemost_hip_peaks_begin", "apemost_hip_peaks_accumulate", "apemost_hip_peaks_get", "apemost_hip_peaks_end",
+    "apemost_hip_peaks_table",
 ]
 
 _lib = None
@@ -199,6 +213,12 @@ def lib():
     L.apemost_hip_replica_flow_get.argtypes = [vp, C.POINTER(ReplicaFlowView)]
     L.apemost_hip_replica_flow_set.argtypes = [vp, C.POINTER(ReplicaFlowView)]
     L.apemost_hip_replica_flow_reset.argtypes = [vp]
+    L.apemost_hip_peaks_begin.argtypes = [vp, C.POINTER(PeaksConfig)]
+    L.apemost_hip_peaks_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_peaks_get.argtypes = [vp, C.POINTER(PeaksView)]
+    L.apemost_hip_peaks_end.argtypes = [vp]
+    L.apemost_hip_peaks_table.argtypes = [C.POINTER(PeaksView), C.c_int32, C.c_int32, C.c_int32, _dp,
+                                          C.POINTER(C.c_uint32)]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

@@ -1,6 +1,7 @@
 // apemost_hip.hip -- kernels and C ABI of the gfx950 parallel-tempering engine
 // (declared in include/apemost_hip.h).  Written for MI355X only.
 #include "pt_kernels.h"
+#include "pt_peaks.h"
 #include "pt_summary.h"
 #include "pt_text.h"
 
@@ -347,6 +348,15 @@ struct apemost_hip_sampler {
         double *d_lo, *d_hi, *d_prob_sum, *d_batch;
         u64 *d_hist;
     } sum;
+    // on-device peaks (apemost_hip_peaks_begin .. end): the kept chains' parameter columns, appended on copy_stream
+    struct {
+        bool open;
+        int n_keep;
+        u64 capacity;
+        u64 n; // samples stored per column (the host knows it without a sync)
+        int *d_chains;
+        double *d_lo, *d_hi, *d_cols;
+    } pk;
 };
 
 extern "C" const char *apemost_hip_last_error(void) { return g_last_error.c_str(); }
@@ -459,6 +469,13 @@ static void summary_free(apemost_hip_sampler *s) {
     s->sum = {};
 }
 
+static void peaks_free(apemost_hip_sampler *s) {
+    for (void *p : {(void *)s->pk.d_chains, (void *)s->pk.d_lo, (void *)s->pk.d_hi, (void *)s->pk.d_cols})
+        if (p)
+            hipFree(p);
+    s->pk = {};
+}
+
 // everything a sampler owns on the device; safe on a half-built sampler
 static void release(apemost_hip_sampler *s) {
     if (s->stream)
@@ -486,6 +503,7 @@ static void release(apemost_hip_sampler *s) {
         hipStreamDestroy(s->copy_stream);
     }
     summary_free(s); // (its kernels ran on copy_stream)
+    peaks_free(s);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {
@@ -2022,6 +2040,264 @@ extern "C" int apemost_hip_summary_end(apemost_hip_sampler *s) {
     if (s->copy_stream)
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     summary_free(s);
+    return APEMOST_HIP_OK;
+}
+
+// ---- on-device peaks (pt_peaks.h) ----
+extern "C" int apemost_hip_peaks_begin(apemost_hip_sampler *s, const apemost_hip_peaks_config *cfg) {
+    CHECK_S(s);
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: config is NULL");
+    const int np = s->cfg.n_par;
+    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
+                    s->cfg.n_chains);
+    if ((long long)cfg->n_keep * np > 65535)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: %d chains of %d parameters are more than 65535 columns",
+                    cfg->n_keep, np);
+    for (int k = 0; k < cfg->n_keep; k++)
+        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
+            return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing",
+                        k, cfg->chains[k], s->cfg.n_chains);
+    if (cfg->capacity < 1 || cfg->capacity > ((u64)1 << 30))
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: capacity %llu outside [1, 2^30]",
+                    (unsigned long long)cfg->capacity);
+    if (!cfg->lo || !cfg->hi)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: lo and hi are needed");
+    for (int p = 0; p < np; p++)
+        if (!std::isfinite(cfg->lo[p]) || !std::isfinite(cfg->hi[p]) || !(cfg->lo[p] < cfg->hi[p]) ||
+            !std::isfinite(cfg->hi[p] - cfg->lo[p]))
+            return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: parameter %d: range [%g, %g] invalid", p, cfg->lo[p],
+                        cfg->hi[p]);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // columns begun before may still be filling
+    peaks_free(s);
+    s->pk.n_keep = cfg->n_keep;
+    s->pk.capacity = cfg->capacity;
+    s->pk.n = 0;
+    HIP_TRY(hipMalloc((void **)&s->pk.d_chains, cfg->n_keep * sizeof(int)));
+    HIP_TRY(hipMalloc((void **)&s->pk.d_lo, np * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pk.d_hi, np * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pk.d_cols, (size_t)cfg->n_keep * np * cfg->capacity * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(s->pk.d_chains, cfg->chains, cfg->n_keep * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->pk.d_lo, cfg->lo, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->pk.d_hi, cfg->hi, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->pk.open = true;
+    return APEMOST_HIP_OK;
+}
+
+// Queued on copy_stream behind everything launched so far on the sampler's stream, like
+// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
+extern "C" int apemost_hip_peaks_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                            uint64_t skip, uint64_t thin) {
+    CHECK_S(s);
+    if (!s->pk.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_accumulate: no peaks_begin");
+    if (thin < 1 || (!d_samples && n_steps > 0))
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_accumulate: bad arguments");
+    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    if (kept > s->pk.capacity - s->pk.n)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_accumulate: %llu samples stored, %llu more are beyond capacity = %llu",
+                    (unsigned long long)s->pk.n, (unsigned long long)kept, (unsigned long long)s->pk.capacity);
+    if (kept == 0)
+        return APEMOST_HIP_OK;
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    PeaksAppendArgs a;
+    a.rows = d_samples;
+    a.n_chains = s->cfg.n_chains;
+    a.n_par = s->cfg.n_par;
+    a.n_keep = s->pk.n_keep;
+    a.chains = s->pk.d_chains;
+    a.skip = skip;
+    a.thin = thin;
+    a.n_kept = kept;
+    a.cols = s->pk.d_cols;
+    a.capacity = s->pk.capacity;
+    a.n = s->pk.n;
+    const dim3 grid((unsigned)((kept + kPeaksThreads - 1) / kPeaksThreads), (unsigned)(s->pk.n_keep * s->cfg.n_par));
+    hipLaunchKernelGGL(peaks_append_kernel, grid, dim3(kPeaksThreads), 0, s->copy_stream, a);
+    HIP_TRY(hipGetLastError());
+    s->pk.n += kept;
+    return APEMOST_HIP_OK;
+}
+
+namespace {
+struct PeaksScratch { // freed on every way out of peaks_get (hipFree waits for the kernels that use it)
+    void *p = nullptr;
+    ~PeaksScratch() {
+        if (p)
+            hipFree(p);
+    }
+};
+} // namespace
+
+extern "C" int apemost_hip_peaks_get(apemost_hip_sampler *s, const apemost_hip_peaks_view *v) {
+    CHECK_S(s);
+    if (!s->pk.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_get: no peaks_begin");
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks view is NULL");
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const int np = s->cfg.n_par, n_cols = s->pk.n_keep * np;
+    const u64 n = s->pk.n;
+    u64 padded = kPeaksTile;
+    while (padded < n)
+        padded <<= 1;
+    const u64 n_segments = n > 0 ? (n + kPeaksSegment - 1) / kPeaksSegment : 1;
+    // the scratch: keys, segment counts and offsets, and the results, each 256-byte aligned
+    size_t at = 0;
+    auto region = [&at](size_t bytes) {
+        const size_t here = at;
+        at = (at + bytes + 255) & ~(size_t)255;
+        return here;
+    };
+    const size_t at_keys = region((size_t)n_cols * padded * sizeof(u64));
+    const size_t at_count = region((size_t)n_cols * n_segments * sizeof(unsigned int));
+    const size_t at_off = region((size_t)n_cols * n_segments * sizeof(u64));
+    const size_t at_values = region((size_t)n_cols * sizeof(u64));
+    const size_t at_peaks = region((size_t)n_cols * sizeof(unsigned int));
+    const size_t at_cuts = region((size_t)n_cols * kPeaksMax * sizeof(u64));
+    const size_t at_left = region((size_t)n_cols * kPeaksMax * sizeof(u64));
+    const size_t at_right = region((size_t)n_cols * kPeaksMax * sizeof(u64));
+    const size_t at_q = region((size_t)n_cols * kPeaksMax * 3 * sizeof(double));
+    const size_t at_set = region((size_t)n_cols * kPeaksMax);
+    PeaksScratch scratch;
+    HIP_TRY(hipMalloc(&scratch.p, at));
+    char *base = (char *)scratch.p;
+    PeaksArgs a;
+    a.cols = s->pk.d_cols;
+    a.capacity = s->pk.capacity;
+    a.n = n;
+    a.padded = padded;
+    a.n_par = np;
+    a.lo = s->pk.d_lo;
+    a.hi = s->pk.d_hi;
+    a.keys = (unsigned long long *)(base + at_keys);
+    a.n_segments = n_segments;
+    a.seg_count = (unsigned int *)(base + at_count);
+    a.seg_off = (unsigned long long *)(base + at_off);
+    a.n_values = (unsigned long long *)(base + at_values);
+    a.n_peaks = (unsigned int *)(base + at_peaks);
+    a.cuts = (unsigned long long *)(base + at_cuts);
+    a.left = (unsigned long long *)(base + at_left);
+    a.right = (unsigned long long *)(base + at_right);
+    a.q = (double *)(base + at_q);
+    a.q_set = (unsigned char *)(base + at_set);
+    // stream order: behind every accumulate queued so far, on the stream they run on
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    hipStream_t st = s->copy_stream;
+    // (peaks beyond those a column has leave their slots 0)
+    HIP_TRY(hipMemsetAsync(base + at_cuts, 0, at - at_cuts, st));
+    const dim3 threads(kPeaksThreads);
+    hipLaunchKernelGGL(peaks_keys_kernel, dim3((unsigned)(padded / kPeaksThreads), n_cols), threads, 0, st, a);
+    const dim3 tiles((unsigned)(padded / kPeaksTile), n_cols), pairs((unsigned)(padded / 2 / kPeaksThreads), n_cols);
+    hipLaunchKernelGGL(peaks_sort_tile_kernel, tiles, threads, 0, st, a.keys, (unsigned long long)padded, 2ull,
+                       (unsigned long long)kPeaksTile);
+    for (u64 k = 2 * (u64)kPeaksTile; k <= padded; k <<= 1) {
+        for (u64 j = k / 2; j >= (u64)kPeaksTile; j >>= 1)
+            hipLaunchKernelGGL(peaks_sort_global_kernel, pairs, threads, 0, st, a.keys, (unsigned long long)padded,
+                               (unsigned long long)k, (unsigned long long)j);
+        hipLaunchKernelGGL(peaks_sort_tile_kernel, tiles, threads, 0, st, a.keys, (unsigned long long)padded,
+                           (unsigned long long)k, (unsigned long long)k);
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(peaks_nvalues_kernel, dim3((n_cols + kPeaksThreads - 1) / kPeaksThreads), threads, 0, st, a, n_cols);
+    hipLaunchKernelGGL(peaks_cut_count_kernel, dim3((unsigned)n_segments, n_cols), threads, 0, st, a);
+    hipLaunchKernelGGL(peaks_cut_scan_kernel, dim3(n_cols), threads, 0, st, a);
+    hipLaunchKernelGGL(peaks_cut_write_kernel, dim3((unsigned)((n_segments + kPeaksThreads - 1) / kPeaksThreads), n_cols),
+                       threads, 0, st, a);
+    hipLaunchKernelGGL(peaks_select_kernel, dim3(n_cols), dim3(128), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    std::vector<u64> h_values(n_cols), h_left((size_t)n_cols * kPeaksMax), h_right((size_t)n_cols * kPeaksMax);
+    std::vector<unsigned int> h_peaks(n_cols);
+    std::vector<double> h_q((size_t)n_cols * kPeaksMax * 3);
+    std::vector<unsigned char> h_set((size_t)n_cols * kPeaksMax);
+    HIP_TRY(hipMemcpyAsync(h_values.data(), a.n_values, h_values.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_peaks.data(), a.n_peaks, h_peaks.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_left.data(), a.left, h_left.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_right.data(), a.right, h_right.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_q.data(), a.q, h_q.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_set.data(), a.q_set, h_set.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (v->n)
+        *v->n = n;
+    if (v->n_values)
+        memcpy(v->n_values, h_values.data(), h_values.size() * sizeof(u64));
+    if (v->n_peaks)
+        memcpy(v->n_peaks, h_peaks.data(), h_peaks.size() * sizeof(unsigned int));
+    if (v->left)
+        memcpy(v->left, h_left.data(), h_left.size() * sizeof(u64));
+    if (v->right)
+        memcpy(v->right, h_right.data(), h_right.size() * sizeof(u64));
+    if (v->q)
+        memcpy(v->q, h_q.data(), h_q.size() * sizeof(double));
+    if (v->q_set)
+        memcpy(v->q_set, h_set.data(), h_set.size());
+    for (int col = 0; col < n_cols; col++)
+        if (h_peaks[col] > (unsigned int)kPeaksMax)
+            return fail(APEMOST_HIP_ERR_INVALID, "peaks_get: kept chain %d, parameter %d: %u peaks, more than %d "
+                        "(the reference asserts npeaks < 100)", col / np, col % np, h_peaks[col], kPeaksMax);
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_peaks_end(apemost_hip_sampler *s) {
+    CHECK_S(s);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    peaks_free(s);
+    return APEMOST_HIP_OK;
+}
+
+// Host arithmetic only (no device): tools/peaks.c:130, 177-200 and the selection sort of src/gsl_helper.c:102-127.
+extern "C" int apemost_hip_peaks_table(const apemost_hip_peaks_view *v, int32_t n_par, int32_t k, int32_t p,
+                                       double *table, uint32_t *n_rows) {
+    if (!v || !v->n_values || !v->n_peaks || !v->left || !v->right || !v->q || !v->q_set || !table || !n_rows)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_table: the view's n_values, n_peaks, left, right, q and q_set, "
+                    "table and n_rows are all needed");
+    if (n_par < 1 || k < 0 || p < 0 || p >= n_par)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_table: bad column (%d, %d) of %d parameters", k, p, n_par);
+    const size_t col = (size_t)k * n_par + p;
+    const uint32_t np = v->n_peaks[col];
+    if (np > (uint32_t)kPeaksMax)
+        return fail(APEMOST_HIP_ERR_INVALID, "peaks_table: kept chain %d, parameter %d: %u peaks, more than %d", k, p, np,
+                    kPeaksMax);
+    // a statistic whose index count is 0 keeps the value it had after the peak before (0 at the start)
+    double stat[3] = {0, 0, 0}; // left quartile, median, right quartile
+    double raw[kPeaksMax][4];   // share, median, left quartile, right quartile: the tool's four vectors
+    for (uint32_t c = 0; c < np; c++) {
+        const size_t at = col * kPeaksMax + c;
+        for (int j = 0; j < 3; j++)
+            if (v->q_set[at] >> j & 1)
+                stat[j] = v->q[at * 3 + j];
+        raw[c][0] = 1.0 * (double)(v->right[at] - v->left[at] + 1) / (double)v->n_values[col];
+        raw[c][1] = stat[1];
+        raw[c][2] = stat[0];
+        raw[c][3] = stat[2];
+    }
+    for (uint32_t j = 0; j < np; j++) { // descending by share, strict >: rows j and best change places
+        uint32_t best = j;
+        for (uint32_t i = j + 1; i < np; i++)
+            if (raw[i][0] > raw[best][0])
+                best = i;
+        if (j != best)
+            for (int f = 0; f < 4; f++)
+                std::swap(raw[j][f], raw[best][f]);
+    }
+    for (uint32_t c = 0; c < np; c++) {
+        table[c * 4 + 0] = raw[c][1];
+        table[c * 4 + 1] = raw[c][1] - raw[c][2];
+        table[c * 4 + 2] = raw[c][3] - raw[c][1];
+        table[c * 4 + 3] = raw[c][0];
+    }
+    *n_rows = np;
     return APEMOST_HIP_OK;
 }
 

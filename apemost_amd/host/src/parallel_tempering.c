@@ -12,6 +12,7 @@
 #include "parallel_tempering_config.h"
 #include "parallel_tempering_run.h"
 #include "apemost_bridge.h"
+#include "run_peaks.h"
 #include "run_summary.h"
 #include "debug.h"
 #include "define_defaults.h"
@@ -203,6 +204,9 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *   summary  fold the kept rows on the device into summary.bin (run_summary.h): what `analyse` prints,
  *            without the sample files.  On its own (summary, summary,thin:N) no sample file is written;
  *            with text or binary[:all] those are written as well
+ *   peaks    keep chain 0's parameter columns on the device and write one <paramname>.peaks per parameter at the
+ *            end: the output of the reference's `peaks.exe min max <name>-chain-0.prob.dump` over the prior box
+ *            (run_peaks.h).  Combines with every other token and writes no sample file by itself, like summary
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -217,7 +221,8 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
 typedef struct {
     int binary;               /* 0 text, 1 binary, 2 binary with every chain's parameters */
     int summary;              /* summary.bin from the device (APEMOST_DUMP token `summary`) */
-    int files;                /* sample files are written (not so for `summary` alone) */
+    int peaks;                /* <paramname>.peaks from the device (APEMOST_DUMP token `peaks`) */
+    int files;                /* sample files are written (not so for `summary` and `peaks` alone) */
     unsigned int n_param_chains; /* chains 0..n-1 have parameter files (text) / carry their parameter vectors (binary) */
     double *pack;             /* binary: one batch, packed */
     size_t pack_capacity;
@@ -235,6 +240,7 @@ static void sink_parse(sample_sink *k) {
     k->binary = 0;
     k->thin = 1;
     k->summary = 0;
+    k->peaks = 0;
     while (spec != NULL && *spec != 0) {
         if (strncmp(spec, "binary:all", 10) == 0)
             k->binary = 2, format_given = 1;
@@ -246,15 +252,17 @@ static void sink_parse(sample_sink *k) {
             k->thin = (unsigned long)atol(spec + 5);
         else if (strncmp(spec, "summary", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
             k->summary = 1;
+        else if (strncmp(spec, "peaks", 5) == 0 && (spec[5] == 0 || spec[5] == ','))
+            k->peaks = 1;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks; got '%s'\n", spec);
             exit(1);
         }
         spec = strchr(spec, ',');
         if (spec != NULL)
             spec++;
     }
-    k->files = !k->summary || format_given;
+    k->files = !(k->summary || k->peaks) || format_given;
 #ifdef HISTOGRAMS_MINMAX
     if (k->summary) {
         fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
@@ -434,25 +442,31 @@ static void sink_close(sample_sink *k) {
     }
 }
 
+/* the kept samples a bounded run will produce from iteration `iter` on; an unbounded run ends the program */
+static uint64_t planned_samples(const char *token, const char *why, unsigned int n_swap, unsigned long iter,
+                                unsigned long max_iterations, unsigned long thin) {
+    unsigned long end = iter;
+    if (max_iterations == 0) {
+        fprintf(stderr, "APEMOST_DUMP=%s needs a bounded run (MAX_ITERATIONS > 0): %s\n", token, why);
+        exit(1);
+    }
+    if (end < max_iterations) /* whole rounds: the last one may run past max_iterations */
+        end += (max_iterations - iter + n_swap - 1) / n_swap * n_swap;
+    return end / thin - iter / thin; /* iterations thin, 2 thin, ... are kept */
+}
+
 /* APEMOST_DUMP=summary: one device summary per shard (chain 0's histograms on shard 0).  The batch size
  * of the error estimate is floor(sqrt(samples planned)); --append loads summary.bin and keeps its own. */
 static void summary_open(run_summary *r, apemost_ladder *l, mcmc **chains, const unsigned int *lo,
                          unsigned int n_shards, unsigned int n_swap, unsigned long iter, unsigned long max_iterations,
                          unsigned long thin, const char *mode) {
     const unsigned int n_beta = lo[n_shards], n_par = get_n_par(chains[0]);
-    unsigned long end = iter;
     uint64_t planned, b;
     run_summary old;
     int resumed = 0;
     unsigned int j, p;
-    if (max_iterations == 0) {
-        fprintf(stderr, "APEMOST_DUMP=summary needs a bounded run (MAX_ITERATIONS > 0): the batch size of the "
-                        "error estimate is fixed before the first sample\n");
-        exit(1);
-    }
-    if (end < max_iterations) /* whole rounds: the last one may run past max_iterations */
-        end += (max_iterations - iter + n_swap - 1) / n_swap * n_swap;
-    planned = end / thin - iter / thin; /* iterations thin, 2 thin, ... are kept */
+    planned = planned_samples("summary", "the batch size of the error estimate is fixed before the first sample", n_swap,
+                              iter, max_iterations, thin);
     memset(&old, 0, sizeof old);
     if (mode[0] == 'a' && run_summary_read(RUN_SUMMARY_FILE, &old) == 0) {
         if (old.n_beta != n_beta || old.n_par != n_par || old.nbins != NBINS || old.thin != thin || old.n_hist != 1) {
@@ -622,6 +636,11 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     memset(&summary, 0, sizeof summary);
     if (sink.summary)
         summary_open(&summary, l, chains, lo, n_shards, n_swap, iter, max_iterations, sink.thin, mode);
+    if (sink.peaks) /* chain 0 lives on shard 0 */
+        run_peaks_open(apemost_ladder_shard(l, 0), chains[0],
+                       planned_samples("peaks", "the columns kept on the device are sized before the first sample", n_swap,
+                                       iter, max_iterations, sink.thin),
+                       mode[0] == 'a');
     for (i = 0; i < 2 && device_pack; i++)
         apemost_hip_or_die(apemost_hip_samples_alloc(apemost_ladder_shard(l, 0), max_rounds * n_swap, &d_packed[i]),
                            "samples_alloc");
@@ -672,6 +691,10 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             apemost_hip_or_die(apemost_hip_summary_accumulate(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
                                                               (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
                                "summary_accumulate");
+        if (sink.peaks) /* chain 0's columns grow on the same stream */
+            apemost_hip_or_die(apemost_hip_peaks_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
+                                                            (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
+                               "peaks_accumulate");
         /* no rows on the host (the text sink, or no sample files): only the counters and chain 0's latest point
          * cross (a packed read that keeps no step) */
         for (j = 0; j < n_shards && !device_pack && !rows_on_host; j++)
@@ -731,6 +754,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
 #endif
     if (sink.summary)
         summary_close(&summary, l, lo, n_shards);
+    if (sink.peaks)
+        run_peaks_close(apemost_ladder_shard(l, 0), chains[0]);
     for (i = 0; i < 2; i++)
         for (j = 0; j < n_shards; j++) {
             apemost_hip_samples_free(apemost_ladder_shard(l, j), d_samples[i][j]);

@@ -378,6 +378,36 @@ class HipSampler:
     def summary_end(self):
         capi.check(self.L.apemost_hip_summary_end(self._h))
 
+    # -- on-device peaks (apemost_amd/peaks.py) -------------------------------------------------
+    def peaks_begin(self, lo, hi, chains=(0,), capacity=1 << 20):
+        """keep the parameter columns of the local chains `chains` (strictly increasing; b * chains_per_ladder is
+        ladder b's chain 0) on the device, up to `capacity` kept samples each, for the peaks of the reference's
+        peaks.exe over [lo[p], hi[p]]"""
+        self._pk_lo = np.ascontiguousarray(lo, dtype=np.float64)
+        self._pk_hi = np.ascontiguousarray(hi, dtype=np.float64)
+        self._pk_chains = np.ascontiguousarray(chains, dtype=np.int32)
+        assert self._pk_lo.shape == (self.n_par,) and self._pk_hi.shape == (self.n_par,) and self._pk_chains.ndim == 1
+        dp = C.POINTER(C.c_double)
+        cfg = capi.PeaksConfig(n_keep=len(self._pk_chains), chains=self._pk_chains.ctypes.data_as(C.POINTER(C.c_int32)),
+                               capacity=capacity, lo=self._pk_lo.ctypes.data_as(dp), hi=self._pk_hi.ctypes.data_as(dp))
+        capi.check(self.L.apemost_hip_peaks_begin(self._h, C.byref(cfg)))
+
+    def peaks_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """append the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2] to the
+        columns; asynchronous (peaks() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_peaks_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def peaks(self):
+        """the peaks of the columns stored so far as a Peaks object (sorts on the device; synchronises with the
+        accumulates issued so far).  A column with 100 peaks or more raises ApemostHipError, as the tool aborts."""
+        from .peaks import Peaks
+        pk = Peaks.empty(len(self._pk_chains), self.n_par, self._pk_lo, self._pk_hi, self._pk_chains)
+        capi.check(self.L.apemost_hip_peaks_get(self._h, C.byref(pk.view())))
+        return pk
+
+    def peaks_end(self):
+        capi.check(self.L.apemost_hip_peaks_end(self._h))
+
     # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------
     def samples_text_bound(self, n_steps, skip=0, thin=1, n_param_chains=1):
         """(streams, host text bytes, device scratch bytes) of one samples_text batch"""

@@ -34,6 +34,7 @@ using __hip_internal::int32_t;
 using __hip_internal::int64_t;
 using __hip_internal::uint32_t;
 using __hip_internal::uint64_t;
+using __hip_internal::uint8_t;
 #endif
 
 #ifdef __cplusplus
@@ -582,6 +583,71 @@ int apemost_hip_summary_get(apemost_hip_sampler *s, const apemost_hip_summary_vi
 int apemost_hip_summary_set(apemost_hip_sampler *s, const apemost_hip_summary_view *v);
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_summary_end(apemost_hip_sampler *s);
+
+/* ---- on-device peaks: exact medians and quartiles per mode, without dumps ---------------------
+ * What the reference's peaks.exe (tools/peaks.c; the manual prefers it to reading the marginal histograms: "it is
+ * exact") computes from the text dump of one chain's parameter, from columns that stay on the device: 8 bytes per
+ * kept step, kept chain and parameter.  For `peaks.exe min max file`, column (k, p) being the file and
+ * [lo[p], hi[p]] being [min, max]:
+ *   1. filter   the values with v >= lo && v <= hi are kept, both ends inclusive; NaN is dropped (:101).  n_values
+ *               of them.
+ *   2. sort     ascending as numbers (:147).  The device sorts the keys bits ^ (bits >> 63 ? ~0 : 1 << 63), which
+ *               order like the doubles; -0.0 comes before +0.0, one of the orders the tool's qsort may leave.
+ *   3. cut      gap = (hi - lo) / 100; a new peak starts at sorted index i > 0 when v[i] - v[i-1] > gap, strictly,
+ *               in fp64 as written (:151, :161-188).  n_peaks counts them all; the first 99 are described (the tool
+ *               asserts npeaks < 100).  With n_values == 0 there is no peak (the tool reads uninitialised memory).
+ *   4. select   peak c covers the sorted indices left[c] .. right[c], n = right - left + 1 values.  q[c][j], j = 0,
+ *               1, 2, is v[left + n*(j+1)/4 - 1] (integer division): the left quartile, the median, the right
+ *               quartile (:56-80).  Bit j of q_set[c] says that the index count n*(j+1)/4 is at least 1; where it is
+ *               0 the statistic does not exist and q[c][j] is 0.
+ * Peaks come in ascending order of position.  Slots of peaks that a column does not have are 0.
+ * apemost_hip_peaks_table turns one column into the tool's printed table.
+ * Sharded ladders: the caller begins peaks on the shard that holds the chain, as for n_hist_chains.  Ladder batches:
+ * `chains` indexes the grid's local chains, ladder-major: b * n_chains is ladder b's chain 0. */
+typedef struct {
+    int32_t n_keep;          /* number of kept chains, 1 .. n_chains; n_keep * n_par <= 65535 */
+    const int32_t *chains;   /* host [n_keep]: local chain indices, strictly increasing */
+    uint64_t capacity;       /* kept samples per column, 1 .. 2^30 */
+    const double *lo, *hi;   /* host [n_par]: peaks.exe's min and max per parameter, finite, lo < hi */
+} apemost_hip_peaks_config;
+typedef struct {
+    uint64_t *n;             /* samples stored per column */
+    uint64_t *n_values;      /* [n_keep][n_par] admitted by the filter */
+    uint32_t *n_peaks;       /* [n_keep][n_par] peaks found (may exceed 99) */
+    uint64_t *left, *right;  /* [n_keep][n_par][99] sorted-index bounds of each peak, in ascending order of position */
+    double *q;               /* [n_keep][n_par][99][3] v[left+n/4-1], v[left+n*2/4-1], v[left+n*3/4-1] */
+    uint8_t *q_set;          /* [n_keep][n_par][99] bit j: q[..][j] exists (its index count >= 1) */
+} apemost_hip_peaks_view;    /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates cols[n_keep][n_par][capacity] on the device (columns begun before are dropped).  APEMOST_HIP_ERR_INVALID,
+ * before any device work, for a NULL config, n_keep or a chain index out of range, chains not strictly increasing, a
+ * capacity outside [1, 2^30], or a range that is not finite with lo < hi. */
+int apemost_hip_peaks_begin(apemost_hip_sampler *s, const apemost_hip_peaks_config *cfg);
+/* appends the parameter values of the kept chains at the kept steps skip, skip + thin, ... of d_samples (DEVICE
+ * [n_steps][n_chains][n_par+2], the rows of the launches issued so far) to the columns.  Asynchronous and queued
+ * like apemost_hip_summary_accumulate: the round kernels never wait for it, and apemost_hip_samples_wait (or
+ * peaks_get) must have returned before d_samples is written again.  A call that would store more than `capacity`
+ * samples is APEMOST_HIP_ERR_INVALID and stores nothing. */
+int apemost_hip_peaks_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                 uint64_t thin);
+/* steps 1 to 4 on the device for every column, in scratch memory of 8 bytes per column and stored sample rounded up
+ * to a power of two (at least 4096), and the view filled (synchronises with the accumulates issued so far).  The
+ * stored columns are only read: accumulates may go on, and a later get describes the longer columns.  When a column
+ * has 100 peaks or more the view is still filled -- n_peaks with the true count, the rest for the first 99 peaks
+ * -- and the call returns APEMOST_HIP_ERR_INVALID with a message that names (k, p): the reference aborts there. */
+int apemost_hip_peaks_get(apemost_hip_sampler *s, const apemost_hip_peaks_view *v);
+/* frees the columns (apemost_hip_destroy does too) */
+int apemost_hip_peaks_end(apemost_hip_sampler *s);
+/* Host arithmetic only, no device and no sampler: column (k, p) of a view of n_par parameters (n_values, n_peaks,
+ * left, right, q and q_set all given) as the table peaks.exe prints.  In position order each statistic that does
+ * not exist keeps the value it had after the peak before, 0 at the start (the tool's three variables live outside
+ * its loop, :130); share = 1.0 * n / n_values; the rows are put in descending order of share by the selection
+ * sort of src/gsl_helper.c:102-127 (strict >, rows j and best change places, so equal shares keep the order that
+ * leaves).  table receives n_peaks rows of four doubles -- median, median - left quartile, right quartile - median,
+ * share -- and must hold 99; *n_rows = n_peaks.  The tool prints "median\t-\t+\tpercent\n", then "%f\t%f\t%f\t%f\n"
+ * per row.  APEMOST_HIP_ERR_INVALID for a column with 100 peaks or more. */
+int apemost_hip_peaks_table(const apemost_hip_peaks_view *v, int32_t n_par, int32_t k, int32_t p, double *table,
+                            uint32_t *n_rows);
 
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
