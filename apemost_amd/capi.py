@@ -75,6 +75,15 @@ class PeaksView(C.Structure):
                 ("q", _dp), ("q_set", C.POINTER(C.c_uint8))]
 
 
+class JointConfig(C.Structure):
+    _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("nbins", C.c_int32), ("n_pairs", C.c_int32),
+                ("pairs", C.POINTER(C.c_int32)), ("lo", _dp), ("hi", _dp)]
+
+
+class JointView(C.Structure):
+    _fields_ = [("n", _up), ("counts", _up), ("origin", _dp), ("sum", _dp), ("cross", _dp)]
+
+
 PEAKS_MAX = 99   # peaks described per column (include/apemost_hip.h)
 
 
@@ -108,6 +117,8 @@ EXPORTS = [
     "apemost_hip_replica_flow_get", "apemost_hip_replica_flow_set", "apemost_hip_replica_flow_reset",
     "apemost_hip_peaks_begin", "apemost_hip_peaks_accumulate", "apemost_hip_peaks_get", "apemost_hip_peaks_end",
     "apemost_hip_peaks_table",
+    "apemost_hip_joint_begin", "apemost_hip_joint_accumulate", "apemost_hip_joint_get", "apemost_hip_joint_set",
+    "apemost_hip_joint_end",
 ]
 
 _lib = None
@@ -219,6 +230,11 @@ def lib():
     L.apemost_hip_peaks_end.argtypes = [vp]
     L.apemost_hip_peaks_table.argtypes = [C.POINTER(PeaksView), C.c_int32, C.c_int32, C.c_int32, _dp,
                                           C.POINTER(C.c_uint32)]
+    L.apemost_hip_joint_begin.argtypes = [vp, C.POINTER(JointConfig)]
+    L.apemost_hip_joint_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_joint_get.argtypes = [vp, C.POINTER(JointView)]
+    L.apemost_hip_joint_set.argtypes = [vp, C.POINTER(JointView)]
+    L.apemost_hip_joint_end.argtypes = [vp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

@@ -1,5 +1,6 @@
 // apemost_hip.hip -- kernels and C ABI of the gfx950 parallel-tempering engine
 // (declared in include/apemost_hip.h).  Written for MI355X only.
+#include "pt_joint.h"
 #include "pt_kernels.h"
 #include "pt_peaks.h"
 #include "pt_summary.h"
@@ -357,6 +358,17 @@ struct apemost_hip_sampler {
         int *d_chains;
         double *d_lo, *d_hi, *d_cols;
     } pk;
+    // on-device joint marginals (apemost_hip_joint_begin .. end): pair histograms and moments, on copy_stream
+    struct {
+        bool open;
+        int n_keep, nbins, n_pairs;
+        u64 chunk; // kept steps staged per launch
+        u64 n;     // kept samples so far (the host knows it without a sync)
+        int *d_chains, *d_pairs;
+        double *d_lo, *d_hi, *d_vals, *d_origin, *d_sum, *d_cross;
+        unsigned short *d_bins;
+        u64 *d_counts;
+    } jt;
 };
 
 extern "C" const char *apemost_hip_last_error(void) { return g_last_error.c_str(); }
@@ -476,6 +488,15 @@ static void peaks_free(apemost_hip_sampler *s) {
     s->pk = {};
 }
 
+static void joint_free(apemost_hip_sampler *s) {
+    for (void *p : {(void *)s->jt.d_chains, (void *)s->jt.d_pairs, (void *)s->jt.d_lo, (void *)s->jt.d_hi,
+                    (void *)s->jt.d_vals, (void *)s->jt.d_origin, (void *)s->jt.d_sum, (void *)s->jt.d_cross,
+                    (void *)s->jt.d_bins, (void *)s->jt.d_counts})
+        if (p)
+            hipFree(p);
+    s->jt = {};
+}
+
 // everything a sampler owns on the device; safe on a half-built sampler
 static void release(apemost_hip_sampler *s) {
     if (s->stream)
@@ -504,6 +525,7 @@ static void release(apemost_hip_sampler *s) {
     }
     summary_free(s); // (its kernels ran on copy_stream)
     peaks_free(s);
+    joint_free(s);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {
@@ -2253,6 +2275,207 @@ extern "C" int apemost_hip_peaks_end(apemost_hip_sampler *s) {
     if (s->copy_stream)
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     peaks_free(s);
+    return APEMOST_HIP_OK;
+}
+
+// ---- on-device joint marginals (pt_joint.h) ----
+extern "C" int apemost_hip_joint_begin(apemost_hip_sampler *s, const apemost_hip_joint_config *cfg) {
+    CHECK_S(s);
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: config is NULL");
+    const int np = s->cfg.n_par;
+    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
+                    s->cfg.n_chains);
+    if ((long long)cfg->n_keep * np > 65535)
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: %d chains of %d parameters are more than 65535 columns",
+                    cfg->n_keep, np);
+    for (int k = 0; k < cfg->n_keep; k++)
+        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
+            return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing",
+                        k, cfg->chains[k], s->cfg.n_chains);
+    if (cfg->nbins < 1 || cfg->nbins > kJointMaxBins)
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: nbins %d outside [1,%d]", cfg->nbins, kJointMaxBins);
+    std::vector<int> pairs;
+    if (!cfg->pairs) { // all i < j in lexicographic order
+        for (int i = 0; i < np; i++)
+            for (int j = i + 1; j < np; j++) {
+                pairs.push_back(i);
+                pairs.push_back(j);
+            }
+    } else {
+        const long long all = (long long)np * (np - 1) / 2;
+        if (cfg->n_pairs < 0 || cfg->n_pairs > all)
+            return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: n_pairs %d outside [0,%lld]", cfg->n_pairs, all);
+        std::vector<char> seen((size_t)np * np, 0);
+        for (int q = 0; q < cfg->n_pairs; q++) {
+            const int i = cfg->pairs[2 * q], j = cfg->pairs[2 * q + 1];
+            if (i < 0 || j >= np || i >= j || seen[(size_t)i * np + j])
+                return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: pairs[%d] = (%d, %d): 0 <= i < j < %d, no duplicates", q, i,
+                            j, np);
+            seen[(size_t)i * np + j] = 1;
+            pairs.push_back(i);
+            pairs.push_back(j);
+        }
+    }
+    const int n_pairs = (int)(pairs.size() / 2);
+    if (!cfg->lo || !cfg->hi)
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: lo and hi are needed");
+    for (int p = 0; p < np; p++)
+        if (!std::isfinite(cfg->lo[p]) || !std::isfinite(cfg->hi[p]) || !(cfg->lo[p] < cfg->hi[p]) ||
+            !std::isfinite(cfg->hi[p] - cfg->lo[p]))
+            return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: parameter %d: range [%g, %g] invalid", p, cfg->lo[p],
+                        cfg->hi[p]);
+    const u64 n_counts = (u64)cfg->n_keep * n_pairs * cfg->nbins * cfg->nbins; // (< 2^16 2^16 2^18: no overflow)
+    if (n_pairs > 65535 || n_counts * sizeof(u64) > ((u64)1 << 30))
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: %d chains x %d pairs x %d^2 bins: counts above 2^30 bytes",
+                    cfg->n_keep, n_pairs, cfg->nbins);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a joint begun before may still be accumulating
+    joint_free(s);
+    const size_t n_cols = (size_t)cfg->n_keep * np, tri = (size_t)np * (np + 1) / 2;
+    // the staged columns: about 4 Mi values over all of them, at least 256 and at most 2^18 kept steps per launch
+    // (the LDS counters are 32 bits wide)
+    u64 chunk = ((u64)1 << 22) / n_cols;
+    chunk = chunk < 256 ? 256 : chunk > ((u64)1 << 18) ? (u64)1 << 18 : chunk;
+    s->jt.n_keep = cfg->n_keep;
+    s->jt.nbins = cfg->nbins;
+    s->jt.n_pairs = n_pairs;
+    s->jt.chunk = chunk;
+    s->jt.n = 0;
+    HIP_TRY(hipMalloc((void **)&s->jt.d_chains, cfg->n_keep * sizeof(int)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_pairs, (n_pairs > 0 ? n_pairs : 1) * 2 * sizeof(int)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_lo, np * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_hi, np * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_vals, n_cols * chunk * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_bins, n_cols * chunk * sizeof(unsigned short)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_origin, n_cols * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_sum, n_cols * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_cross, cfg->n_keep * tri * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->jt.d_counts, (n_counts > 0 ? n_counts : 1) * sizeof(u64)));
+    HIP_TRY(hipMemsetAsync(s->jt.d_origin, 0, n_cols * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->jt.d_sum, 0, n_cols * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->jt.d_cross, 0, cfg->n_keep * tri * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->jt.d_counts, 0, (n_counts > 0 ? n_counts : 1) * sizeof(u64), s->stream));
+    HIP_TRY(hipMemcpyAsync(s->jt.d_chains, cfg->chains, cfg->n_keep * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    if (n_pairs > 0)
+        HIP_TRY(hipMemcpyAsync(s->jt.d_pairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->jt.d_lo, cfg->lo, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->jt.d_hi, cfg->hi, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream)); // (`pairs` and the caller's arrays are read until here)
+    s->jt.open = true;
+    return APEMOST_HIP_OK;
+}
+
+// Queued on copy_stream behind everything launched so far on the sampler's stream, like
+// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
+extern "C" int apemost_hip_joint_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                            uint64_t skip, uint64_t thin) {
+    CHECK_S(s);
+    if (!s->jt.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_accumulate: no joint_begin");
+    if (thin < 1 || (!d_samples && n_steps > 0))
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_accumulate: bad arguments");
+    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    if (kept == 0)
+        return APEMOST_HIP_OK;
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const int np = s->cfg.n_par, n_cols = s->jt.n_keep * np;
+    const int band_rows = joint_band_rows(s->jt.nbins), n_bands = (s->jt.nbins + band_rows - 1) / band_rows;
+    const int entries = s->jt.n_keep * (np + np * (np + 1) / 2);
+    for (u64 k0 = 0; k0 < kept; k0 += s->jt.chunk) {
+        JointArgs a;
+        a.rows = d_samples;
+        a.n_chains = s->cfg.n_chains;
+        a.n_par = np;
+        a.n_keep = s->jt.n_keep;
+        a.chains = s->jt.d_chains;
+        a.skip = skip + k0 * thin;
+        a.thin = thin;
+        a.n = (unsigned int)(kept - k0 < s->jt.chunk ? kept - k0 : s->jt.chunk);
+        a.chunk = s->jt.chunk;
+        a.nbins = s->jt.nbins;
+        a.n_pairs = s->jt.n_pairs;
+        a.pairs = s->jt.d_pairs;
+        a.lo = s->jt.d_lo;
+        a.hi = s->jt.d_hi;
+        a.vals = s->jt.d_vals;
+        a.bins = s->jt.d_bins;
+        a.first = s->jt.n == 0;
+        a.counts = s->jt.d_counts;
+        a.origin = s->jt.d_origin;
+        a.sum = s->jt.d_sum;
+        a.cross = s->jt.d_cross;
+        hipLaunchKernelGGL(joint_gather_kernel, dim3((a.n + kJointGatherPer - 1) / kJointGatherPer, (unsigned)n_cols),
+                           dim3(kJointThreads), 0, s->copy_stream, a);
+        HIP_TRY(hipGetLastError());
+        if (s->jt.n_pairs > 0) {
+            hipLaunchKernelGGL(joint_pair_kernel, dim3((unsigned)n_bands, (unsigned)s->jt.n_pairs, (unsigned)s->jt.n_keep),
+                               dim3(kJointThreads), 0, s->copy_stream, a);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(joint_moments_kernel, dim3((unsigned)((entries + kJointMomentThreads - 1) / kJointMomentThreads)),
+                           dim3(kJointMomentThreads), 0, s->copy_stream, a);
+        HIP_TRY(hipGetLastError());
+        s->jt.n += a.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+static int joint_xfer(apemost_hip_sampler *s, const apemost_hip_joint_view *v, bool up) {
+    if (!s->jt.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "joint_%s: no joint_begin", up ? "set" : "get");
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "joint view is NULL");
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const size_t np = s->cfg.n_par, n_cols = (size_t)s->jt.n_keep * np, tri = np * (np + 1) / 2;
+    const size_t n_counts = (size_t)s->jt.n_keep * s->jt.n_pairs * s->jt.nbins * s->jt.nbins;
+    // stream order: behind every accumulate queued so far, on the stream they run on
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+#define JOINT_COPY(dev, host, bytes)                                                                            \
+    do {                                                                                                       \
+        if ((host) && (bytes) > 0)                                                                             \
+            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
+                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
+    } while (0)
+    JOINT_COPY(s->jt.d_counts, v->counts, n_counts * sizeof(u64));
+    JOINT_COPY(s->jt.d_origin, v->origin, n_cols * sizeof(double));
+    JOINT_COPY(s->jt.d_sum, v->sum, n_cols * sizeof(double));
+    JOINT_COPY(s->jt.d_cross, v->cross, s->jt.n_keep * tri * sizeof(double));
+#undef JOINT_COPY
+    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    if (v->n) {
+        if (up)
+            s->jt.n = *v->n;
+        else
+            *v->n = s->jt.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_joint_get(apemost_hip_sampler *s, const apemost_hip_joint_view *v) {
+    CHECK_S(s);
+    return joint_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_joint_set(apemost_hip_sampler *s, const apemost_hip_joint_view *v) {
+    CHECK_S(s);
+    return joint_xfer(s, v, true);
+}
+
+extern "C" int apemost_hip_joint_end(apemost_hip_sampler *s) {
+    CHECK_S(s);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    joint_free(s);
     return APEMOST_HIP_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "parallel_tempering_config.h"
 #include "parallel_tempering_run.h"
 #include "apemost_bridge.h"
+#include "run_joint.h"
 #include "run_peaks.h"
 #include "run_summary.h"
 #include "debug.h"
@@ -207,6 +208,10 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *   peaks    keep chain 0's parameter columns on the device and write one <paramname>.peaks per parameter at the
  *            end: the output of the reference's `peaks.exe min max <name>-chain-0.prob.dump` over the prior box
  *            (run_peaks.h).  Combines with every other token and writes no sample file by itself, like summary
+ *   joint    fold chain 0's rows on the device into one NBINS x NBINS histogram per pair of parameters over the prior
+ *            box, on the bins of the marginal histograms, and into the moments of the parameter covariance; at the end
+ *            write joint.bin, one <a>-<b>.joint per pair and correlation.matrix (run_joint.h).  Combines with every
+ *            other token and writes no sample file by itself, like peaks
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -222,7 +227,8 @@ typedef struct {
     int binary;               /* 0 text, 1 binary, 2 binary with every chain's parameters */
     int summary;              /* summary.bin from the device (APEMOST_DUMP token `summary`) */
     int peaks;                /* <paramname>.peaks from the device (APEMOST_DUMP token `peaks`) */
-    int files;                /* sample files are written (not so for `summary` and `peaks` alone) */
+    int joint;                /* joint.bin and the pair files from the device (APEMOST_DUMP token `joint`) */
+    int files;                /* sample files are written (not so for `summary`, `peaks` and `joint` alone) */
     unsigned int n_param_chains; /* chains 0..n-1 have parameter files (text) / carry their parameter vectors (binary) */
     double *pack;             /* binary: one batch, packed */
     size_t pack_capacity;
@@ -241,6 +247,7 @@ static void sink_parse(sample_sink *k) {
     k->thin = 1;
     k->summary = 0;
     k->peaks = 0;
+    k->joint = 0;
     while (spec != NULL && *spec != 0) {
         if (strncmp(spec, "binary:all", 10) == 0)
             k->binary = 2, format_given = 1;
@@ -254,15 +261,17 @@ static void sink_parse(sample_sink *k) {
             k->summary = 1;
         else if (strncmp(spec, "peaks", 5) == 0 && (spec[5] == 0 || spec[5] == ','))
             k->peaks = 1;
+        else if (strncmp(spec, "joint", 5) == 0 && (spec[5] == 0 || spec[5] == ','))
+            k->joint = 1;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint; got '%s'\n", spec);
             exit(1);
         }
         spec = strchr(spec, ',');
         if (spec != NULL)
             spec++;
     }
-    k->files = !(k->summary || k->peaks) || format_given;
+    k->files = !(k->summary || k->peaks || k->joint) || format_given;
 #ifdef HISTOGRAMS_MINMAX
     if (k->summary) {
         fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
@@ -576,6 +585,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     unsigned int lo[APEMOST_MAX_SHARDS + 1], n_shards, i, j;
     int k = 0, device_pack, rows_on_host, text_sink;
     run_summary summary;
+    run_joint joint;
 
     if (max_rounds < 1)
         max_rounds = 1;
@@ -641,6 +651,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
                        planned_samples("peaks", "the columns kept on the device are sized before the first sample", n_swap,
                                        iter, max_iterations, sink.thin),
                        mode[0] == 'a');
+    if (sink.joint) /* chain 0 lives on shard 0 */
+        run_joint_open(&joint, apemost_ladder_shard(l, 0), chains[0], NBINS, sink.thin, mode[0] == 'a');
     for (i = 0; i < 2 && device_pack; i++)
         apemost_hip_or_die(apemost_hip_samples_alloc(apemost_ladder_shard(l, 0), max_rounds * n_swap, &d_packed[i]),
                            "samples_alloc");
@@ -695,6 +707,10 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             apemost_hip_or_die(apemost_hip_peaks_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
                                                             (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
                                "peaks_accumulate");
+        if (sink.joint) /* chain 0's pair histograms and moments, on the same stream */
+            apemost_hip_or_die(apemost_hip_joint_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
+                                                            (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
+                               "joint_accumulate");
         /* no rows on the host (the text sink, or no sample files): only the counters and chain 0's latest point
          * cross (a packed read that keeps no step) */
         for (j = 0; j < n_shards && !device_pack && !rows_on_host; j++)
@@ -756,6 +772,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         summary_close(&summary, l, lo, n_shards);
     if (sink.peaks)
         run_peaks_close(apemost_ladder_shard(l, 0), chains[0]);
+    if (sink.joint)
+        run_joint_close(&joint, apemost_ladder_shard(l, 0), chains[0]);
     for (i = 0; i < 2; i++)
         for (j = 0; j < n_shards; j++) {
             apemost_hip_samples_free(apemost_ladder_shard(l, j), d_samples[i][j]);

@@ -1,0 +1,315 @@
+/* joint.bin reader and writer and the text files of the APEMOST_DUMP token `joint` (run_joint.h) */
+#include "run_joint.h"
+
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "apemost_bridge.h"
+#include "mcmc_gettersetter.h"
+
+#define RUN_JOINT_MAGIC "APEMOSTJ"
+#define RUN_JOINT_VERSION 1
+
+static void *alloc_or_die(size_t count, size_t size) {
+    void *p = calloc(count > 0 ? count : 1, size);
+    if (p == NULL) {
+        fprintf(stderr, "joint marginals: out of memory\n");
+        exit(1);
+    }
+    return p;
+}
+
+static size_t tri_count(const run_joint *r) {
+    return (size_t)r->n_par * (r->n_par + 1) / 2;
+}
+
+static size_t tri_index(const run_joint *r, unsigned int i, unsigned int j) {
+    return (size_t)i * r->n_par - (size_t)i * (i > 0 ? i - 1 : 0) / 2 + (j - i);
+}
+
+static void joint_alloc(run_joint *r) {
+    r->pairs = (int32_t *)alloc_or_die((size_t)r->n_pairs * 2, sizeof(int32_t));
+    r->lo = (double *)alloc_or_die(r->n_par, sizeof(double));
+    r->hi = (double *)alloc_or_die(r->n_par, sizeof(double));
+    r->origin = (double *)alloc_or_die(r->n_par, sizeof(double));
+    r->sum = (double *)alloc_or_die(r->n_par, sizeof(double));
+    r->cross = (double *)alloc_or_die(tri_count(r), sizeof(double));
+    r->counts = (uint64_t *)alloc_or_die((size_t)r->n_pairs * r->nbins * r->nbins, sizeof(uint64_t));
+}
+
+static void joint_free(run_joint *r) {
+    free(r->pairs);
+    free(r->lo);
+    free(r->hi);
+    free(r->origin);
+    free(r->sum);
+    free(r->cross);
+    free(r->counts);
+    memset(r, 0, sizeof *r);
+}
+
+static void read_or_die(void *p, size_t size, size_t count, FILE *f, const char *path) {
+    if (count > 0 && fread(p, size, count, f) != count) {
+        fprintf(stderr, "%s: truncated joint file\n", path);
+        exit(1);
+    }
+}
+
+/* 0: read; -1: no such file.  *n_keep and *chain receive the kept chains and the first of them */
+static int joint_read(const char *path, run_joint *r, uint32_t *n_keep, int32_t *chain) {
+    FILE *f = fopen(path, "rb");
+    char magic[8];
+    uint32_t u32[6];
+    uint64_t u64[2];
+    if (f == NULL)
+        return -1;
+    read_or_die(magic, 1, 8, f, path);
+    read_or_die(u32, sizeof(uint32_t), 6, f, path);
+    if (memcmp(magic, RUN_JOINT_MAGIC, 8) != 0 || u32[0] != RUN_JOINT_VERSION) {
+        fprintf(stderr, "%s: not a joint file of version %d\n", path, RUN_JOINT_VERSION);
+        exit(1);
+    }
+    *n_keep = u32[1];
+    r->n_par = u32[2];
+    r->nbins = u32[3];
+    r->n_pairs = u32[4];
+    read_or_die(u64, sizeof(uint64_t), 2, f, path);
+    r->n = u64[0];
+    r->thin = u64[1];
+    *chain = -1;
+    if (*n_keep != 1 || r->nbins < 1 || r->nbins > 512 || r->n_par < 1 || r->n_par > 65535 ||
+        r->n_pairs > r->n_par * (r->n_par - 1) / 2) { /* (not this program's: the caller refuses it by its shape) */
+        fclose(f);
+        r->pairs = NULL;
+        r->lo = r->hi = r->origin = r->sum = r->cross = NULL;
+        r->counts = NULL;
+        return 0;
+    }
+    joint_alloc(r);
+    read_or_die(chain, sizeof(int32_t), 1, f, path);
+    read_or_die(r->pairs, sizeof(int32_t), (size_t)r->n_pairs * 2, f, path);
+    read_or_die(r->lo, sizeof(double), r->n_par, f, path);
+    read_or_die(r->hi, sizeof(double), r->n_par, f, path);
+    read_or_die(r->origin, sizeof(double), r->n_par, f, path);
+    read_or_die(r->sum, sizeof(double), r->n_par, f, path);
+    read_or_die(r->cross, sizeof(double), tri_count(r), f, path);
+    read_or_die(r->counts, sizeof(uint64_t), (size_t)r->n_pairs * r->nbins * r->nbins, f, path);
+    fclose(f);
+    return 0;
+}
+
+static FILE *open_or_die(const char *path, const char *mode) {
+    FILE *f = fopen(path, mode);
+    if (f == NULL) {
+        fprintf(stderr, "opening file %s failed\n", path);
+        perror("opening file failed");
+        exit(1);
+    }
+    return f;
+}
+
+static void close_or_die(FILE *f, const char *path) {
+    if (fclose(f) != 0) {
+        fprintf(stderr, "writing %s failed\n", path);
+        exit(1);
+    }
+}
+
+static void joint_write(const char *path, const run_joint *r) {
+    FILE *f = open_or_die(path, "wb");
+    uint32_t u32[6];
+    uint64_t u64[2];
+    const int32_t chain = 0;
+    u32[0] = RUN_JOINT_VERSION;
+    u32[1] = 1;
+    u32[2] = r->n_par;
+    u32[3] = r->nbins;
+    u32[4] = r->n_pairs;
+    u32[5] = 0;
+    u64[0] = r->n;
+    u64[1] = r->thin;
+    fwrite(RUN_JOINT_MAGIC, 1, 8, f);
+    fwrite(u32, sizeof(uint32_t), 6, f);
+    fwrite(u64, sizeof(uint64_t), 2, f);
+    fwrite(&chain, sizeof(int32_t), 1, f);
+    fwrite(r->pairs, sizeof(int32_t), (size_t)r->n_pairs * 2, f);
+    fwrite(r->lo, sizeof(double), r->n_par, f);
+    fwrite(r->hi, sizeof(double), r->n_par, f);
+    fwrite(r->origin, sizeof(double), r->n_par, f);
+    fwrite(r->sum, sizeof(double), r->n_par, f);
+    fwrite(r->cross, sizeof(double), tri_count(r), f);
+    fwrite(r->counts, sizeof(uint64_t), (size_t)r->n_pairs * r->nbins * r->nbins, f);
+    close_or_die(f, path);
+}
+
+static void joint_view(run_joint *r, apemost_hip_joint_view *v) {
+    v->n = &r->n;
+    v->counts = r->counts;
+    v->origin = r->origin;
+    v->sum = r->sum;
+    v->cross = r->cross;
+}
+
+void run_joint_open(run_joint *r, apemost_hip_sampler *s, const mcmc *chain0, unsigned int nbins, uint64_t thin,
+                    int append) {
+    const unsigned int n_par = get_n_par(chain0);
+    const int32_t chain = 0;
+    apemost_hip_joint_config c;
+    apemost_hip_joint_view v;
+    run_joint old;
+    uint32_t old_keep = 0;
+    int32_t old_chain = -1;
+    int resumed = 0;
+    unsigned int i, j, p, q = 0;
+    memset(&old, 0, sizeof old);
+    memset(r, 0, sizeof *r);
+    r->n_par = n_par;
+    r->nbins = nbins;
+    r->n_pairs = n_par * (n_par - 1) / 2;
+    r->thin = thin;
+    if (append && joint_read(RUN_JOINT_FILE, &old, &old_keep, &old_chain) == 0) {
+        if (old_keep != 1 || old_chain != 0 || old.n_par != n_par || old.nbins != nbins || old.thin != thin ||
+            old.n_pairs != r->n_pairs) {
+            fprintf(stderr, "%s: written by a run of another shape (chains, parameters, NBINS or thin:N); "
+                            "cannot append\n", RUN_JOINT_FILE);
+            exit(1);
+        }
+        resumed = 1;
+    } else if (append)
+        fprintf(stderr, "--append: no %s, the joint marginals start with this run\n", RUN_JOINT_FILE);
+    joint_alloc(r);
+    for (i = 0; i < n_par; i++)
+        for (j = i + 1; j < n_par; j++, q++) {
+            r->pairs[2 * q] = (int32_t)i;
+            r->pairs[2 * q + 1] = (int32_t)j;
+        }
+    for (p = 0; p < n_par; p++) {
+        r->lo[p] = get_params_min_for(chain0, p);
+        r->hi[p] = get_params_max_for(chain0, p);
+        if (resumed && (old.lo[p] != r->lo[p] || old.hi[p] != r->hi[p])) {
+            fprintf(stderr, "%s: parameter %u had the range [%g, %g], now [%g, %g]; cannot append\n", RUN_JOINT_FILE, p,
+                    old.lo[p], old.hi[p], r->lo[p], r->hi[p]);
+            exit(1);
+        }
+    }
+    if (resumed && memcmp(old.pairs, r->pairs, (size_t)r->n_pairs * 2 * sizeof(int32_t)) != 0) {
+        fprintf(stderr, "%s: written by a run of another shape (chains, parameters, NBINS or thin:N); "
+                        "cannot append\n", RUN_JOINT_FILE);
+        exit(1);
+    }
+    c.n_keep = 1;
+    c.chains = &chain;
+    c.nbins = (int32_t)nbins;
+    c.n_pairs = 0;
+    c.pairs = NULL; /* all pairs, in the order written above */
+    c.lo = r->lo;
+    c.hi = r->hi;
+    apemost_hip_or_die(apemost_hip_joint_begin(s, &c), "joint_begin");
+    if (resumed) {
+        r->n = old.n;
+        memcpy(r->origin, old.origin, n_par * sizeof(double));
+        memcpy(r->sum, old.sum, n_par * sizeof(double));
+        memcpy(r->cross, old.cross, tri_count(r) * sizeof(double));
+        memcpy(r->counts, old.counts, (size_t)r->n_pairs * nbins * nbins * sizeof(uint64_t));
+        joint_view(r, &v);
+        apemost_hip_or_die(apemost_hip_joint_set(s, &v), "joint_set");
+    }
+    if (old.lo != NULL)
+        joint_free(&old);
+}
+
+/* "%.15e", a NaN of either sign as nan */
+static void print_value(FILE *f, double v) {
+    if (v != v)
+        fprintf(f, "nan");
+    else
+        fprintf(f, "%.15e", v);
+}
+
+/* the summary's edge b of n over [lo, hi] (gsl_histogram_set_ranges_uniform, the top one widened as create_hist()).
+ * The definition it must follow is summary_edge of apemost_amd/csrc/pt_summary.h, which bins the samples: the same
+ * two products and one sum, unfused (summary.edges of apemost_amd/summary.py is the Python statement of it). */
+static double joint_edge(double lo, double hi, unsigned int b, unsigned int n) {
+    const double f1 = (double)(n - b) / (double)n, f2 = (double)b / (double)n;
+    double e = f1 * lo;
+    const double t = f2 * hi;
+    e = e + t;
+    if (b == n)
+        e += (hi - lo) / 10000;
+    return e;
+}
+
+static void write_pair(const run_joint *r, unsigned int q, const char **names) {
+    const unsigned int i = (unsigned int)r->pairs[2 * q], j = (unsigned int)r->pairs[2 * q + 1], n = r->nbins;
+    const uint64_t *c = r->counts + (size_t)q * n * n;
+    char name[500], (*ey)[32];
+    char x0[32], x1[32];
+    unsigned int a, b;
+    FILE *f;
+    sprintf(name, "%.200s-%.200s.joint", names[i], names[j]);
+    f = open_or_die(name, "w");
+    ey = (char(*)[32])alloc_or_die((size_t)n + 1, 32);
+    for (b = 0; b <= n; b++)
+        sprintf(ey[b], "%.15e", joint_edge(r->lo[j], r->hi[j], b, n));
+    for (a = 0; a < n; a++) {
+        sprintf(x0, "%.15e", joint_edge(r->lo[i], r->hi[i], a, n));
+        sprintf(x1, "%.15e", joint_edge(r->lo[i], r->hi[i], a + 1, n));
+        for (b = 0; b < n; b++)
+            fprintf(f, "%s %s %s %s %lu\n", x0, x1, ey[b], ey[b + 1], (unsigned long)c[(size_t)a * n + b]);
+        fprintf(f, "\n");
+    }
+    free(ey);
+    close_or_die(f, name);
+}
+
+/* cov_ij = (cross_ij - sum_i sum_j / n) / (n - 1); corr_ij = cov_ij / (sqrt(cov_ii) sqrt(cov_jj)), the diagonal 1 where
+ * the variance is finite and positive and NaN elsewhere: apemost_amd/joint.py, operation for operation */
+static void write_correlation(const run_joint *r) {
+    const unsigned int np = r->n_par;
+    const double n = (double)r->n, n1 = n - 1.0;
+    double *cov = (double *)alloc_or_die((size_t)np * np, sizeof(double));
+    double *sd = (double *)alloc_or_die(np, sizeof(double));
+    unsigned int i, j;
+    FILE *f = open_or_die("correlation.matrix", "w");
+    for (i = 0; i < np; i++)
+        for (j = 0; j < np; j++) {
+            const double cr = r->cross[i <= j ? tri_index(r, i, j) : tri_index(r, j, i)];
+            const double prod = r->sum[i] * r->sum[j];
+            const double part = prod / n;
+            const double diff = cr - part;
+            cov[(size_t)i * np + j] = diff / n1;
+        }
+    for (i = 0; i < np; i++)
+        sd[i] = sqrt(cov[(size_t)i * np + i]);
+    for (i = 0; i < np; i++) {
+        for (j = 0; j < np; j++) {
+            const double v = cov[(size_t)i * np + i], scale = sd[i] * sd[j];
+            double x = cov[(size_t)i * np + j] / scale;
+            if (i == j)
+                x = (v > 0 && v - v == 0) ? 1.0 : sqrt(-1.0);
+            if (j > 0)
+                fprintf(f, "\t");
+            print_value(f, x);
+        }
+        fprintf(f, "\n");
+    }
+    free(cov);
+    free(sd);
+    close_or_die(f, "correlation.matrix");
+}
+
+void run_joint_close(run_joint *r, apemost_hip_sampler *s, const mcmc *chain0) {
+    const char **names = get_params_descr(chain0);
+    apemost_hip_joint_view v;
+    unsigned int q;
+    joint_view(r, &v);
+    apemost_hip_or_die(apemost_hip_joint_get(s, &v), "joint_get");
+    apemost_hip_or_die(apemost_hip_joint_end(s), "joint_end");
+    joint_write(RUN_JOINT_FILE, r);
+    for (q = 0; q < r->n_pairs; q++)
+        write_pair(r, q, names);
+    write_correlation(r);
+    joint_free(r);
+}

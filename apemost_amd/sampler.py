@@ -408,6 +408,49 @@ class HipSampler:
     def peaks_end(self):
         capi.check(self.L.apemost_hip_peaks_end(self._h))
 
+    # -- on-device joint marginals (apemost_amd/joint.py) ------------------------------------------
+    def joint_begin(self, lo, hi, chains=(0,), nbins=200, pairs=None):
+        """start pair histograms (nbins x nbins over [lo, hi], the summary's bins) and moments about the first
+        sample for the local chains `chains` (strictly increasing; b * chains_per_ladder is ladder b's chain 0).
+        pairs: a list of (i, j), i < j; None: all of them in lexicographic order; []: the moments alone."""
+        from .joint import all_pairs
+        self._jt_lo = np.ascontiguousarray(lo, dtype=np.float64)
+        self._jt_hi = np.ascontiguousarray(hi, dtype=np.float64)
+        self._jt_chains = np.ascontiguousarray(chains, dtype=np.int32)
+        assert self._jt_lo.shape == (self.n_par,) and self._jt_hi.shape == (self.n_par,) and self._jt_chains.ndim == 1
+        self._jt_pairs = np.ascontiguousarray(all_pairs(self.n_par) if pairs is None else pairs,
+                                              dtype=np.int32).reshape(-1, 2)
+        self._jt_nbins = int(nbins)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        given = np.zeros((max(len(self._jt_pairs), 1), 2), dtype=np.int32)    # (never a NULL pointer for an empty list)
+        given[:len(self._jt_pairs)] = self._jt_pairs
+        cfg = capi.JointConfig(n_keep=len(self._jt_chains), chains=self._jt_chains.ctypes.data_as(ip), nbins=nbins,
+                               n_pairs=len(self._jt_pairs), pairs=None if pairs is None else given.ctypes.data_as(ip),
+                               lo=self._jt_lo.ctypes.data_as(dp), hi=self._jt_hi.ctypes.data_as(dp))
+        capi.check(self.L.apemost_hip_joint_begin(self._h, C.byref(cfg)))
+
+    def joint_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2] into the joint
+        marginals; asynchronous (joint() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_joint_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def joint(self):
+        """the joint marginals so far as a Joint object (synchronises with the accumulates issued so far)"""
+        from .joint import Joint
+        jt = Joint.empty(len(self._jt_chains), self.n_par, self._jt_nbins, self._jt_pairs, self._jt_lo, self._jt_hi,
+                         self._jt_chains)
+        capi.check(self.L.apemost_hip_joint_get(self._h, C.byref(jt.view())))
+        return jt
+
+    def joint_set(self, jt):
+        """load a Joint (a resumed run) into the joint begun with the same configuration"""
+        assert jt.counts.shape == (len(self._jt_chains), len(self._jt_pairs), self._jt_nbins, self._jt_nbins)
+        assert jt.sum.shape == (len(self._jt_chains), self.n_par) and np.array_equal(jt.pairs, self._jt_pairs)
+        capi.check(self.L.apemost_hip_joint_set(self._h, C.byref(jt.view())))
+
+    def joint_end(self):
+        capi.check(self.L.apemost_hip_joint_end(self._h))
+
     # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------
     def samples_text_bound(self, n_steps, skip=0, thin=1, n_param_chains=1):
         """(streams, host text bytes, device scratch bytes) of one samples_text batch"""

@@ -649,6 +649,67 @@ int apemost_hip_peaks_end(apemost_hip_sampler *s);
 int apemost_hip_peaks_table(const apemost_hip_peaks_view *v, int32_t n_par, int32_t k, int32_t p, double *table,
                             uint32_t *n_rows);
 
+/* ---- on-device joint marginals: pair histograms and covariance, without dumps ------------------
+ * What a corner plot and a parameter covariance need and neither the 1-D bin counts of the run summary nor the
+ * sorted columns of peaks can give: how the parameters of a kept chain depend on each other.  Accumulated from the
+ * sample rows while they are still on the device, per kept chain k:
+ *   n                   kept samples so far;
+ *   counts[k][q][a][b]  for pair q = (i, j), i < j: the samples whose parameter i lies in bin a and whose parameter j
+ *                       lies in bin b.  The bins are the run summary's: nbins bins over [lo[p], hi[p]] on the edges
+ *                       ((nbins-b)/nbins)*lo + (b/nbins)*hi, the top one widened by (hi-lo)/10000, bin b holding
+ *                       e[b] <= v < e[b+1], found by gsl_histogram_increment's bisection (one device function for
+ *                       both).  A sample counts only if both values have a bin: anything outside a parameter's range,
+ *                       NaN included, is dropped.  While every sample lies inside the box the sums of counts[k][q] over
+ *                       b and over a are the summary's hist of parameters i and j;
+ *   origin[k][p]        parameter p of the first sample ever accumulated for chain k (0 before there is one);
+ *   sum[k][p]           the sequential sum, in sample order, of d_p = v_p - origin[k][p] over every kept sample;
+ *   cross[k][i][j]      for i <= j the sequential sum of d_i * d_j, the product rounded to fp64 and then added, stored
+ *                       as the upper triangle row by row: (0,0), (0,1), .., (0,n_par-1), (1,1), ...
+ *                       No filter on the moments: every kept sample enters, so a non-finite value makes the sums of
+ *                       its parameter non-finite.  mean = origin + sum / n, covariance = (cross_ij - sum_i sum_j / n)
+ *                       / (n - 1): taken about the origin, which lies inside the sample, the subtraction cancels
+ *                       digits of the spread, not of the position.
+ * Every count is exact and every sum is one thread's chain of additions in sample order: the results are bitwise
+ * equal to a sequential host loop, whatever the boundaries of the accumulate calls are.
+ * Sharded ladders: the caller begins on the shard that holds the chain.  Ladder batches: `chains` indexes the grid's
+ * local chains, ladder-major: b * n_chains is ladder b's chain 0.  Both as for peaks. */
+typedef struct {
+    int32_t n_keep;          /* number of kept chains, 1 .. n_chains; n_keep * n_par <= 65535 */
+    const int32_t *chains;   /* host [n_keep]: local chain indices, strictly increasing */
+    int32_t nbins;           /* 1 .. 512 */
+    int32_t n_pairs;         /* pairs given; 0 with pairs != NULL: the moments alone; ignored with pairs == NULL */
+    const int32_t *pairs;    /* host [n_pairs][2], i < j, no duplicates; NULL: all n_par (n_par - 1) / 2 pairs i < j in
+                                lexicographic order */
+    const double *lo, *hi;   /* host [n_par]: the histogram range, finite, lo < hi, hi - lo finite */
+} apemost_hip_joint_config;
+typedef struct {
+    uint64_t *n;             /* kept samples */
+    uint64_t *counts;        /* [n_keep][n_pairs][nbins][nbins] */
+    double *origin, *sum;    /* [n_keep][n_par] */
+    double *cross;           /* [n_keep][n_par (n_par + 1) / 2], upper triangle row-major */
+} apemost_hip_joint_view;    /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates and zeroes the accumulator, and device scratch for one staged piece of the kept columns (10 bytes per
+ * value, about 4 Mi values).  A joint begun before is dropped once the new configuration has been accepted; a begin
+ * that is refused leaves it open and accumulating as it was.  APEMOST_HIP_ERR_INVALID, before any device work, for a
+ * NULL config, n_keep or a chain index out of range, chains not strictly increasing, nbins outside 1 .. 512, a pair
+ * with i >= j, an index out of range or a duplicate, missing lo or hi, a range that is not finite with lo < hi, or a
+ * counts array above 2^30 bytes. */
+int apemost_hip_joint_begin(apemost_hip_sampler *s, const apemost_hip_joint_config *cfg);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2], the rows of the
+ * launches issued so far) into the accumulator.  Asynchronous and queued like apemost_hip_summary_accumulate: the
+ * round kernels never wait for it, and apemost_hip_samples_wait (or joint_get) must have returned before d_samples is
+ * written again.  APEMOST_HIP_ERR_INVALID without joint_begin or with thin == 0. */
+int apemost_hip_joint_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                 uint64_t thin);
+/* copies the accumulator out (synchronises with the accumulates issued so far) */
+int apemost_hip_joint_get(apemost_hip_sampler *s, const apemost_hip_joint_view *v);
+/* loads a view saved by joint_get into a joint begun with the same configuration (a resumed run); the origin is
+ * loaded too, and with n > 0 the next sample does not replace it */
+int apemost_hip_joint_set(apemost_hip_sampler *s, const apemost_hip_joint_view *v);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_joint_end(apemost_hip_sampler *s);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
