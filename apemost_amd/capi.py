@@ -84,6 +84,14 @@ class JointView(C.Structure):
     _fields_ = [("n", _up), ("counts", _up), ("origin", _dp), ("sum", _dp), ("cross", _dp)]
 
 
+class EvidenceConfig(C.Structure):
+    _fields_ = [("batch_size", C.c_uint64), ("max_batches", C.c_uint64), ("coef_up", _dp), ("coef_down", _dp)]
+
+
+class EvidenceView(C.Structure):
+    _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("batch", _dp), ("m", _dp), ("S", _dp)]
+
+
 PEAKS_MAX = 99   # peaks described per column (include/apemost_hip.h)
 
 
@@ -119,6 +127,8 @@ EXPORTS = [
     "apemost_hip_peaks_table",
     "apemost_hip_joint_begin", "apemost_hip_joint_accumulate", "apemost_hip_joint_get", "apemost_hip_joint_set",
     "apemost_hip_joint_end",
+    "apemost_hip_evidence_begin", "apemost_hip_evidence_accumulate", "apemost_hip_evidence_get",
+    "apemost_hip_evidence_set", "apemost_hip_evidence_end",
 ]
 
 _lib = None
@@ -235,6 +245,11 @@ def lib():
     L.apemost_hip_joint_get.argtypes = [vp, C.POINTER(JointView)]
     L.apemost_hip_joint_set.argtypes = [vp, C.POINTER(JointView)]
     L.apemost_hip_joint_end.argtypes = [vp]
+    L.apemost_hip_evidence_begin.argtypes = [vp, C.POINTER(EvidenceConfig)]
+    L.apemost_hip_evidence_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_evidence_get.argtypes = [vp, C.POINTER(EvidenceView)]
+    L.apemost_hip_evidence_set.argtypes = [vp, C.POINTER(EvidenceView)]
+    L.apemost_hip_evidence_end.argtypes = [vp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

@@ -1,5 +1,6 @@
 // apemost_hip.hip -- kernels and C ABI of the gfx950 parallel-tempering engine
 // (declared in include/apemost_hip.h).  Written for MI355X only.
+#include "pt_evidence.h"
 #include "pt_joint.h"
 #include "pt_kernels.h"
 #include "pt_peaks.h"
@@ -369,6 +370,15 @@ struct apemost_hip_sampler {
         unsigned short *d_bins;
         u64 *d_counts;
     } jt;
+    // on-device evidence fold (apemost_hip_evidence_begin .. end): moments, batch sums and log-sum-exps of column
+    // n_par+1 of every chain, on copy_stream
+    struct {
+        bool open;
+        u64 bs, max_batches;
+        u64 chunk; // kept steps staged per launch
+        u64 n;     // kept samples so far (the host knows it without a sync)
+        double *d_coef, *d_vals, *d_origin, *d_sum, *d_sq, *d_batch, *d_m, *d_S;
+    } ev;
 };
 
 extern "C" const char *apemost_hip_last_error(void) { return g_last_error.c_str(); }
@@ -497,6 +507,14 @@ static void joint_free(apemost_hip_sampler *s) {
     s->jt = {};
 }
 
+static void evidence_free(apemost_hip_sampler *s) {
+    for (double *p : {s->ev.d_coef, s->ev.d_vals, s->ev.d_origin, s->ev.d_sum, s->ev.d_sq, s->ev.d_batch, s->ev.d_m,
+                      s->ev.d_S})
+        if (p)
+            hipFree(p);
+    s->ev = {};
+}
+
 // everything a sampler owns on the device; safe on a half-built sampler
 static void release(apemost_hip_sampler *s) {
     if (s->stream)
@@ -526,6 +544,7 @@ static void release(apemost_hip_sampler *s) {
     summary_free(s); // (its kernels ran on copy_stream)
     peaks_free(s);
     joint_free(s);
+    evidence_free(s);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {
@@ -2476,6 +2495,169 @@ extern "C" int apemost_hip_joint_end(apemost_hip_sampler *s) {
     if (s->copy_stream)
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     joint_free(s);
+    return APEMOST_HIP_OK;
+}
+
+// ---- on-device evidence fold (pt_evidence.h) ----
+extern "C" int apemost_hip_evidence_begin(apemost_hip_sampler *s, const apemost_hip_evidence_config *cfg) {
+    CHECK_S(s);
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: config is NULL");
+    if (cfg->batch_size < 1)
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: batch_size must be >= 1");
+    if (!cfg->coef_up || !cfg->coef_down)
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: coef_up and coef_down are needed");
+    const size_t nc = (size_t)s->cfg.n_chains;
+    for (size_t c = 0; c < nc; c++)
+        if (!std::isfinite(cfg->coef_up[c]) || !std::isfinite(cfg->coef_down[c]))
+            return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: chain %zu: coefficients (%g, %g) are not finite", c,
+                        cfg->coef_up[c], cfg->coef_down[c]);
+    if (cfg->max_batches > ((size_t)1 << 40) || cfg->max_batches + 1 > ((size_t)1 << 40) / nc)
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: max_batches %llu too large",
+                    (unsigned long long)cfg->max_batches);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a fold begun before may still be accumulating
+    evidence_free(s);
+    // the staged column: about 1 Mi values over all chains, at least 256 and at most 2^18 kept steps per launch
+    u64 chunk = ((u64)1 << 20) / nc;
+    chunk = chunk < 256 ? 256 : chunk > ((u64)1 << 18) ? (u64)1 << 18 : chunk;
+    s->ev.bs = cfg->batch_size;
+    s->ev.max_batches = cfg->max_batches;
+    s->ev.chunk = chunk;
+    s->ev.n = 0;
+    const size_t nb = nc * (cfg->max_batches + 1);
+    HIP_TRY(hipMalloc((void **)&s->ev.d_coef, 2 * nc * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ev.d_vals, nc * chunk * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ev.d_origin, nc * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ev.d_sum, nc * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ev.d_sq, nc * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ev.d_batch, nb * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ev.d_m, 2 * nc * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ev.d_S, 2 * nc * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(s->ev.d_origin, 0, nc * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ev.d_sum, 0, nc * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ev.d_sq, 0, nc * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ev.d_batch, 0, nb * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ev.d_m, 0, 2 * nc * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ev.d_S, 0, 2 * nc * sizeof(double), s->stream));
+    HIP_TRY(hipMemcpyAsync(s->ev.d_coef, cfg->coef_up, nc * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->ev.d_coef + nc, cfg->coef_down, nc * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's arrays are read until here)
+    s->ev.open = true;
+    return APEMOST_HIP_OK;
+}
+
+// Queued on copy_stream behind everything launched so far on the sampler's stream, like
+// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
+extern "C" int apemost_hip_evidence_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                               uint64_t skip, uint64_t thin) {
+    CHECK_S(s);
+    if (!s->ev.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence_accumulate: no evidence_begin");
+    if (thin < 1 || (!d_samples && n_steps > 0))
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence_accumulate: bad arguments");
+    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    if (summary_closed(s->ev.n + kept, s->ev.bs) > s->ev.max_batches)
+        return fail(APEMOST_HIP_ERR_INVALID,
+                    "evidence_accumulate: %llu samples would close batch %llu, beyond max_batches = %llu",
+                    (unsigned long long)(s->ev.n + kept), (unsigned long long)summary_closed(s->ev.n + kept, s->ev.bs),
+                    (unsigned long long)s->ev.max_batches);
+    if (kept == 0)
+        return APEMOST_HIP_OK;
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const int nc = s->cfg.n_chains;
+    for (u64 k0 = 0; k0 < kept; k0 += s->ev.chunk) {
+        EvidenceArgs a;
+        a.rows = d_samples;
+        a.n_chains = nc;
+        a.n_par = s->cfg.n_par;
+        a.skip = skip + k0 * thin;
+        a.thin = thin;
+        a.n = (unsigned int)(kept - k0 < s->ev.chunk ? kept - k0 : s->ev.chunk);
+        a.first = s->ev.n == 0;
+        a.bs = s->ev.bs;
+        a.left = summary_left(s->ev.n, s->ev.bs);
+        a.n_closed = summary_closed(s->ev.n, s->ev.bs);
+        a.batch_stride = s->ev.max_batches + 1;
+        a.coef = s->ev.d_coef;
+        a.vals = s->ev.d_vals;
+        a.origin = s->ev.d_origin;
+        a.sum = s->ev.d_sum;
+        a.sq = s->ev.d_sq;
+        a.batch = s->ev.d_batch;
+        a.m = s->ev.d_m;
+        a.S = s->ev.d_S;
+        hipLaunchKernelGGL(evidence_gather_kernel,
+                           dim3((unsigned)((nc + kEvidenceGatherThreads - 1) / kEvidenceGatherThreads), (a.n + 7u) / 8u),
+                           dim3(kEvidenceGatherThreads), 0, s->copy_stream, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(evidence_fold_kernel,
+                           dim3((unsigned)((nc + kEvidenceThreads - 1) / kEvidenceThreads), (unsigned)kEvidenceQuantities),
+                           dim3(kEvidenceThreads), 0, s->copy_stream, a);
+        HIP_TRY(hipGetLastError());
+        s->ev.n += a.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+static int evidence_xfer(apemost_hip_sampler *s, const apemost_hip_evidence_view *v, bool up) {
+    if (!s->ev.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence_%s: no evidence_begin", up ? "set" : "get");
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence view is NULL");
+    if (up && v->n && summary_closed(*v->n, s->ev.bs) > s->ev.max_batches)
+        return fail(APEMOST_HIP_ERR_INVALID, "evidence_set: %llu samples close more than max_batches batches",
+                    (unsigned long long)*v->n);
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const size_t nc = (size_t)s->cfg.n_chains;
+    // stream order: behind every accumulate queued so far, on the stream they run on
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+#define EVIDENCE_COPY(dev, host, bytes)                                                                        \
+    do {                                                                                                       \
+        if ((host) && (bytes) > 0)                                                                             \
+            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
+                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
+    } while (0)
+    EVIDENCE_COPY(s->ev.d_origin, v->origin, nc * sizeof(double));
+    EVIDENCE_COPY(s->ev.d_sum, v->sum, nc * sizeof(double));
+    EVIDENCE_COPY(s->ev.d_sq, v->sq, nc * sizeof(double));
+    EVIDENCE_COPY(s->ev.d_batch, v->batch, nc * (s->ev.max_batches + 1) * sizeof(double));
+    EVIDENCE_COPY(s->ev.d_m, v->m, 2 * nc * sizeof(double));
+    EVIDENCE_COPY(s->ev.d_S, v->S, 2 * nc * sizeof(double));
+#undef EVIDENCE_COPY
+    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    if (v->n) {
+        if (up)
+            s->ev.n = *v->n;
+        else
+            *v->n = s->ev.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_evidence_get(apemost_hip_sampler *s, const apemost_hip_evidence_view *v) {
+    CHECK_S(s);
+    return evidence_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_evidence_set(apemost_hip_sampler *s, const apemost_hip_evidence_view *v) {
+    CHECK_S(s);
+    return evidence_xfer(s, v, true);
+}
+
+extern "C" int apemost_hip_evidence_end(apemost_hip_sampler *s) {
+    CHECK_S(s);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    evidence_free(s);
     return APEMOST_HIP_OK;
 }
 

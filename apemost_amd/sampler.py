@@ -451,6 +451,48 @@ class HipSampler:
     def joint_end(self):
         capi.check(self.L.apemost_hip_joint_end(self._h))
 
+    # -- on-device evidence fold (apemost_amd/evidence.py) ------------------------------------------
+    def evidence_begin(self, betas=None, batch_size=1, max_batches=0, coef_up=None, coef_down=None, thin=1):
+        """start the fold of column n_par+1 of every local chain: moments about the first sample, batch sums and the
+        two log-sum-exps of the stepping-stone estimators.  betas: the ladder-major betas of the local chains (None:
+        the sampler's own); the coefficients follow from them (Evidence.coefficients) unless coef_up and coef_down
+        [n_chains] are given, which a shard of a sharded ladder needs: its neighbours' betas live elsewhere."""
+        from .evidence import Evidence
+        if betas is None:
+            betas = self.get_state(fields=("beta",)).beta
+        self._ev_betas = np.ascontiguousarray(betas, dtype=np.float64)
+        assert self._ev_betas.shape == (self.n_chains,)
+        if coef_up is None or coef_down is None:
+            coef_up, coef_down = Evidence.coefficients(self._ev_betas, self.n_ladders)
+        self._ev_coef = np.ascontiguousarray([coef_up, coef_down], dtype=np.float64)
+        assert self._ev_coef.shape == (2, self.n_chains)
+        self._ev_bs, self._ev_max, self._ev_thin = int(batch_size), int(max_batches), int(thin)
+        cfg = capi.EvidenceConfig(batch_size=batch_size, max_batches=max_batches,
+                                  coef_up=self._ev_coef[0].ctypes.data_as(capi._dp),
+                                  coef_down=self._ev_coef[1].ctypes.data_as(capi._dp))
+        capi.check(self.L.apemost_hip_evidence_begin(self._h, C.byref(cfg)))
+
+    def evidence_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]; asynchronous
+        (evidence() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_evidence_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def evidence(self):
+        """the fold so far as an Evidence object (synchronises with the accumulates issued so far)"""
+        from .evidence import Evidence
+        ev = Evidence.empty(self._ev_betas, self._ev_bs, self._ev_max, self._ev_coef[0], self._ev_coef[1],
+                            self.n_ladders, self._ev_thin)
+        capi.check(self.L.apemost_hip_evidence_get(self._h, C.byref(ev.view())))
+        return ev
+
+    def evidence_set(self, ev):
+        """load an Evidence (a resumed run) into the fold begun with the same configuration"""
+        assert ev.batch.shape == (self.n_chains, self._ev_max + 1) and ev.batch_size == self._ev_bs
+        capi.check(self.L.apemost_hip_evidence_set(self._h, C.byref(ev.view())))
+
+    def evidence_end(self):
+        capi.check(self.L.apemost_hip_evidence_end(self._h))
+
     # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------
     def samples_text_bound(self, n_steps, skip=0, thin=1, n_param_chains=1):
         """(streams, host text bytes, device scratch bytes) of one samples_text batch"""

@@ -710,6 +710,70 @@ int apemost_hip_joint_set(apemost_hip_sampler *s, const apemost_hip_joint_view *
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_joint_end(apemost_hip_sampler *s);
 
+/* ---- on-device evidence fold: stepping stone, corrected trapezoid, error bars ------------------
+ * What the estimators of ln p(D|M,I) beyond the rectangle rule of the run summary need, and what a run without sample
+ * dumps cannot recompute: per chain the variance and the batch sums of column n_par+1 (v = prob - prior = beta *
+ * loglike), and the log-mean-exp of multiples of it.  Accumulated from the sample rows while they are still on the
+ * device, for EVERY local chain c of the sampler:
+ *   n               kept samples so far, the same for every chain;
+ *   origin[c]       v of the first sample ever accumulated (0 before there is one);
+ *   sum[c], sq[c]   with d = v - origin[c] the sequential sums, in sample order, of d and of d * d (the product rounded
+ *                   to fp64 and then added).  mean v = origin + sum / n, variance = (sq - sum^2 / n) / (n - 1): taken
+ *                   about the origin, which lies inside the sample, the subtraction cancels digits of the spread, not
+ *                   of the position (v is of the order of the log-likelihood, its spread of the order of n_par);
+ *   batch[c][k]     batch sums of v under the closing rule of the summary's batch_sums: sample n, counted from 1,
+ *                   closes a batch when n % batch_size == batch_size - 1; k < n_batches are closed, slot n_batches holds
+ *                   the sum of the batch still open.  The array is [n_chains][max_batches + 1];
+ *   m[s][c], S[s][c]   for s = 0 (up) and 1 (down) a running log-sum-exp of x = coef_s[c] * v (one rounded
+ *                   multiply): the first sample sets m = x, S = 1; every later one
+ *                       if (x > m) { S = S * exp(m - x) + 1; m = x; } else S += exp(x - m);
+ *                   with the device library's fp64 exp, so that ln mean exp(x) = m + ln(S / n).  m is the running
+ *                   maximum of x (exact); S carries one rounding of exp, of the multiply and of the add per sample.
+ *                   The arrays are [2][n_chains].  With coef_up[c] = (beta_{c-1} - beta_c) / beta_c and
+ *                   coef_down[c] = -(beta_c - beta_{c+1}) / beta_c these are the stepping-stone ratios
+ *                   ln Z(beta_{c-1}) / Z(beta_c) and -ln Z(beta_{c+1}) / Z(beta_c) (Xie et al. 2011); the device
+ *                   sees the coefficients only, never a beta (apemost_amd/evidence.py computes them).
+ * No filter: every kept sample enters, so a non-finite v makes the sums of its chain non-finite.
+ * Every quantity is one thread's chain of operations in sample order, its state carried in device memory between
+ * calls: origin, sum, sq, batch and m are bitwise equal to a sequential host loop, S is equal to it up to exp,
+ * whatever the boundaries of the accumulate calls are.
+ * Ladder batches: the chains are the grid's local chains, ladder-major, and so are the coefficients the caller
+ * supplies.  Sharded ladders: one accumulator per shard with that shard's slice of the coefficients; the caller
+ * concatenates. */
+typedef struct {
+    uint64_t batch_size;      /* >= 1 */
+    uint64_t max_batches;     /* capacity: an accumulate that would close batch max_batches + 1 is invalid */
+    const double *coef_up;    /* host [n_chains], finite */
+    const double *coef_down;  /* host [n_chains], finite */
+} apemost_hip_evidence_config;
+typedef struct {
+    uint64_t *n;              /* kept samples */
+    double *origin, *sum, *sq; /* [n_chains] */
+    double *batch;            /* [n_chains][max_batches + 1] */
+    double *m, *S;            /* [2][n_chains]: up, down */
+} apemost_hip_evidence_view;  /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates and zeroes the accumulator, and device scratch for one staged piece of the column (about 1 Mi values).
+ * An evidence fold begun before is dropped once the new configuration has been accepted; a begin that is refused
+ * leaves it open and accumulating as it was.  APEMOST_HIP_ERR_INVALID, before any device work, for a NULL config,
+ * batch_size == 0, a missing or non-finite coefficient, or a max_batches whose batch array would exceed 2^40 values. */
+int apemost_hip_evidence_begin(apemost_hip_sampler *s, const apemost_hip_evidence_config *cfg);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2], the rows of the
+ * launches issued so far) into the accumulator.  Asynchronous and queued like apemost_hip_summary_accumulate, on the
+ * stream of apemost_hip_samples_read_async: the round kernels never wait for it, and apemost_hip_samples_wait (or
+ * evidence_get) must have returned before d_samples is written again.  APEMOST_HIP_ERR_INVALID, before any device
+ * work, without evidence_begin, with thin == 0, or when the kept steps would close batch max_batches + 1. */
+int apemost_hip_evidence_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                    uint64_t thin);
+/* copies the accumulator out (synchronises with the accumulates issued so far) */
+int apemost_hip_evidence_get(apemost_hip_sampler *s, const apemost_hip_evidence_view *v);
+/* loads a view saved by evidence_get into a fold begun with the same configuration (a resumed run); with n > 0 the
+ * next sample replaces neither the origin nor m and S.  APEMOST_HIP_ERR_INVALID when n closes more than max_batches
+ * batches. */
+int apemost_hip_evidence_set(apemost_hip_sampler *s, const apemost_hip_evidence_view *v);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_evidence_end(apemost_hip_sampler *s);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
