@@ -92,6 +92,15 @@ class EvidenceView(C.Structure):
     _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("batch", _dp), ("m", _dp), ("S", _dp)]
 
 
+class AutocorrConfig(C.Structure):
+    _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("max_lag", C.c_int32), ("n_cols", C.c_int32),
+                ("cols", C.POINTER(C.c_int32))]
+
+
+class AutocorrView(C.Structure):
+    _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("lag", _dp), ("head", _dp), ("tail", _dp)]
+
+
 PEAKS_MAX = 99   # peaks described per column (include/apemost_hip.h)
 
 
@@ -129,6 +138,8 @@ EXPORTS = [
     "apemost_hip_joint_end",
     "apemost_hip_evidence_begin", "apemost_hip_evidence_accumulate", "apemost_hip_evidence_get",
     "apemost_hip_evidence_set", "apemost_hip_evidence_end",
+    "apemost_hip_autocorr_begin", "apemost_hip_autocorr_accumulate", "apemost_hip_autocorr_get",
+    "apemost_hip_autocorr_set", "apemost_hip_autocorr_end",
 ]
 
 _lib = None
@@ -250,6 +261,11 @@ def lib():
     L.apemost_hip_evidence_get.argtypes = [vp, C.POINTER(EvidenceView)]
     L.apemost_hip_evidence_set.argtypes = [vp, C.POINTER(EvidenceView)]
     L.apemost_hip_evidence_end.argtypes = [vp]
+    L.apemost_hip_autocorr_begin.argtypes = [vp, C.POINTER(AutocorrConfig)]
+    L.apemost_hip_autocorr_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_autocorr_get.argtypes = [vp, C.POINTER(AutocorrView)]
+    L.apemost_hip_autocorr_set.argtypes = [vp, C.POINTER(AutocorrView)]
+    L.apemost_hip_autocorr_end.argtypes = [vp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

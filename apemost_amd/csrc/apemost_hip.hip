@@ -1,5 +1,6 @@
 // apemost_hip.hip -- kernels and C ABI of the gfx950 parallel-tempering engine
 // (declared in include/apemost_hip.h).  Written for MI355X only.
+#include "pt_autocorr.h"
 #include "pt_evidence.h"
 #include "pt_joint.h"
 #include "pt_kernels.h"
@@ -379,6 +380,15 @@ struct apemost_hip_sampler {
         u64 n;     // kept samples so far (the host knows it without a sync)
         double *d_coef, *d_vals, *d_origin, *d_sum, *d_sq, *d_batch, *d_m, *d_S;
     } ev;
+    // on-device autocorrelation (apemost_hip_autocorr_begin .. end): lag sums of kept chains' columns, on copy_stream
+    struct {
+        bool open;
+        int n_keep, n_cols, max_lag;
+        u64 chunk; // kept steps staged per launch
+        u64 n;     // kept samples so far (the host knows it without a sync)
+        int *d_chains, *d_cols;
+        double *d_buf, *d_origin, *d_sum, *d_lag, *d_head, *d_tail;
+    } ac;
 };
 
 extern "C" const char *apemost_hip_last_error(void) { return g_last_error.c_str(); }
@@ -515,6 +525,16 @@ static void evidence_free(apemost_hip_sampler *s) {
     s->ev = {};
 }
 
+static void autocorr_free(apemost_hip_sampler *s) {
+    for (int *p : {s->ac.d_chains, s->ac.d_cols})
+        if (p)
+            hipFree(p);
+    for (double *p : {s->ac.d_buf, s->ac.d_origin, s->ac.d_sum, s->ac.d_lag, s->ac.d_head, s->ac.d_tail})
+        if (p)
+            hipFree(p);
+    s->ac = {};
+}
+
 // everything a sampler owns on the device; safe on a half-built sampler
 static void release(apemost_hip_sampler *s) {
     if (s->stream)
@@ -545,6 +565,7 @@ static void release(apemost_hip_sampler *s) {
     peaks_free(s);
     joint_free(s);
     evidence_free(s);
+    autocorr_free(s);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {
@@ -2658,6 +2679,186 @@ extern "C" int apemost_hip_evidence_end(apemost_hip_sampler *s) {
     if (s->copy_stream)
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     evidence_free(s);
+    return APEMOST_HIP_OK;
+}
+
+// ---- on-device autocorrelation (pt_autocorr.h) ----
+extern "C" int apemost_hip_autocorr_begin(apemost_hip_sampler *s, const apemost_hip_autocorr_config *cfg) {
+    CHECK_S(s);
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_begin: config is NULL");
+    const int np = s->cfg.n_par;
+    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
+        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
+                    s->cfg.n_chains);
+    for (int k = 0; k < cfg->n_keep; k++)
+        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
+            return fail(APEMOST_HIP_ERR_INVALID,
+                        "autocorr_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing", k,
+                        cfg->chains[k], s->cfg.n_chains);
+    if (cfg->max_lag < 1 || cfg->max_lag > kAutocorrMaxLag)
+        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_begin: max_lag %d outside [1,%d]", cfg->max_lag, kAutocorrMaxLag);
+    std::vector<int> cols;
+    if (!cfg->cols) { // the parameters and prob - prior
+        for (int p = 0; p < np; p++)
+            cols.push_back(p);
+        cols.push_back(np + 1);
+    } else {
+        if (cfg->n_cols < 1 || cfg->n_cols > np + 2)
+            return fail(APEMOST_HIP_ERR_INVALID, "autocorr_begin: n_cols %d outside [1,%d]", cfg->n_cols, np + 2);
+        for (int c = 0; c < cfg->n_cols; c++) {
+            if (cfg->cols[c] < 0 || cfg->cols[c] > np + 1 || (c > 0 && cfg->cols[c] <= cfg->cols[c - 1]))
+                return fail(APEMOST_HIP_ERR_INVALID,
+                            "autocorr_begin: cols[%d] = %d: column indices in [0,%d], strictly increasing", c, cfg->cols[c],
+                            np + 1);
+            cols.push_back(cfg->cols[c]);
+        }
+    }
+    const u64 n_series = (u64)cfg->n_keep * cols.size();
+    const u64 L = (u64)cfg->max_lag, H = L - 1;
+    if (n_series > 65535 || n_series * L > ((u64)1 << 24))
+        return fail(APEMOST_HIP_ERR_INVALID,
+                    "autocorr_begin: %d chains x %zu columns x %d lags: more than 65535 series or 2^24 lag sums",
+                    cfg->n_keep, cols.size(), cfg->max_lag);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a fold begun before may still be accumulating
+    autocorr_free(s);
+    // the staged series: about 1 Mi values over all of them, at least 256 and at most 2^16 kept steps per launch
+    u64 chunk = ((u64)1 << 20) / n_series;
+    chunk = chunk < 256 ? 256 : chunk > ((u64)1 << 16) ? (u64)1 << 16 : chunk;
+    s->ac.n_keep = cfg->n_keep;
+    s->ac.n_cols = (int)cols.size();
+    s->ac.max_lag = cfg->max_lag;
+    s->ac.chunk = chunk;
+    s->ac.n = 0;
+    const size_t nh = (size_t)(n_series * (H > 0 ? H : 1));
+    HIP_TRY(hipMalloc((void **)&s->ac.d_chains, cfg->n_keep * sizeof(int)));
+    HIP_TRY(hipMalloc((void **)&s->ac.d_cols, cols.size() * sizeof(int)));
+    HIP_TRY(hipMalloc((void **)&s->ac.d_buf, n_series * (H + chunk) * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ac.d_origin, n_series * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ac.d_sum, n_series * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ac.d_lag, n_series * L * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ac.d_head, nh * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->ac.d_tail, nh * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(s->ac.d_origin, 0, n_series * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ac.d_sum, 0, n_series * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ac.d_lag, 0, n_series * L * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ac.d_head, 0, nh * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->ac.d_tail, 0, nh * sizeof(double), s->stream));
+    HIP_TRY(hipMemcpyAsync(s->ac.d_chains, cfg->chains, cfg->n_keep * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->ac.d_cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream)); // (`cols` and the caller's arrays are read until here)
+    s->ac.open = true;
+    return APEMOST_HIP_OK;
+}
+
+// Queued on copy_stream behind everything launched so far on the sampler's stream, like
+// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
+extern "C" int apemost_hip_autocorr_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                               uint64_t skip, uint64_t thin) {
+    CHECK_S(s);
+    if (!s->ac.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_accumulate: no autocorr_begin");
+    if (thin < 1 || (!d_samples && n_steps > 0))
+        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_accumulate: bad arguments");
+    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    if (kept == 0)
+        return APEMOST_HIP_OK;
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const unsigned n_series = (unsigned)(s->ac.n_keep * s->ac.n_cols);
+    const unsigned H = (unsigned)s->ac.max_lag - 1u;
+    for (u64 k0 = 0; k0 < kept; k0 += s->ac.chunk) {
+        AutocorrArgs a;
+        a.rows = d_samples;
+        a.n_chains = s->cfg.n_chains;
+        a.n_par = s->cfg.n_par;
+        a.n_keep = s->ac.n_keep;
+        a.n_cols = s->ac.n_cols;
+        a.chains = s->ac.d_chains;
+        a.cols = s->ac.d_cols;
+        a.skip = skip + k0 * thin;
+        a.thin = thin;
+        a.n = (unsigned int)(kept - k0 < s->ac.chunk ? kept - k0 : s->ac.chunk);
+        a.n0 = s->ac.n;
+        a.max_lag = s->ac.max_lag;
+        a.n_groups = (s->ac.max_lag + kAutocorrGroup - 1) / kAutocorrGroup;
+        a.stride = H + s->ac.chunk;
+        a.buf = s->ac.d_buf;
+        a.origin = s->ac.d_origin;
+        a.sum = s->ac.d_sum;
+        a.lag = s->ac.d_lag;
+        a.head = s->ac.d_head;
+        a.tail = s->ac.d_tail;
+        hipLaunchKernelGGL(autocorr_gather_kernel, dim3((H + a.n + kAutocorrThreads - 1) / kAutocorrThreads, n_series),
+                           dim3(kAutocorrThreads), 0, s->copy_stream, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(autocorr_fold_kernel, dim3((unsigned)a.n_groups + 1u, n_series), dim3(kAutocorrWave), 0,
+                           s->copy_stream, a);
+        HIP_TRY(hipGetLastError());
+        if (H > 0) {
+            hipLaunchKernelGGL(autocorr_carry_kernel, dim3((H + kAutocorrThreads - 1) / kAutocorrThreads, n_series),
+                               dim3(kAutocorrThreads), 0, s->copy_stream, a);
+            HIP_TRY(hipGetLastError());
+        }
+        s->ac.n += a.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+static int autocorr_xfer(apemost_hip_sampler *s, const apemost_hip_autocorr_view *v, bool up) {
+    if (!s->ac.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_%s: no autocorr_begin", up ? "set" : "get");
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "autocorr view is NULL");
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const size_t n_series = (size_t)s->ac.n_keep * s->ac.n_cols, L = (size_t)s->ac.max_lag, H = L - 1;
+    // stream order: behind every accumulate queued so far, on the stream they run on
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+#define AUTOCORR_COPY(dev, host, bytes)                                                                        \
+    do {                                                                                                       \
+        if ((host) && (bytes) > 0)                                                                             \
+            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
+                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
+    } while (0)
+    AUTOCORR_COPY(s->ac.d_origin, v->origin, n_series * sizeof(double));
+    AUTOCORR_COPY(s->ac.d_sum, v->sum, n_series * sizeof(double));
+    AUTOCORR_COPY(s->ac.d_lag, v->lag, n_series * L * sizeof(double));
+    AUTOCORR_COPY(s->ac.d_head, v->head, n_series * H * sizeof(double));
+    AUTOCORR_COPY(s->ac.d_tail, v->tail, n_series * H * sizeof(double));
+#undef AUTOCORR_COPY
+    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    if (v->n) {
+        if (up)
+            s->ac.n = *v->n;
+        else
+            *v->n = s->ac.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_autocorr_get(apemost_hip_sampler *s, const apemost_hip_autocorr_view *v) {
+    CHECK_S(s);
+    return autocorr_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_autocorr_set(apemost_hip_sampler *s, const apemost_hip_autocorr_view *v) {
+    CHECK_S(s);
+    return autocorr_xfer(s, v, true);
+}
+
+extern "C" int apemost_hip_autocorr_end(apemost_hip_sampler *s) {
+    CHECK_S(s);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    autocorr_free(s);
     return APEMOST_HIP_OK;
 }
 

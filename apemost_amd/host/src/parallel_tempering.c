@@ -12,6 +12,7 @@
 #include "parallel_tempering_config.h"
 #include "parallel_tempering_run.h"
 #include "apemost_bridge.h"
+#include "run_autocorr.h"
 #include "run_evidence.h"
 #include "run_joint.h"
 #include "run_peaks.h"
@@ -218,6 +219,11 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            the rectangle, trapezoid and variance-corrected trapezoid rules, the stepping stone in both directions and
  *            error bars (run_evidence.h).  Needs a bounded run and positive, strictly decreasing betas.  Combines with
  *            every other token and writes no sample file by itself, like joint
+ *   autocorr fold chain 0's parameters and its column prob - prior on the device into the lag sums of the lags
+ *            0 .. APEMOST_AUTOCORR_LAGS - 1 (default 1024, at most 4096; lags count kept samples); at the end write
+ *            autocorr.bin and autocorr.txt: mean, variance, integrated autocorrelation time (Sokal's window and
+ *            Geyer's initial positive sequence), effective sample size and standard error per column
+ *            (run_autocorr.h).  Combines with every other token and writes no sample file by itself, like evidence
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -235,7 +241,9 @@ typedef struct {
     int peaks;                /* <paramname>.peaks from the device (APEMOST_DUMP token `peaks`) */
     int joint;                /* joint.bin and the pair files from the device (APEMOST_DUMP token `joint`) */
     int evidence;             /* evidence.bin and evidence.txt from the device (APEMOST_DUMP token `evidence`) */
-    int files;                /* sample files are written (not so for `summary`, `peaks`, `joint` and `evidence` alone) */
+    int autocorr;             /* autocorr.bin and autocorr.txt from the device (APEMOST_DUMP token `autocorr`) */
+    int files;                /* sample files are written (not so for `summary`, `peaks`, `joint`, `evidence` and
+                                 `autocorr` alone) */
     unsigned int n_param_chains; /* chains 0..n-1 have parameter files (text) / carry their parameter vectors (binary) */
     double *pack;             /* binary: one batch, packed */
     size_t pack_capacity;
@@ -256,6 +264,7 @@ static void sink_parse(sample_sink *k) {
     k->peaks = 0;
     k->joint = 0;
     k->evidence = 0;
+    k->autocorr = 0;
     while (spec != NULL && *spec != 0) {
         if (strncmp(spec, "binary:all", 10) == 0)
             k->binary = 2, format_given = 1;
@@ -273,15 +282,17 @@ static void sink_parse(sample_sink *k) {
             k->joint = 1;
         else if (strncmp(spec, "evidence", 8) == 0 && (spec[8] == 0 || spec[8] == ','))
             k->evidence = 1;
+        else if (strncmp(spec, "autocorr", 8) == 0 && (spec[8] == 0 || spec[8] == ','))
+            k->autocorr = 1;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr; got '%s'\n", spec);
             exit(1);
         }
         spec = strchr(spec, ',');
         if (spec != NULL)
             spec++;
     }
-    k->files = !(k->summary || k->peaks || k->joint || k->evidence) || format_given;
+    k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr) || format_given;
 #ifdef HISTOGRAMS_MINMAX
     if (k->summary) {
         fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
@@ -597,6 +608,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     run_summary summary;
     run_joint joint;
     run_evidence evidence;
+    run_autocorr autocorr;
 
     if (max_rounds < 1)
         max_rounds = 1;
@@ -669,6 +681,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
                           planned_samples("evidence", "the batch size of the error estimate is fixed before the first sample",
                                           n_swap, iter, max_iterations, sink.thin),
                           sink.thin, mode[0] == 'a');
+    if (sink.autocorr) /* chain 0 lives on shard 0 */
+        run_autocorr_open(&autocorr, apemost_ladder_shard(l, 0), chains[0], sink.thin, mode[0] == 'a');
     for (i = 0; i < 2 && device_pack; i++)
         apemost_hip_or_die(apemost_hip_samples_alloc(apemost_ladder_shard(l, 0), max_rounds * n_swap, &d_packed[i]),
                            "samples_alloc");
@@ -731,6 +745,10 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             apemost_hip_or_die(apemost_hip_evidence_accumulate(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
                                                                (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
                                "evidence_accumulate");
+        if (sink.autocorr) /* chain 0's columns, on the same stream */
+            apemost_hip_or_die(apemost_hip_autocorr_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
+                                                               (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
+                               "autocorr_accumulate");
         /* no rows on the host (the text sink, or no sample files): only the counters and chain 0's latest point
          * cross (a packed read that keeps no step) */
         for (j = 0; j < n_shards && !device_pack && !rows_on_host; j++)
@@ -796,6 +814,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         run_joint_close(&joint, apemost_ladder_shard(l, 0), chains[0]);
     if (sink.evidence)
         run_evidence_close(&evidence, l, lo, n_shards);
+    if (sink.autocorr)
+        run_autocorr_close(&autocorr, apemost_ladder_shard(l, 0), chains[0]);
     for (i = 0; i < 2; i++)
         for (j = 0; j < n_shards; j++) {
             apemost_hip_samples_free(apemost_ladder_shard(l, j), d_samples[i][j]);

@@ -493,6 +493,43 @@ class HipSampler:
     def evidence_end(self):
         capi.check(self.L.apemost_hip_evidence_end(self._h))
 
+    # -- on-device autocorrelation (apemost_amd/autocorr.py) ----------------------------------------
+    def autocorr_begin(self, chains=(0,), max_lag=1024, cols=None, thin=1):
+        """start the lag sums of the columns `cols` (None: the parameters and prob - prior) of the local chains
+        `chains` (strictly increasing; b * chains_per_ladder is ladder b's chain 0) for the lags 0 .. max_lag - 1.
+        thin is recorded in the result: lags count kept samples."""
+        from .autocorr import default_cols
+        self._ac_chains = np.ascontiguousarray(chains, dtype=np.int32)
+        self._ac_cols = np.ascontiguousarray(default_cols(self.n_par) if cols is None else cols, dtype=np.int32)
+        assert self._ac_chains.ndim == 1 and self._ac_cols.ndim == 1
+        self._ac_lag, self._ac_thin = int(max_lag), int(thin)
+        ip = C.POINTER(C.c_int32)
+        cfg = capi.AutocorrConfig(n_keep=len(self._ac_chains), chains=self._ac_chains.ctypes.data_as(ip),
+                                  max_lag=self._ac_lag, n_cols=len(self._ac_cols),
+                                  cols=None if cols is None else self._ac_cols.ctypes.data_as(ip))
+        capi.check(self.L.apemost_hip_autocorr_begin(self._h, C.byref(cfg)))
+
+    def autocorr_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2] into the lag
+        sums; asynchronous (autocorr() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_autocorr_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def autocorr(self):
+        """the fold so far as an Autocorr object (synchronises with the accumulates issued so far)"""
+        from .autocorr import Autocorr
+        ac = Autocorr.empty(self._ac_chains, self._ac_lag, self.n_par, self._ac_cols, self._ac_thin, self.n_ladders)
+        capi.check(self.L.apemost_hip_autocorr_get(self._h, C.byref(ac.view())))
+        return ac
+
+    def autocorr_set(self, ac):
+        """load an Autocorr (a resumed run) into the fold begun with the same configuration"""
+        assert ac.lag.shape == (len(self._ac_chains), len(self._ac_cols), self._ac_lag)
+        assert np.array_equal(ac.chains, self._ac_chains) and np.array_equal(ac.cols, self._ac_cols)
+        capi.check(self.L.apemost_hip_autocorr_set(self._h, C.byref(ac.view())))
+
+    def autocorr_end(self):
+        capi.check(self.L.apemost_hip_autocorr_end(self._h))
+
     # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------
     def samples_text_bound(self, n_steps, skip=0, thin=1, n_param_chains=1):
         """(streams, host text bytes, device scratch bytes) of one samples_text batch"""

@@ -774,6 +774,65 @@ int apemost_hip_evidence_set(apemost_hip_sampler *s, const apemost_hip_evidence_
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_evidence_end(apemost_hip_sampler *s);
 
+/* ---- on-device autocorrelation: lag sums, integrated times, effective sample size ---------------
+ * How many independent samples a run holds: what the autocorrelation function of sample columns needs, accumulated
+ * from the sample rows while they are still on the device.  A series is one (kept chain, column) pair, series
+ * s = k * n_cols + c for kept chain k and listed column c; its samples are x_0, x_1, ... in kept order and
+ * d_t = x_t - origin.  With L = max_lag, per series:
+ *   n               kept samples so far, the same for every series;
+ *   origin[s]       x_0 of the first sample ever accumulated (0 before there is one);
+ *   sum[s]          the sequential sum of d_t;
+ *   lag[s][l]       for l = 0 .. L-1 the sequential sum, in ascending t, of d_t * d_{t-l} over the pairs with t >= l
+ *                   only (the product rounded to fp64 and then added);
+ *   head[s][j]      for j = 0 .. L-2: d_j, and 0 where j >= n;
+ *   tail[s][j]      for j = 0 .. L-2: d of sample n - (L-1) + j, and 0 where that index is negative.  It is the carry
+ *                   the fold needs across calls.
+ * Head and tail let the host remove the mean exactly: with m = sum / n,
+ *   acov_l = (lag_l - m (sum - sum_{j<l} head_j) - m (sum - sum of the last l tail entries) + (n - l) m^2) / n.
+ * Lags count kept samples: with thin they are in units of thin steps.
+ * No filter: a non-finite value makes the sums of its own series non-finite and changes no other series.
+ * Every quantity is one thread's chain of operations in sample order, its state carried in device memory between
+ * calls: all of them are bitwise equal to a sequential host loop whatever the boundaries of the accumulate calls are,
+ * pieces shorter than L-1 and the ramp-up while n < L included.
+ * Ladder batches: chains are local chain indices of the grid, ladder-major.  Sharded ladders: begin on the shard that
+ * holds the chain. */
+typedef struct {
+    int32_t n_keep;           /* 1 .. n_chains */
+    const int32_t *chains;    /* host [n_keep], local chain indices, strictly increasing */
+    int32_t max_lag;          /* L: 1 .. 4096 */
+    int32_t n_cols;           /* 1 .. n_par+2; ignored when cols is NULL */
+    const int32_t *cols;      /* host [n_cols], column indices in 0 .. n_par+1, strictly increasing; NULL: the n_par
+                                 parameters and column n_par+1 (prob - prior), n_par+1 columns */
+} apemost_hip_autocorr_config;
+typedef struct {
+    uint64_t *n;              /* kept samples */
+    double *origin, *sum;     /* [n_series] */
+    double *lag;              /* [n_series][L] */
+    double *head, *tail;      /* [n_series][L-1] */
+} apemost_hip_autocorr_view;  /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates and zeroes the accumulator, and device scratch for one staged piece: 2^20 / n_series kept steps, at least
+ * 256 and at most 65536, behind L-1 history slots per series.  A fold begun before is dropped once the new
+ * configuration has been accepted; a begin that is refused leaves it open and accumulating as it was.
+ * APEMOST_HIP_ERR_INVALID, before any device work, for a NULL config, n_keep or an index out of range, indices not
+ * strictly increasing, max_lag outside 1 .. 4096, more than 65535 series, or n_series * L above 2^24 lag sums
+ * (128 MiB). */
+int apemost_hip_autocorr_begin(apemost_hip_sampler *s, const apemost_hip_autocorr_config *cfg);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2], the rows of the
+ * launches issued so far) into the accumulator.  Asynchronous and queued like apemost_hip_summary_accumulate, on the
+ * stream of apemost_hip_samples_read_async: the round kernels never wait for it, and apemost_hip_samples_wait (or
+ * autocorr_get) must have returned before d_samples is written again.  APEMOST_HIP_ERR_INVALID, before any device
+ * work, without autocorr_begin or with thin == 0. */
+int apemost_hip_autocorr_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                    uint64_t thin);
+/* copies the accumulator out (synchronises with the accumulates issued so far) */
+int apemost_hip_autocorr_get(apemost_hip_sampler *s, const apemost_hip_autocorr_view *v);
+/* loads a view saved by autocorr_get into a fold begun with the same configuration (a resumed run); with n > 0 the
+ * next sample replaces neither the origin nor the head. */
+int apemost_hip_autocorr_set(apemost_hip_sampler *s, const apemost_hip_autocorr_view *v);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_autocorr_end(apemost_hip_sampler *s);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
