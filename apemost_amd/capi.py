@@ -101,6 +101,16 @@ class AutocorrView(C.Structure):
     _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("lag", _dp), ("head", _dp), ("tail", _dp)]
 
 
+class PredictConfig(C.Structure):
+    _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("n_x", C.c_int32), ("x", _dp),
+                ("nbins", C.c_int32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class PredictView(C.Structure):
+    _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("vmin", _dp), ("vmax", _dp), ("hist", _up),
+                ("best_prob", _dp), ("best_params", _dp), ("best_n", _up)]
+
+
 PEAKS_MAX = 99   # peaks described per column (include/apemost_hip.h)
 
 
@@ -140,6 +150,8 @@ EXPORTS = [
     "apemost_hip_evidence_set", "apemost_hip_evidence_end",
     "apemost_hip_autocorr_begin", "apemost_hip_autocorr_accumulate", "apemost_hip_autocorr_get",
     "apemost_hip_autocorr_set", "apemost_hip_autocorr_end",
+    "apemost_hip_predict_begin", "apemost_hip_predict_accumulate", "apemost_hip_predict_get",
+    "apemost_hip_predict_set", "apemost_hip_predict_end", "apemost_hip_predict_curve",
 ]
 
 _lib = None
@@ -266,6 +278,12 @@ def lib():
     L.apemost_hip_autocorr_get.argtypes = [vp, C.POINTER(AutocorrView)]
     L.apemost_hip_autocorr_set.argtypes = [vp, C.POINTER(AutocorrView)]
     L.apemost_hip_autocorr_end.argtypes = [vp]
+    L.apemost_hip_predict_begin.argtypes = [vp, C.POINTER(PredictConfig)]
+    L.apemost_hip_predict_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_predict_get.argtypes = [vp, C.POINTER(PredictView)]
+    L.apemost_hip_predict_set.argtypes = [vp, C.POINTER(PredictView)]
+    L.apemost_hip_predict_end.argtypes = [vp]
+    L.apemost_hip_predict_curve.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, _dp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

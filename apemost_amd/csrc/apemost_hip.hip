@@ -5,6 +5,7 @@
 #include "pt_joint.h"
 #include "pt_kernels.h"
 #include "pt_peaks.h"
+#include "pt_predict.h"
 #include "pt_summary.h"
 #include "pt_text.h"
 
@@ -389,6 +390,17 @@ struct apemost_hip_sampler {
         int *d_chains, *d_cols;
         double *d_buf, *d_origin, *d_sum, *d_lag, *d_head, *d_tail;
     } ac;
+    // on-device posterior predictive (apemost_hip_predict_begin .. end): the model curve of kept chains' samples at
+    // n_x abscissae, on copy_stream
+    struct {
+        bool open;
+        int n_keep, n_x, nbins, points;
+        double lo, hi;
+        u64 n; // kept samples so far (the host knows it without a sync)
+        int *d_chains;
+        double *d_x, *d_origin, *d_sum, *d_sq, *d_vmin, *d_vmax, *d_best_prob, *d_best_params;
+        u64 *d_hist, *d_best_n;
+    } pr;
 };
 
 extern "C" const char *apemost_hip_last_error(void) { return g_last_error.c_str(); }
@@ -535,6 +547,15 @@ static void autocorr_free(apemost_hip_sampler *s) {
     s->ac = {};
 }
 
+static void predict_free(apemost_hip_sampler *s) {
+    for (void *p : {(void *)s->pr.d_chains, (void *)s->pr.d_x, (void *)s->pr.d_origin, (void *)s->pr.d_sum,
+                    (void *)s->pr.d_sq, (void *)s->pr.d_vmin, (void *)s->pr.d_vmax, (void *)s->pr.d_best_prob,
+                    (void *)s->pr.d_best_params, (void *)s->pr.d_hist, (void *)s->pr.d_best_n})
+        if (p)
+            hipFree(p);
+    s->pr = {};
+}
+
 // everything a sampler owns on the device; safe on a half-built sampler
 static void release(apemost_hip_sampler *s) {
     if (s->stream)
@@ -566,6 +587,7 @@ static void release(apemost_hip_sampler *s) {
     joint_free(s);
     evidence_free(s);
     autocorr_free(s);
+    predict_free(s);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {
@@ -2859,6 +2881,274 @@ extern "C" int apemost_hip_autocorr_end(apemost_hip_sampler *s) {
     if (s->copy_stream)
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     autocorr_free(s);
+    return APEMOST_HIP_OK;
+}
+
+// ---- on-device posterior predictive (pt_predict.h) ----
+#define PREDICT_BUILTIN(s, what)                                                                                \
+    do {                                                                                                        \
+        if ((s)->cfg.model == APEMOST_MODEL_USER)                                                               \
+            return fail(APEMOST_HIP_ERR_UNSUPPORTED, what ": a user-supplied device model has no curve");       \
+    } while (0)
+
+static void predict_launch_fold(apemost_hip_sampler *s, const PredictArgs &a) {
+    const dim3 grid((unsigned)(a.n_blocks + 1) * (unsigned)a.n_keep), block(kPredictWave);
+    const size_t lds = predict_lds_bytes(a.nbins, a.points);
+#define PREDICT_FOLD(M)                                                                                          \
+    do {                                                                                                         \
+        if (a.nbins > 0)                                                                                         \
+            hipLaunchKernelGGL((predict_fold_kernel<M, true>), grid, block, lds, s->copy_stream, a);            \
+        else                                                                                                     \
+            hipLaunchKernelGGL((predict_fold_kernel<M, false>), grid, block, 0, s->copy_stream, a);             \
+    } while (0)
+    switch (s->cfg.model) {
+    case APEMOST_MODEL_SIMPLESIN: PREDICT_FOLD(APEMOST_MODEL_SIMPLESIN); break;
+    case APEMOST_MODEL_SINE3: PREDICT_FOLD(APEMOST_MODEL_SINE3); break;
+    case APEMOST_MODEL_PULSE: PREDICT_FOLD(APEMOST_MODEL_PULSE); break;
+    default: PREDICT_FOLD(APEMOST_MODEL_PULSE_VROT); break;
+    }
+#undef PREDICT_FOLD
+}
+
+extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_hip_predict_config *cfg) {
+    CHECK_S(s);
+    PREDICT_BUILTIN(s, "predict_begin");
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: config is NULL");
+    const int np = s->cfg.n_par;
+    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
+                    s->cfg.n_chains);
+    for (int k = 0; k < cfg->n_keep; k++)
+        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
+            return fail(APEMOST_HIP_ERR_INVALID,
+                        "predict_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing", k,
+                        cfg->chains[k], s->cfg.n_chains);
+    const int n_x = cfg->x ? cfg->n_x : s->cfg.n_data;
+    if (n_x < 1)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: n_x %d < 1", n_x);
+    if (cfg->x)
+        for (int i = 0; i < n_x; i++)
+            if (!std::isfinite(cfg->x[i]))
+                return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: x[%d] is not finite", i);
+    if (cfg->nbins < 0 || cfg->nbins > kPredictMaxBins)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: nbins %d outside [0,%d]", cfg->nbins, kPredictMaxBins);
+    if (cfg->nbins > 0 && !(std::isfinite(cfg->lo) && std::isfinite(cfg->hi) && cfg->lo < cfg->hi))
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: the histogram range [%g, %g] is not finite with lo < hi",
+                    cfg->lo, cfg->hi);
+    const u64 n_series = (u64)cfg->n_keep * (u64)n_x;
+    if (n_series > ((u64)1 << 20) || n_series * (u64)cfg->nbins > ((u64)1 << 26))
+        return fail(APEMOST_HIP_ERR_INVALID,
+                    "predict_begin: %d chains x %d abscissae x %d bins: more than 2^20 series or 2^26 counts", cfg->n_keep,
+                    n_x, cfg->nbins);
+    if (np > kPredictTile)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: %d parameters, more than %d", np, kPredictTile);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a fold begun before may still be accumulating
+    predict_free(s);
+    s->pr.n_keep = cfg->n_keep;
+    s->pr.n_x = n_x;
+    s->pr.nbins = cfg->nbins;
+    s->pr.points = predict_points(cfg->nbins);
+    s->pr.lo = cfg->lo;
+    s->pr.hi = cfg->hi;
+    s->pr.n = 0;
+    const size_t ns = (size_t)n_series, nk = (size_t)cfg->n_keep, nh = ns * (size_t)cfg->nbins;
+    HIP_TRY(hipMalloc((void **)&s->pr.d_chains, nk * sizeof(int)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_x, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_origin, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_sum, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_sq, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_vmin, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_vmax, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_hist, (nh ? nh : 1) * sizeof(u64)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_best_prob, nk * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_best_params, nk * np * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_best_n, nk * sizeof(u64)));
+    HIP_TRY(hipMemsetAsync(s->pr.d_origin, 0, ns * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->pr.d_sum, 0, ns * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->pr.d_sq, 0, ns * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->pr.d_hist, 0, (nh ? nh : 1) * sizeof(u64), s->stream));
+    HIP_TRY(hipMemsetAsync(s->pr.d_best_params, 0, nk * np * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->pr.d_best_n, 0, nk * sizeof(u64), s->stream));
+    std::vector<double> pinf(ns, INFINITY), ninf(ns, -INFINITY);
+    HIP_TRY(hipMemcpyAsync(s->pr.d_vmin, pinf.data(), ns * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->pr.d_vmax, ninf.data(), ns * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->pr.d_best_prob, ninf.data(), nk * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->pr.d_chains, cfg->chains, nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    for (int k = 0; k < cfg->n_keep; k++) {
+        double *dst = s->pr.d_x + (size_t)k * n_x;
+        if (cfg->x) {
+            HIP_TRY(hipMemcpyAsync(dst, cfg->x, (size_t)n_x * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        } else { // column 0 of the kept chain's own ladder (the data is stored by columns, ladder after ladder)
+            const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
+            const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * s->cfg.n_data;
+            HIP_TRY(hipMemcpyAsync(dst, col0, (size_t)n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's arrays are read until here)
+    s->pr.open = true;
+    return APEMOST_HIP_OK;
+}
+
+// Queued on copy_stream behind everything launched so far on the sampler's stream, like
+// apemost_hip_autocorr_accumulate; apemost_hip_samples_wait covers it.
+extern "C" int apemost_hip_predict_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                              uint64_t skip, uint64_t thin) {
+    CHECK_S(s);
+    PREDICT_BUILTIN(s, "predict_accumulate");
+    if (!s->pr.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_accumulate: no predict_begin");
+    if (thin < 1 || (!d_samples && n_steps > 0))
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_accumulate: bad arguments");
+    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    if (kept == 0)
+        return APEMOST_HIP_OK;
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    for (u64 k0 = 0; k0 < kept; k0 += kPredictPiece) {
+        PredictArgs a;
+        a.rows = d_samples;
+        a.n_chains = s->cfg.n_chains;
+        a.n_par = s->cfg.n_par;
+        a.n_keep = s->pr.n_keep;
+        a.chains = s->pr.d_chains;
+        a.skip = skip + k0 * thin;
+        a.thin = thin;
+        a.n = (unsigned int)(kept - k0 < (u64)kPredictPiece ? kept - k0 : (u64)kPredictPiece);
+        a.n0 = s->pr.n;
+        a.n_x = s->pr.n_x;
+        a.x = s->pr.d_x;
+        a.nbins = s->pr.nbins;
+        a.points = s->pr.points;
+        a.n_blocks = (s->pr.n_x + s->pr.points - 1) / s->pr.points;
+        a.lo = s->pr.lo;
+        a.hi = s->pr.hi;
+        a.origin = s->pr.d_origin;
+        a.sum = s->pr.d_sum;
+        a.sq = s->pr.d_sq;
+        a.vmin = s->pr.d_vmin;
+        a.vmax = s->pr.d_vmax;
+        a.hist = s->pr.d_hist;
+        a.best_prob = s->pr.d_best_prob;
+        a.best_params = s->pr.d_best_params;
+        a.best_n = s->pr.d_best_n;
+        predict_launch_fold(s, a);
+        HIP_TRY(hipGetLastError());
+        s->pr.n += a.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+static int predict_xfer(apemost_hip_sampler *s, const apemost_hip_predict_view *v, bool up) {
+    if (!s->pr.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_%s: no predict_begin", up ? "set" : "get");
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict view is NULL");
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const size_t nk = (size_t)s->pr.n_keep, ns = nk * s->pr.n_x, np = (size_t)s->cfg.n_par;
+    // stream order: behind every accumulate queued so far, on the stream they run on
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+#define PREDICT_COPY(dev, host, bytes)                                                                         \
+    do {                                                                                                       \
+        if ((host) && (bytes) > 0)                                                                             \
+            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
+                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
+    } while (0)
+    PREDICT_COPY(s->pr.d_origin, v->origin, ns * sizeof(double));
+    PREDICT_COPY(s->pr.d_sum, v->sum, ns * sizeof(double));
+    PREDICT_COPY(s->pr.d_sq, v->sq, ns * sizeof(double));
+    PREDICT_COPY(s->pr.d_vmin, v->vmin, ns * sizeof(double));
+    PREDICT_COPY(s->pr.d_vmax, v->vmax, ns * sizeof(double));
+    PREDICT_COPY(s->pr.d_hist, v->hist, ns * s->pr.nbins * sizeof(u64));
+    PREDICT_COPY(s->pr.d_best_prob, v->best_prob, nk * sizeof(double));
+    PREDICT_COPY(s->pr.d_best_params, v->best_params, nk * np * sizeof(double));
+    PREDICT_COPY(s->pr.d_best_n, v->best_n, nk * sizeof(u64));
+#undef PREDICT_COPY
+    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    if (v->n) {
+        if (up)
+            s->pr.n = *v->n;
+        else
+            *v->n = s->pr.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_predict_get(apemost_hip_sampler *s, const apemost_hip_predict_view *v) {
+    CHECK_S(s);
+    PREDICT_BUILTIN(s, "predict_get");
+    return predict_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_predict_set(apemost_hip_sampler *s, const apemost_hip_predict_view *v) {
+    CHECK_S(s);
+    PREDICT_BUILTIN(s, "predict_set");
+    return predict_xfer(s, v, true);
+}
+
+extern "C" int apemost_hip_predict_end(apemost_hip_sampler *s) {
+    CHECK_S(s);
+    PREDICT_BUILTIN(s, "predict_end");
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    predict_free(s);
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x,
+                                         const double *x, double *out) {
+    CHECK_S(s);
+    PREDICT_BUILTIN(s, "predict_curve");
+    if (!x)
+        n_x = s->cfg.n_data;
+    if (n < 1 || !params || !out || n_x < 1 || (u64)n * (u64)n_x > ((u64)1 << 26))
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_curve: %d rows x %d abscissae, or a NULL array", n, n_x);
+    const int np = s->cfg.n_par;
+    double *d_par = nullptr, *d_x = nullptr, *d_out = nullptr;
+    hipError_t err = hipMalloc((void **)&d_par, (size_t)n * np * sizeof(double));
+    if (err == hipSuccess)
+        err = hipMalloc((void **)&d_x, (size_t)n_x * sizeof(double));
+    if (err == hipSuccess)
+        err = hipMalloc((void **)&d_out, (size_t)n * n_x * sizeof(double));
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(d_par, params, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, s->stream);
+    if (err == hipSuccess)
+        err = x ? hipMemcpyAsync(d_x, x, (size_t)n_x * sizeof(double), hipMemcpyHostToDevice, s->stream)
+                : hipMemcpyAsync(d_x, s->d.data, (size_t)n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream);
+    if (err == hipSuccess) {
+        const dim3 grid((unsigned)((n_x + kPredictWave - 1) / kPredictWave) * (unsigned)n), block(kPredictWave);
+        switch (s->cfg.model) {
+        case APEMOST_MODEL_SIMPLESIN:
+            hipLaunchKernelGGL(predict_curve_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->stream, d_par, np, n_x, d_x, d_out);
+            break;
+        case APEMOST_MODEL_SINE3:
+            hipLaunchKernelGGL(predict_curve_kernel<APEMOST_MODEL_SINE3>, grid, block, 0, s->stream, d_par, np, n_x, d_x, d_out);
+            break;
+        case APEMOST_MODEL_PULSE:
+            hipLaunchKernelGGL(predict_curve_kernel<APEMOST_MODEL_PULSE>, grid, block, 0, s->stream, d_par, np, n_x, d_x, d_out);
+            break;
+        default:
+            hipLaunchKernelGGL(predict_curve_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->stream, d_par, np, n_x, d_x, d_out);
+            break;
+        }
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(out, d_out, (size_t)n * n_x * sizeof(double), hipMemcpyDeviceToHost, s->stream);
+    const hipError_t sync = hipStreamSynchronize(s->stream);
+    for (double *p : {d_par, d_x, d_out})
+        if (p)
+            hipFree(p);
+    HIP_TRY(err);
+    HIP_TRY(sync);
     return APEMOST_HIP_OK;
 }
 

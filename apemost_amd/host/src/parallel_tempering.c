@@ -13,6 +13,7 @@
 #include "parallel_tempering_run.h"
 #include "apemost_bridge.h"
 #include "run_autocorr.h"
+#include "run_predict.h"
 #include "run_evidence.h"
 #include "run_joint.h"
 #include "run_peaks.h"
@@ -224,6 +225,12 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            autocorr.bin and autocorr.txt: mean, variance, integrated autocorrelation time (Sokal's window and
  *            Geyer's initial positive sequence), effective sample size and standard error per column
  *            (run_autocorr.h).  Combines with every other token and writes no sample file by itself, like evidence
+ *   predict  fold the model curve of chain 0's kept samples over the data's own abscissae on the device: at the end
+ *            write predict.bin and predict.txt, one line per data point with x, the data, the curve's mean and
+ *            standard deviation, the residual, the curve's minimum and maximum and the best-fit curve; with
+ *            APEMOST_PREDICT_BINS=N and APEMOST_PREDICT_RANGE=lo:hi both set also the median and the 68 % band
+ *            (run_predict.h).  Needs a bounded run and a built-in model.  Combines with every other token and writes
+ *            no sample file by itself, like autocorr
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -242,8 +249,9 @@ typedef struct {
     int joint;                /* joint.bin and the pair files from the device (APEMOST_DUMP token `joint`) */
     int evidence;             /* evidence.bin and evidence.txt from the device (APEMOST_DUMP token `evidence`) */
     int autocorr;             /* autocorr.bin and autocorr.txt from the device (APEMOST_DUMP token `autocorr`) */
-    int files;                /* sample files are written (not so for `summary`, `peaks`, `joint`, `evidence` and
-                                 `autocorr` alone) */
+    int predict;              /* predict.bin and predict.txt from the device (APEMOST_DUMP token `predict`) */
+    int files;                /* sample files are written (not so for `summary`, `peaks`, `joint`, `evidence`, `autocorr`
+                                 and `predict` alone) */
     unsigned int n_param_chains; /* chains 0..n-1 have parameter files (text) / carry their parameter vectors (binary) */
     double *pack;             /* binary: one batch, packed */
     size_t pack_capacity;
@@ -265,6 +273,7 @@ static void sink_parse(sample_sink *k) {
     k->joint = 0;
     k->evidence = 0;
     k->autocorr = 0;
+    k->predict = 0;
     while (spec != NULL && *spec != 0) {
         if (strncmp(spec, "binary:all", 10) == 0)
             k->binary = 2, format_given = 1;
@@ -284,15 +293,17 @@ static void sink_parse(sample_sink *k) {
             k->evidence = 1;
         else if (strncmp(spec, "autocorr", 8) == 0 && (spec[8] == 0 || spec[8] == ','))
             k->autocorr = 1;
+        else if (strncmp(spec, "predict", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
+            k->predict = 1;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict; got '%s'\n", spec);
             exit(1);
         }
         spec = strchr(spec, ',');
         if (spec != NULL)
             spec++;
     }
-    k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr) || format_given;
+    k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr || k->predict) || format_given;
 #ifdef HISTOGRAMS_MINMAX
     if (k->summary) {
         fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
@@ -609,6 +620,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     run_joint joint;
     run_evidence evidence;
     run_autocorr autocorr;
+    run_predict predict;
 
     if (max_rounds < 1)
         max_rounds = 1;
@@ -683,6 +695,12 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
                           sink.thin, mode[0] == 'a');
     if (sink.autocorr) /* chain 0 lives on shard 0 */
         run_autocorr_open(&autocorr, apemost_ladder_shard(l, 0), chains[0], sink.thin, mode[0] == 'a');
+    if (sink.predict) { /* chain 0 lives on shard 0 */
+        (void)planned_samples("predict", "predict.bin and predict.txt are written when the run ends", n_swap, iter,
+                              max_iterations, sink.thin);
+        run_predict_open(&predict, apemost_ladder_shard(l, 0), chains[0], apemost_ladder_model(l), sink.thin,
+                         mode[0] == 'a');
+    }
     for (i = 0; i < 2 && device_pack; i++)
         apemost_hip_or_die(apemost_hip_samples_alloc(apemost_ladder_shard(l, 0), max_rounds * n_swap, &d_packed[i]),
                            "samples_alloc");
@@ -749,6 +767,10 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             apemost_hip_or_die(apemost_hip_autocorr_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
                                                                (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
                                "autocorr_accumulate");
+        if (sink.predict) /* chain 0's model curve, on the same stream */
+            apemost_hip_or_die(apemost_hip_predict_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
+                                                              (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
+                               "predict_accumulate");
         /* no rows on the host (the text sink, or no sample files): only the counters and chain 0's latest point
          * cross (a packed read that keeps no step) */
         for (j = 0; j < n_shards && !device_pack && !rows_on_host; j++)
@@ -816,6 +838,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         run_evidence_close(&evidence, l, lo, n_shards);
     if (sink.autocorr)
         run_autocorr_close(&autocorr, apemost_ladder_shard(l, 0), chains[0]);
+    if (sink.predict)
+        run_predict_close(&predict, apemost_ladder_shard(l, 0), chains[0]);
     for (i = 0; i < 2; i++)
         for (j = 0; j < n_shards; j++) {
             apemost_hip_samples_free(apemost_ladder_shard(l, j), d_samples[i][j]);

@@ -98,6 +98,7 @@ class HipSampler:
         self.chain_offset = chain_offset
         self.seed = seed
         self.n_ladders, self.chains_per_ladder, self.seeds = 1, n_chains, [seed]
+        self._x0 = [data[:, 0].copy()]
 
     def _init_batch(self, model, n_par, n_chains, data, seeds, device, chain_offset, n_chains_global, waves_per_chain,
                     sigma, hmin, lds_policy, circular_params, flags, adapt_target, device_model_source):
@@ -120,6 +121,7 @@ class HipSampler:
         self.chain_offset = 0
         self.seed = seeds[0]
         self.n_ladders, self.chains_per_ladder, self.seeds = n_ladders, n_chains, seeds
+        self._x0 = [None] * n_ladders
         if data.ndim == 2:
             self.set_data(data)
         else:
@@ -141,6 +143,8 @@ class HipSampler:
             capi.check(self.L.apemost_hip_set_data(self._h, p))
         else:
             capi.check(self.L.apemost_hip_set_data_ladder(self._h, int(ladder), p))
+        for b in range(self.n_ladders) if ladder is None else [int(ladder)]:
+            self._x0[b] = data[:, 0].copy()   # the abscissae: what predict_begin(x=None) folds over
 
     def ladder_view(self, arr, b):
         """ladder b's part of a ladder-major array or of sample rows of this sampler (module-level ladder_view)"""
@@ -529,6 +533,68 @@ class HipSampler:
 
     def autocorr_end(self):
         capi.check(self.L.apemost_hip_autocorr_end(self._h))
+
+    # -- on-device posterior predictive (apemost_amd/predict.py) ------------------------------------
+    def predict_begin(self, chains=(0,), x=None, nbins=0, lo=None, hi=None, thin=1):
+        """start the fold of the model curve at the abscissae x (None: column 0 of the data, for every kept chain that
+        of its own ladder) over the kept samples of the local chains `chains` (strictly increasing).  nbins > 0 adds a
+        histogram of the curve's values over [lo, hi] at every abscissa: medians and credible bands.  thin is recorded
+        in the result."""
+        self._pr_chains = np.ascontiguousarray(chains, dtype=np.int32)
+        assert self._pr_chains.ndim == 1
+        self._pr_nbins, self._pr_thin = int(nbins), int(thin)
+        self._pr_lo, self._pr_hi = (0.0, 0.0) if nbins == 0 else (float(lo), float(hi))
+        if x is None:
+            xs = [self._x0[int(c) // self.chains_per_ladder if self.n_ladders > 1 else 0]
+                  for c in self._pr_chains.tolist() if 0 <= c < self.n_chains]
+            xs = xs if len(xs) == len(self._pr_chains) else [self._x0[0]] * len(self._pr_chains)
+            self._pr_x = np.array(xs, dtype=np.float64).reshape(len(self._pr_chains), -1)
+            xp, n_x = None, 0
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            self._pr_x = np.tile(x, (len(self._pr_chains), 1))
+            xp, n_x = x.ctypes.data_as(capi._dp), len(x)
+        cfg = capi.PredictConfig(n_keep=len(self._pr_chains), chains=self._pr_chains.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 n_x=n_x, x=xp, nbins=self._pr_nbins, lo=self._pr_lo, hi=self._pr_hi)
+        capi.check(self.L.apemost_hip_predict_begin(self._h, C.byref(cfg)))
+
+    def predict_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]; asynchronous
+        (predict() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_predict_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def predict(self):
+        """the fold so far as a Predict object (synchronises with the accumulates issued so far)"""
+        from .predict import Predict
+        pr = Predict.empty(self._pr_chains, self._pr_x, self.n_par, self.cfg.model, self._pr_nbins, self._pr_lo,
+                           self._pr_hi, self._pr_thin, self.n_ladders)
+        capi.check(self.L.apemost_hip_predict_get(self._h, C.byref(pr.view())))
+        return pr
+
+    def predict_set(self, pr):
+        """load a Predict (a resumed run) into the fold begun with the same configuration"""
+        assert pr.hist.shape == self._pr_x.shape + (self._pr_nbins,) and pr.n_par == self.n_par
+        assert np.array_equal(pr.chains, self._pr_chains)
+        capi.check(self.L.apemost_hip_predict_set(self._h, C.byref(pr.view())))
+
+    def predict_end(self):
+        capi.check(self.L.apemost_hip_predict_end(self._h))
+
+    def predict_curve(self, params, x=None):
+        """the model curve [n][n_x] of the parameter rows params [n][n_par] (or one row) at x (None: column 0 of the
+        data, of ladder 0 in a batch), evaluated on the device by the fold's own curve function"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        one = params.ndim == 1
+        params = params.reshape(-1, self.n_par)
+        if x is None:
+            xp, n_x = None, self.cfg.n_data
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            xp, n_x = x.ctypes.data_as(capi._dp), len(x)
+        out = np.zeros((len(params), n_x))
+        capi.check(self.L.apemost_hip_predict_curve(self._h, len(params), params.ctypes.data_as(capi._dp), n_x, xp,
+                                                    out.ctypes.data_as(capi._dp)))
+        return out[0] if one else out
 
     # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------
     def samples_text_bound(self, n_steps, skip=0, thin=1, n_param_chains=1):

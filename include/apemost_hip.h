@@ -833,6 +833,72 @@ int apemost_hip_autocorr_set(apemost_hip_sampler *s, const apemost_hip_autocorr_
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_autocorr_end(apemost_hip_sampler *s);
 
+/* ---- on-device posterior predictive: the model curve's mean, bands and best fit ------------------
+ * The fitted model itself: the curve of the built-in likelihood (simplesin and sine3: m(x); pulse and pulse_vrot: the
+ * Lorentzian sum y(nu); the operation order is specified at the head of apemost_amd/csrc/pt_predict.h) evaluated at
+ * n_x abscissae for every kept sample of the kept chains, while the sample rows are still on the device.  A series is
+ * one (kept chain k, abscissa i) pair, series s = k * n_x + i, with the samples v_t = curve(parameters of kept sample
+ * t of chain k, x_i).  Per series:
+ *   n               kept samples so far, the same for every series;
+ *   origin[s]       v_0 of the first sample ever accumulated (0 before there is one);
+ *   sum[s], sq[s]   with d = v - origin the sequential sums of d and of d * d (the product rounded to fp64, then added);
+ *   vmin[s], vmax[s]  from +inf and -inf by strict < and >: a NaN never enters;
+ *   hist[s][b]      nbins counts over one range [lo, hi] shared by all series, on the run summary's edges (GSL's uniform
+ *                   edges, the top one widened by (hi-lo)/10000, bin b = [e[b], e[b+1]), found by bisection); values
+ *                   outside the range and NaN are not counted.  Medians and credible bands come from these counts.
+ * and per kept chain the best sample:
+ *   best_prob[k]    the largest column n_par (prob) over the kept samples, from -inf by strict >: the first occurrence
+ *                   wins, a NaN (or -inf) never does;
+ *   best_params[k][n_par]  the parameter row of that sample;  best_n[k]  its 1-based kept index, 0 before there is one.
+ * No filter: a non-finite parameter makes the sums of its own chain's series non-finite and changes nothing else.
+ * Every quantity is one thread's chain of operations in sample order, its state carried in device memory between
+ * calls: all of them are bitwise equal to a sequential host loop whatever the boundaries of the accumulate calls are.
+ * Ladder batches: chains are local chain indices of the grid, ladder-major; with x = NULL a kept chain takes the data
+ * of its own ladder.  Sharded ladders: begin on the shard that holds the chain.
+ * APEMOST_MODEL_USER has no curve (a device model supplies term() only): every apemost_hip_predict_* entry point
+ * returns APEMOST_HIP_ERR_UNSUPPORTED for such a sampler. */
+typedef struct {
+    int32_t n_keep;           /* 1 .. n_chains */
+    const int32_t *chains;    /* host [n_keep], local chain indices, strictly increasing */
+    int32_t n_x;              /* >= 1; ignored when x is NULL */
+    const double *x;          /* host [n_x], finite; NULL: column 0 of the sampler's data as it is at begin, n_x = n_data */
+    int32_t nbins;            /* 0: no histograms; else 1 .. 4096 */
+    double lo, hi;            /* the histograms' range: finite, lo < hi (ignored when nbins is 0) */
+} apemost_hip_predict_config;
+typedef struct {
+    uint64_t *n;              /* kept samples */
+    double *origin, *sum, *sq, *vmin, *vmax; /* [n_keep][n_x] */
+    uint64_t *hist;           /* [n_keep][n_x][nbins] */
+    double *best_prob;        /* [n_keep] */
+    double *best_params;      /* [n_keep][n_par] */
+    uint64_t *best_n;         /* [n_keep] */
+} apemost_hip_predict_view;   /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates and initialises the accumulator.  A fold begun before is dropped once the new configuration has been
+ * accepted; a begin that is refused leaves it open and accumulating as it was.  APEMOST_HIP_ERR_INVALID, before any
+ * device work, for a NULL config, n_keep or an index out of range, indices not strictly increasing, n_x < 1, a
+ * non-finite x, nbins outside 0 .. 4096, a range that is not finite with lo < hi, n_keep * n_x above 2^20 series, or
+ * n_keep * n_x * nbins above 2^26 counts (512 MiB). */
+int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_hip_predict_config *cfg);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2], the rows of the
+ * launches issued so far) into the accumulator, in launches of at most 8192 kept steps.  Asynchronous and queued like
+ * apemost_hip_autocorr_accumulate, on the stream of apemost_hip_samples_read_async.  APEMOST_HIP_ERR_INVALID, before
+ * any device work, without predict_begin or with thin == 0. */
+int apemost_hip_predict_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                   uint64_t thin);
+/* copies the accumulator out (synchronises with the accumulates issued so far) */
+int apemost_hip_predict_get(apemost_hip_sampler *s, const apemost_hip_predict_view *v);
+/* loads a view saved by predict_get into a fold begun with the same configuration (a resumed run); with n > 0 the
+ * next sample replaces neither the origins nor the best sample (unless its prob is larger) */
+int apemost_hip_predict_set(apemost_hip_sampler *s, const apemost_hip_predict_view *v);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_predict_end(apemost_hip_sampler *s);
+/* out[r][i] = the same curve for the caller's parameter rows: params host [n][n_par], x host [n_x] (NULL: column 0 of
+ * the sampler's data -- of ladder 0 in a batch --, n_x = n_data), out host [n][n_x].  Synchronous; needs no
+ * predict_begin.  APEMOST_HIP_ERR_INVALID for n < 1, NULL params or out, n_x < 1 or n * n_x above 2^26. */
+int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x, const double *x,
+                              double *out);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
