@@ -111,6 +111,15 @@ class PredictView(C.Structure):
                 ("best_prob", _dp), ("best_params", _dp), ("best_n", _up)]
 
 
+class PointwiseConfig(C.Structure):
+    _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32))]
+
+
+class PointwiseView(C.Structure):
+    _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("m_up", _dp), ("S_up", _dp), ("m_dn", _dp),
+                ("S_dn", _dp), ("S2_dn", _dp), ("par_origin", _dp), ("par_sum", _dp)]
+
+
 PEAKS_MAX = 99   # peaks described per column (include/apemost_hip.h)
 
 
@@ -152,6 +161,9 @@ EXPORTS = [
     "apemost_hip_autocorr_set", "apemost_hip_autocorr_end",
     "apemost_hip_predict_begin", "apemost_hip_predict_accumulate", "apemost_hip_predict_get",
     "apemost_hip_predict_set", "apemost_hip_predict_end", "apemost_hip_predict_curve",
+    "apemost_hip_pointwise_begin", "apemost_hip_pointwise_accumulate", "apemost_hip_pointwise_get",
+    "apemost_hip_pointwise_set", "apemost_hip_pointwise_end", "apemost_hip_pointwise_loglike",
+    "apemost_hip_pointwise_loglike_ladder",
 ]
 
 _lib = None
@@ -284,6 +296,13 @@ def lib():
     L.apemost_hip_predict_set.argtypes = [vp, C.POINTER(PredictView)]
     L.apemost_hip_predict_end.argtypes = [vp]
     L.apemost_hip_predict_curve.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, _dp]
+    L.apemost_hip_pointwise_begin.argtypes = [vp, C.POINTER(PointwiseConfig)]
+    L.apemost_hip_pointwise_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_pointwise_get.argtypes = [vp, C.POINTER(PointwiseView)]
+    L.apemost_hip_pointwise_set.argtypes = [vp, C.POINTER(PointwiseView)]
+    L.apemost_hip_pointwise_end.argtypes = [vp]
+    L.apemost_hip_pointwise_loglike.argtypes = [vp, C.c_int32, _dp, _dp]
+    L.apemost_hip_pointwise_loglike_ladder.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

@@ -5,6 +5,7 @@
 #include "pt_joint.h"
 #include "pt_kernels.h"
 #include "pt_peaks.h"
+#include "pt_pointwise.h"
 #include "pt_predict.h"
 #include "pt_summary.h"
 #include "pt_text.h"
@@ -401,6 +402,18 @@ struct apemost_hip_sampler {
         double *d_x, *d_origin, *d_sum, *d_sq, *d_vmin, *d_vmax, *d_best_prob, *d_best_params;
         u64 *d_hist, *d_best_n;
     } pr;
+    // on-device pointwise log-likelihood (apemost_hip_pointwise_begin .. end): the term of every datum under the kept
+    // chains' samples, on copy_stream
+    struct {
+        bool open;
+        int n_keep;
+        double c; // 1 / (-2 sigma^2)
+        u64 n;    // kept samples so far (the host knows it without a sync)
+        int *d_chains;
+        double *d_x, *d_y;    // [n_keep][n_data]
+        double *d_state;      // the eight [n_keep][n_data] words, one after the other (kPointwiseWords)
+        double *d_par;        // par_origin, par_sum: [n_keep][n_par] each
+    } pw;
 };
 
 extern "C" const char *apemost_hip_last_error(void) { return g_last_error.c_str(); }
@@ -556,6 +569,14 @@ static void predict_free(apemost_hip_sampler *s) {
     s->pr = {};
 }
 
+static void pointwise_free(apemost_hip_sampler *s) {
+    for (void *p : {(void *)s->pw.d_chains, (void *)s->pw.d_x, (void *)s->pw.d_y, (void *)s->pw.d_state,
+                    (void *)s->pw.d_par})
+        if (p)
+            hipFree(p);
+    s->pw = {};
+}
+
 // everything a sampler owns on the device; safe on a half-built sampler
 static void release(apemost_hip_sampler *s) {
     if (s->stream)
@@ -588,6 +609,7 @@ static void release(apemost_hip_sampler *s) {
     evidence_free(s);
     autocorr_free(s);
     predict_free(s);
+    pointwise_free(s);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {
@@ -3150,6 +3172,245 @@ extern "C" int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, cons
     HIP_TRY(err);
     HIP_TRY(sync);
     return APEMOST_HIP_OK;
+}
+
+// ---- on-device pointwise log-likelihood (pt_pointwise.h) ----
+#define POINTWISE_BUILTIN(s, what)                                                                              \
+    do {                                                                                                        \
+        if ((s)->cfg.model == APEMOST_MODEL_USER)                                                               \
+            return fail(APEMOST_HIP_ERR_UNSUPPORTED, what ": a user-supplied device model has no datum's term"); \
+    } while (0)
+
+constexpr int kPointwiseWords = 8; // origin, sum, sq, m_up, S_up, m_dn, S_dn, S2_dn
+
+static double pointwise_c(const apemost_hip_sampler *s) {
+    const double sigma = s->sh.consts.sigma;
+    const double t = -2.0 * sigma;
+    const double denom = t * sigma;
+    return 1.0 / denom;
+}
+
+extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg) {
+    CHECK_S(s);
+    POINTWISE_BUILTIN(s, "pointwise_begin");
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: config is NULL");
+    const int np = s->cfg.n_par, nd = s->cfg.n_data;
+    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
+                    s->cfg.n_chains);
+    for (int k = 0; k < cfg->n_keep; k++)
+        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
+            return fail(APEMOST_HIP_ERR_INVALID,
+                        "pointwise_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing", k,
+                        cfg->chains[k], s->cfg.n_chains);
+    const u64 n_series = (u64)cfg->n_keep * (u64)nd;
+    if (n_series > ((u64)1 << 20))
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d chains x %d data: more than 2^20 series", cfg->n_keep,
+                    nd);
+    if (np > kPointwiseTile)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d parameters, more than %d", np, kPointwiseTile);
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a fold begun before may still be accumulating
+    pointwise_free(s);
+    s->pw.n_keep = cfg->n_keep;
+    s->pw.c = pointwise_c(s);
+    s->pw.n = 0;
+    const size_t ns = (size_t)n_series, nk = (size_t)cfg->n_keep;
+    HIP_TRY(hipMalloc((void **)&s->pw.d_chains, nk * sizeof(int)));
+    HIP_TRY(hipMalloc((void **)&s->pw.d_x, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pw.d_y, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pw.d_state, kPointwiseWords * ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pw.d_par, 2 * nk * np * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(s->pw.d_state, 0, kPointwiseWords * ns * sizeof(double), s->stream));
+    HIP_TRY(hipMemsetAsync(s->pw.d_par, 0, 2 * nk * np * sizeof(double), s->stream));
+    HIP_TRY(hipMemcpyAsync(s->pw.d_chains, cfg->chains, nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    for (int k = 0; k < cfg->n_keep; k++) {
+        // columns 0 and 1 of the kept chain's own ladder (the data is stored by columns, ladder after ladder)
+        const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
+        const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * nd;
+        HIP_TRY(hipMemcpyAsync(s->pw.d_x + (size_t)k * nd, col0, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice,
+                               s->stream));
+        HIP_TRY(hipMemcpyAsync(s->pw.d_y + (size_t)k * nd, col0 + nd, (size_t)nd * sizeof(double),
+                               hipMemcpyDeviceToDevice, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's array is read until here)
+    s->pw.open = true;
+    return APEMOST_HIP_OK;
+}
+
+// Queued on copy_stream behind everything launched so far on the sampler's stream, like
+// apemost_hip_predict_accumulate; apemost_hip_samples_wait covers it.
+extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                                uint64_t skip, uint64_t thin) {
+    CHECK_S(s);
+    POINTWISE_BUILTIN(s, "pointwise_accumulate");
+    if (!s->pw.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: no pointwise_begin");
+    if (thin < 1 || (!d_samples && n_steps > 0))
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: bad arguments");
+    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
+    if (kept == 0)
+        return APEMOST_HIP_OK;
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const size_t ns = (size_t)s->pw.n_keep * s->cfg.n_data;
+    for (u64 k0 = 0; k0 < kept; k0 += kPointwisePiece) {
+        PointwiseArgs a;
+        a.rows = d_samples;
+        a.n_chains = s->cfg.n_chains;
+        a.n_par = s->cfg.n_par;
+        a.n_keep = s->pw.n_keep;
+        a.chains = s->pw.d_chains;
+        a.skip = skip + k0 * thin;
+        a.thin = thin;
+        a.n = (unsigned int)(kept - k0 < (u64)kPointwisePiece ? kept - k0 : (u64)kPointwisePiece);
+        a.n0 = s->pw.n;
+        a.n_data = s->cfg.n_data;
+        a.n_blocks = (s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+        a.x = s->pw.d_x;
+        a.y = s->pw.d_y;
+        a.c = s->pw.c;
+        a.origin = s->pw.d_state;
+        a.sum = s->pw.d_state + ns;
+        a.sq = s->pw.d_state + 2 * ns;
+        a.m_up = s->pw.d_state + 3 * ns;
+        a.S_up = s->pw.d_state + 4 * ns;
+        a.m_dn = s->pw.d_state + 5 * ns;
+        a.S_dn = s->pw.d_state + 6 * ns;
+        a.S2_dn = s->pw.d_state + 7 * ns;
+        a.par_origin = s->pw.d_par;
+        a.par_sum = s->pw.d_par + (size_t)s->pw.n_keep * s->cfg.n_par;
+        const dim3 grid((unsigned)(a.n_blocks + 1) * (unsigned)a.n_keep), block(kPointwiseWave);
+        switch (s->cfg.model) {
+        case APEMOST_MODEL_SIMPLESIN:
+            hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->copy_stream, a);
+            break;
+        case APEMOST_MODEL_SINE3:
+            hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_SINE3>, grid, block, 0, s->copy_stream, a);
+            break;
+        case APEMOST_MODEL_PULSE:
+            hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_PULSE>, grid, block, 0, s->copy_stream, a);
+            break;
+        default:
+            hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->copy_stream, a);
+            break;
+        }
+        HIP_TRY(hipGetLastError());
+        s->pw.n += a.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+static int pointwise_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v, bool up) {
+    if (!s->pw.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_%s: no pointwise_begin", up ? "set" : "get");
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise view is NULL");
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    const size_t nk = (size_t)s->pw.n_keep, ns = nk * s->cfg.n_data, np = (size_t)s->cfg.n_par;
+    // stream order: behind every accumulate queued so far, on the stream they run on
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    double *const host[kPointwiseWords] = {v->origin, v->sum, v->sq, v->m_up, v->S_up, v->m_dn, v->S_dn, v->S2_dn};
+#define POINTWISE_COPY(dev, hst, bytes)                                                                        \
+    do {                                                                                                       \
+        if ((hst) && (bytes) > 0)                                                                              \
+            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(hst), (bytes), kind, s->copy_stream)     \
+                       : hipMemcpyAsync((void *)(hst), (const void *)(dev), (bytes), kind, s->copy_stream));   \
+    } while (0)
+    for (int q = 0; q < kPointwiseWords; q++)
+        POINTWISE_COPY(s->pw.d_state + (size_t)q * ns, host[q], ns * sizeof(double));
+    POINTWISE_COPY(s->pw.d_par, v->par_origin, nk * np * sizeof(double));
+    POINTWISE_COPY(s->pw.d_par + nk * np, v->par_sum, nk * np * sizeof(double));
+#undef POINTWISE_COPY
+    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    if (v->n) {
+        if (up)
+            s->pw.n = *v->n;
+        else
+            *v->n = s->pw.n;
+    }
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_get(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
+    CHECK_S(s);
+    POINTWISE_BUILTIN(s, "pointwise_get");
+    return pointwise_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_pointwise_set(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
+    CHECK_S(s);
+    POINTWISE_BUILTIN(s, "pointwise_set");
+    return pointwise_xfer(s, v, true);
+}
+
+extern "C" int apemost_hip_pointwise_end(apemost_hip_sampler *s) {
+    CHECK_S(s);
+    POINTWISE_BUILTIN(s, "pointwise_end");
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    pointwise_free(s);
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int32_t ladder, int32_t n,
+                                                    const double *params, double *out) {
+    CHECK_S(s);
+    POINTWISE_BUILTIN(s, "pointwise_loglike");
+    const int np = s->cfg.n_par, nd = s->cfg.n_data;
+    if (ladder < 0 || ladder >= (s->batch ? s->n_ladders : 1))
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: ladder %d outside [0,%d)", ladder,
+                    s->batch ? s->n_ladders : 1);
+    if (n < 1 || !params || !out || (u64)n * (u64)nd > ((u64)1 << 26))
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: %d rows x %d data, or a NULL array", n, nd);
+    double *d_par = nullptr, *d_out = nullptr;
+    hipError_t err = hipMalloc((void **)&d_par, (size_t)n * np * sizeof(double));
+    if (err == hipSuccess)
+        err = hipMalloc((void **)&d_out, (size_t)n * nd * sizeof(double));
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(d_par, params, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, s->stream);
+    if (err == hipSuccess) {
+        const dim3 grid((unsigned)((nd + kPointwiseWave - 1) / kPointwiseWave) * (unsigned)n), block(kPointwiseWave);
+        // the ladder's columns 0 and 1 (the data is stored by columns, ladder after ladder)
+        const double *x = s->d.data + (size_t)ladder * s->cfg.n_cols * nd, *y = x + nd;
+        const double c = pointwise_c(s);
+        switch (s->cfg.model) {
+        case APEMOST_MODEL_SIMPLESIN:
+            hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
+            break;
+        case APEMOST_MODEL_SINE3:
+            hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_SINE3>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
+            break;
+        case APEMOST_MODEL_PULSE:
+            hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_PULSE>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
+            break;
+        default:
+            hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
+            break;
+        }
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(out, d_out, (size_t)n * nd * sizeof(double), hipMemcpyDeviceToHost, s->stream);
+    const hipError_t sync = hipStreamSynchronize(s->stream);
+    for (double *p : {d_par, d_out})
+        if (p)
+            hipFree(p);
+    HIP_TRY(err);
+    HIP_TRY(sync);
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_loglike(apemost_hip_sampler *s, int32_t n, const double *params, double *out) {
+    return apemost_hip_pointwise_loglike_ladder(s, 0, n, params, out);
 }
 
 // Host arithmetic only (no device): tools/peaks.c:130, 177-200 and the selection sort of src/gsl_helper.c:102-127.

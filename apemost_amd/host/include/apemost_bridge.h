@@ -22,6 +22,7 @@ apemost_hip_sampler *apemost_ladder_sampler(apemost_ladder *l); /* shard 0 */
 #define APEMOST_MAX_SHARDS 16
 unsigned int apemost_ladder_shards(const apemost_ladder *l);
 int apemost_ladder_model(const apemost_ladder *l); /* the APEMOST_MODEL_* detected at open */
+double apemost_ladder_sigma(const apemost_ladder *l); /* the SIGMA the samplers were created with */
 apemost_hip_sampler *apemost_ladder_shard(apemost_ladder *l, unsigned int k);
 unsigned int apemost_ladder_shard_first(const apemost_ladder *l, unsigned int k); /* k = shards: n_chains */
 void apemost_ladder_calc_model(apemost_ladder *l, unsigned int first, unsigned int count);

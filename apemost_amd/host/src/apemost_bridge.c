@@ -24,6 +24,7 @@ struct apemost_ladder {
     unsigned int n, n_par;
     unsigned int n_shards;
     int model; /* the device likelihood detected at open */
+    double sigma; /* the sigma of the shards' configs */
     apemost_hip_sampler *s[APEMOST_MAX_SHARDS];
     unsigned int lo[APEMOST_MAX_SHARDS + 1]; /* shard k holds chains [lo[k], lo[k+1]) */
     apemost_hip_state_view v; /* host staging arrays for the whole ladder, structure of arrays */
@@ -467,6 +468,7 @@ apemost_ladder *apemost_ladder_open(mcmc **chains, unsigned int n_chains) {
     l->n = n_chains;
     l->n_par = chains[0]->n_par;
     l->model = model;
+    l->sigma = SIGMA; /* what the shards' cfg.sigma is set to above */
     /* every shard at least two chains (shard 0 calibrates chains 0 and 1 by itself) */
     while (shards > 1 && n_chains < 2 * shards)
         shards--;
@@ -496,6 +498,7 @@ void apemost_ladder_close(apemost_ladder *l) {
 apemost_hip_sampler *apemost_ladder_sampler(apemost_ladder *l) { return l->s[0]; }
 unsigned int apemost_ladder_shards(const apemost_ladder *l) { return l->n_shards; }
 int apemost_ladder_model(const apemost_ladder *l) { return l->model; }
+double apemost_ladder_sigma(const apemost_ladder *l) { return l->sigma; }
 apemost_hip_sampler *apemost_ladder_shard(apemost_ladder *l, unsigned int k) { return l->s[k]; }
 unsigned int apemost_ladder_shard_first(const apemost_ladder *l, unsigned int k) { return l->lo[k]; }
 

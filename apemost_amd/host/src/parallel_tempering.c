@@ -14,6 +14,7 @@
 #include "apemost_bridge.h"
 #include "run_autocorr.h"
 #include "run_predict.h"
+#include "run_pointwise.h"
 #include "run_evidence.h"
 #include "run_joint.h"
 #include "run_peaks.h"
@@ -231,6 +232,11 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            APEMOST_PREDICT_BINS=N and APEMOST_PREDICT_RANGE=lo:hi both set also the median and the 68 % band
  *            (run_predict.h).  Needs a bounded run and a built-in model.  Combines with every other token and writes
  *            no sample file by itself, like autocorr
+ *   pointwise  fold the log-likelihood term of every datum under chain 0's kept samples on the device: at the end
+ *            write pointwise.bin, pointwise.txt (one line per datum with x, y, the term's mean and standard deviation,
+ *            lppd, p_waic2, elpd_loo and the effective sample size of the leave-one-out weights) and criteria.txt
+ *            (lppd, WAIC, leave-one-out and DIC; run_pointwise.h).  Needs a bounded run and a built-in model.
+ *            Combines with every other token and writes no sample file by itself, like predict
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -250,8 +256,9 @@ typedef struct {
     int evidence;             /* evidence.bin and evidence.txt from the device (APEMOST_DUMP token `evidence`) */
     int autocorr;             /* autocorr.bin and autocorr.txt from the device (APEMOST_DUMP token `autocorr`) */
     int predict;              /* predict.bin and predict.txt from the device (APEMOST_DUMP token `predict`) */
-    int files;                /* sample files are written (not so for `summary`, `peaks`, `joint`, `evidence`, `autocorr`
-                                 and `predict` alone) */
+    int pointwise;            /* pointwise.bin, pointwise.txt and criteria.txt from the device (token `pointwise`) */
+    int files;                /* sample files are written (not so for `summary`, `peaks`, `joint`, `evidence`, `autocorr`,
+                                 `predict` and `pointwise` alone) */
     unsigned int n_param_chains; /* chains 0..n-1 have parameter files (text) / carry their parameter vectors (binary) */
     double *pack;             /* binary: one batch, packed */
     size_t pack_capacity;
@@ -274,6 +281,7 @@ static void sink_parse(sample_sink *k) {
     k->evidence = 0;
     k->autocorr = 0;
     k->predict = 0;
+    k->pointwise = 0;
     while (spec != NULL && *spec != 0) {
         if (strncmp(spec, "binary:all", 10) == 0)
             k->binary = 2, format_given = 1;
@@ -295,15 +303,18 @@ static void sink_parse(sample_sink *k) {
             k->autocorr = 1;
         else if (strncmp(spec, "predict", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
             k->predict = 1;
+        else if (strncmp(spec, "pointwise", 9) == 0 && (spec[9] == 0 || spec[9] == ','))
+            k->pointwise = 1;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise; got '%s'\n", spec);
             exit(1);
         }
         spec = strchr(spec, ',');
         if (spec != NULL)
             spec++;
     }
-    k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr || k->predict) || format_given;
+    k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr || k->predict || k->pointwise) ||
+               format_given;
 #ifdef HISTOGRAMS_MINMAX
     if (k->summary) {
         fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
@@ -621,6 +632,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     run_evidence evidence;
     run_autocorr autocorr;
     run_predict predict;
+    run_pointwise pointwise;
 
     if (max_rounds < 1)
         max_rounds = 1;
@@ -701,6 +713,12 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         run_predict_open(&predict, apemost_ladder_shard(l, 0), chains[0], apemost_ladder_model(l), sink.thin,
                          mode[0] == 'a');
     }
+    if (sink.pointwise) { /* chain 0 lives on shard 0 */
+        (void)planned_samples("pointwise", "pointwise.bin, pointwise.txt and criteria.txt are written when the run ends",
+                              n_swap, iter, max_iterations, sink.thin);
+        run_pointwise_open(&pointwise, apemost_ladder_shard(l, 0), chains[0], apemost_ladder_model(l),
+                           apemost_ladder_sigma(l), sink.thin, mode[0] == 'a');
+    }
     for (i = 0; i < 2 && device_pack; i++)
         apemost_hip_or_die(apemost_hip_samples_alloc(apemost_ladder_shard(l, 0), max_rounds * n_swap, &d_packed[i]),
                            "samples_alloc");
@@ -771,6 +789,10 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             apemost_hip_or_die(apemost_hip_predict_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
                                                               (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
                                "predict_accumulate");
+        if (sink.pointwise) /* chain 0's pointwise log-likelihood, on the same stream */
+            apemost_hip_or_die(apemost_hip_pointwise_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
+                                                                (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
+                               "pointwise_accumulate");
         /* no rows on the host (the text sink, or no sample files): only the counters and chain 0's latest point
          * cross (a packed read that keeps no step) */
         for (j = 0; j < n_shards && !device_pack && !rows_on_host; j++)
@@ -840,6 +862,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         run_autocorr_close(&autocorr, apemost_ladder_shard(l, 0), chains[0]);
     if (sink.predict)
         run_predict_close(&predict, apemost_ladder_shard(l, 0), chains[0]);
+    if (sink.pointwise)
+        run_pointwise_close(&pointwise, apemost_ladder_shard(l, 0));
     for (i = 0; i < 2; i++)
         for (j = 0; j < n_shards; j++) {
             apemost_hip_samples_free(apemost_ladder_shard(l, j), d_samples[i][j]);

@@ -1,0 +1,97 @@
+/* the device side of the APEMOST_DUMP token `pointwise` (run_pointwise.h): begin, resume, collect */
+#include "run_pointwise.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "apemost_bridge.h"
+#include "mcmc_gettersetter.h"
+
+static void pointwise_view(run_pointwise *r, apemost_hip_pointwise_view *v) {
+    v->n = &r->n;
+    v->origin = r->state[0];
+    v->sum = r->state[1];
+    v->sq = r->state[2];
+    v->m_up = r->state[3];
+    v->S_up = r->state[4];
+    v->m_dn = r->state[5];
+    v->S_dn = r->state[6];
+    v->S2_dn = r->state[7];
+    v->par_origin = r->par_origin;
+    v->par_sum = r->par_sum;
+}
+
+void run_pointwise_open(run_pointwise *r, apemost_hip_sampler *s, const mcmc *chain0, int model, double sigma,
+                        uint64_t thin, int append) {
+    const int32_t chain = 0;
+    apemost_hip_pointwise_config c;
+    apemost_hip_pointwise_view v;
+    run_pointwise old;
+    int found = -1, q;
+    uint32_t i;
+    memset(r, 0, sizeof *r);
+    memset(&old, 0, sizeof old);
+    r->n_par = get_n_par(chain0);
+    r->n_data = (uint32_t)chain0->data->size1;
+    r->model = (uint32_t)model;
+    r->sigma = sigma;
+    r->thin = thin;
+    r->chain = chain;
+    run_pointwise_alloc(r);
+    for (i = 0; i < r->n_data; i++) {
+        r->x[i] = gsl_matrix_get(chain0->data, i, 0);
+        r->y[i] = gsl_matrix_get(chain0->data, i, 1);
+    }
+    if (append)
+        found = run_pointwise_read(RUN_POINTWISE_FILE, &old);
+    if (found >= 0) {
+        if (found != 0 || old.chain != 0 || old.n_par != r->n_par || old.n_data != r->n_data || old.model != r->model ||
+            old.thin != thin || old.sigma != sigma || memcmp(old.x, r->x, r->n_data * sizeof(double)) != 0 ||
+            memcmp(old.y, r->y, r->n_data * sizeof(double)) != 0) {
+            fprintf(stderr, "%s: written by a run of another shape (model, parameters, data, sigma or thin:N); cannot "
+                            "append\n", RUN_POINTWISE_FILE);
+            exit(1);
+        }
+    } else if (append)
+        fprintf(stderr, "--append: no %s, the pointwise log-likelihood starts with this run\n", RUN_POINTWISE_FILE);
+    c.n_keep = 1;
+    c.chains = &chain;
+    apemost_hip_or_die(apemost_hip_pointwise_begin(s, &c), "pointwise_begin");
+    if (found == 0) {
+        r->n = old.n;
+        for (q = 0; q < RUN_POINTWISE_WORDS; q++)
+            memcpy(r->state[q], old.state[q], r->n_data * sizeof(double));
+        memcpy(r->par_origin, old.par_origin, r->n_par * sizeof(double));
+        memcpy(r->par_sum, old.par_sum, r->n_par * sizeof(double));
+        pointwise_view(r, &v);
+        apemost_hip_or_die(apemost_hip_pointwise_set(s, &v), "pointwise_set");
+        run_pointwise_free(&old);
+    }
+}
+
+void run_pointwise_close(run_pointwise *r, apemost_hip_sampler *s) {
+    apemost_hip_pointwise_view v;
+    double *mean = (double *)calloc(r->n_par > 0 ? r->n_par : 1, sizeof(double));
+    uint32_t p;
+    if (mean == NULL) {
+        fprintf(stderr, "pointwise: out of memory\n");
+        exit(1);
+    }
+    pointwise_view(r, &v);
+    apemost_hip_or_die(apemost_hip_pointwise_get(s, &v), "pointwise_get");
+    apemost_hip_or_die(apemost_hip_pointwise_end(s), "pointwise_end");
+    /* the term at the posterior mean parameters, by the same device code (left NaN before there is a sample) */
+    if (r->n > 0) {
+        for (p = 0; p < r->n_par; p++) {
+            const double t = r->par_sum[p] / (double)r->n;
+            mean[p] = r->par_origin[p] + t;
+        }
+        apemost_hip_or_die(apemost_hip_pointwise_loglike(s, 1, mean, r->at_mean), "pointwise_loglike");
+    }
+    run_pointwise_write(RUN_POINTWISE_FILE, r);
+    run_pointwise_write_text(RUN_POINTWISE_TEXT, r);
+    run_pointwise_write_criteria(RUN_POINTWISE_CRITERIA, r);
+    free(mean);
+    run_pointwise_free(r);
+}

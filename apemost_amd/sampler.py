@@ -99,6 +99,7 @@ class HipSampler:
         self.seed = seed
         self.n_ladders, self.chains_per_ladder, self.seeds = 1, n_chains, [seed]
         self._x0 = [data[:, 0].copy()]
+        self._y0 = [data[:, 1].copy()]
 
     def _init_batch(self, model, n_par, n_chains, data, seeds, device, chain_offset, n_chains_global, waves_per_chain,
                     sigma, hmin, lds_policy, circular_params, flags, adapt_target, device_model_source):
@@ -122,6 +123,7 @@ class HipSampler:
         self.seed = seeds[0]
         self.n_ladders, self.chains_per_ladder, self.seeds = n_ladders, n_chains, seeds
         self._x0 = [None] * n_ladders
+        self._y0 = [None] * n_ladders
         if data.ndim == 2:
             self.set_data(data)
         else:
@@ -145,6 +147,7 @@ class HipSampler:
             capi.check(self.L.apemost_hip_set_data_ladder(self._h, int(ladder), p))
         for b in range(self.n_ladders) if ladder is None else [int(ladder)]:
             self._x0[b] = data[:, 0].copy()   # the abscissae: what predict_begin(x=None) folds over
+            self._y0[b] = data[:, 1].copy()   # with them the data of pointwise_begin
 
     def ladder_view(self, arr, b):
         """ladder b's part of a ladder-major array or of sample rows of this sampler (module-level ladder_view)"""
@@ -594,6 +597,67 @@ class HipSampler:
         out = np.zeros((len(params), n_x))
         capi.check(self.L.apemost_hip_predict_curve(self._h, len(params), params.ctypes.data_as(capi._dp), n_x, xp,
                                                     out.ctypes.data_as(capi._dp)))
+        return out[0] if one else out
+
+    # -- on-device pointwise log-likelihood (apemost_amd/pointwise.py) -------------------------------
+    def pointwise_begin(self, chains=(0,), thin=1):
+        """start the fold of the pointwise log-likelihood of every datum (columns 0 and 1 of the data as they are now,
+        for every kept chain those of its own ladder) over the kept samples of the local chains `chains` (strictly
+        increasing).  The criteria mean what they say for a chain at beta = 1: chain 0, the default.  thin is recorded
+        in the result."""
+        self._pw_chains = np.ascontiguousarray(chains, dtype=np.int32)
+        assert self._pw_chains.ndim == 1
+        self._pw_thin = int(thin)
+        lads = [int(c) // self.chains_per_ladder if self.n_ladders > 1 else 0
+                for c in self._pw_chains.tolist() if 0 <= c < self.n_chains]
+        lads = lads if len(lads) == len(self._pw_chains) else [0] * len(self._pw_chains)
+        self._pw_data = np.array([[self._x0[b], self._y0[b]] for b in lads], dtype=np.float64).reshape(
+            len(self._pw_chains), 2, -1)
+        cfg = capi.PointwiseConfig(n_keep=len(self._pw_chains),
+                                   chains=self._pw_chains.ctypes.data_as(C.POINTER(C.c_int32)))
+        capi.check(self.L.apemost_hip_pointwise_begin(self._h, C.byref(cfg)))
+
+    def pointwise_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]; asynchronous
+        (pointwise() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_pointwise_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def pointwise(self, at_mean=True):
+        """the fold so far as a Pointwise object (synchronises with the accumulates issued so far).  at_mean: also
+        evaluate the term at every kept chain's posterior mean parameters, which DIC needs, on the device: one
+        pointwise_loglike call, or in a batch one per kept chain over its own ladder's data (not part of the device
+        state)."""
+        from .pointwise import Pointwise
+        pw = Pointwise.empty(self._pw_chains, self._pw_data[:, 0], self._pw_data[:, 1], self.n_par, self.cfg.model,
+                             self.cfg.sigma, self._pw_thin, self.n_ladders)
+        capi.check(self.L.apemost_hip_pointwise_get(self._h, C.byref(pw.view())))
+        if at_mean and int(pw.n[0]) > 0:
+            if self.n_ladders == 1:
+                pw.at_mean = self.pointwise_loglike(pw.par_mean_all()).reshape(pw.n_keep, pw.n_data)
+            else:
+                for k in range(pw.n_keep):
+                    pw.at_mean[k] = self.pointwise_loglike(pw.par_mean(k), int(pw.chains[k]) // self.chains_per_ladder)
+        return pw
+
+    def pointwise_set(self, pw):
+        """load a Pointwise (a resumed run) into the fold begun with the same configuration"""
+        assert pw.origin.shape == self._pw_data[:, 0].shape and pw.n_par == self.n_par
+        assert np.array_equal(pw.chains, self._pw_chains)
+        capi.check(self.L.apemost_hip_pointwise_set(self._h, C.byref(pw.view())))
+
+    def pointwise_end(self):
+        capi.check(self.L.apemost_hip_pointwise_end(self._h))
+
+    def pointwise_loglike(self, params, ladder=0):
+        """the pointwise log-likelihood [n][n_data] of the parameter rows params [n][n_par] (or one row) over the
+        sampler's data (of ladder `ladder` in a batch), evaluated on the device by the fold's own term"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        one = params.ndim == 1
+        params = np.ascontiguousarray(params.reshape(-1, self.n_par))
+        out = np.zeros((len(params), self.cfg.n_data))
+        capi.check(self.L.apemost_hip_pointwise_loglike_ladder(self._h, int(ladder), len(params),
+                                                               params.ctypes.data_as(capi._dp),
+                                                               out.ctypes.data_as(capi._dp)))
         return out[0] if one else out
 
     # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------

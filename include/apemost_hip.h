@@ -899,6 +899,70 @@ int apemost_hip_predict_end(apemost_hip_sampler *s);
 int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x, const double *x,
                               double *out);
 
+/* ---- on-device pointwise log-likelihood: WAIC, leave-one-out and DIC without dumps ------------------
+ * The term l_i(theta) of every datum (x_i, y_i) -- columns 0 and 1 of the sampler's data as they are at begin -- under
+ * every kept sample of the kept chains, while the sample rows are still on the device.  No sample dump holds it: a row
+ * carries only the sum over the data.  With v the model curve of apemost_hip_predict_* at x_i (the operation order is
+ * specified at the head of apemost_amd/csrc/pt_pointwise.h):
+ *   simplesin, sine3    l = ((v - y_i) * (v - y_i)) * c with c = 1.0 / ((-2.0 * sigma) * sigma) from the sampler's sigma;
+ *                       the constant -ln(sigma sqrt(2 pi)) is left out, as the reference's likelihood leaves it out: it
+ *                       shifts every criterion by the same amount per datum;
+ *   pulse, pulse_vrot   l = -(log(v) + y_i / v); the parameter-1 offset of the reference's sum is not a datum's term.
+ * A series is one (kept chain k, datum i) pair, series s = k * n_data + i.  Per series:
+ *   n                      kept samples so far, the same for every series;
+ *   origin[s]              l of the first sample ever accumulated (0 before there is one);
+ *   sum[s], sq[s]          with d = l - origin the sequential sums of d and of d * d (the product rounded, then added);
+ *   m_up[s], S_up[s]       the running log-sum-exp of l, the recurrence of the evidence fold: ln mean exp(l) =
+ *                          m_up + ln(S_up / n), the pointwise log predictive density;
+ *   m_dn[s], S_dn[s], S2_dn[s]   the running log-sum-exp of -l and the running sum of the squares of the same
+ *                          exponentials: -(m_dn + ln(S_dn / n)) is the importance-sampling leave-one-out density and
+ *                          S_dn^2 / S2_dn the effective sample size of its weights.
+ * and per kept chain  par_origin[k][p], par_sum[k][p]: the first sample's parameters and the sequential sums of the
+ * parameters about them (the posterior mean that DIC needs).
+ * No filter: a non-finite or non-positive v gives what IEEE arithmetic gives and touches its own chain's series only.
+ * Every quantity is one thread's chain of operations in sample order, its state carried in device memory between
+ * calls: all of them equal a sequential host loop whatever the boundaries of the accumulate calls are.
+ * Ladder batches: chains are local chain indices of the grid, ladder-major; a kept chain takes the data of its own
+ * ladder.  Sharded ladders: begin on the shard that holds the chain.
+ * APEMOST_MODEL_USER has no datum's term (a device model supplies a lane's partial sum): every
+ * apemost_hip_pointwise_* entry point returns APEMOST_HIP_ERR_UNSUPPORTED for such a sampler. */
+typedef struct {
+    int32_t n_keep;           /* 1 .. n_chains */
+    const int32_t *chains;    /* host [n_keep], local chain indices, strictly increasing */
+} apemost_hip_pointwise_config;
+typedef struct {
+    uint64_t *n;              /* kept samples */
+    double *origin, *sum, *sq, *m_up, *S_up, *m_dn, *S_dn, *S2_dn; /* [n_keep][n_data] */
+    double *par_origin, *par_sum; /* [n_keep][n_par] */
+} apemost_hip_pointwise_view; /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates and initialises the accumulator.  A fold begun before is dropped once the new configuration has been
+ * accepted; a begin that is refused leaves it open and accumulating as it was.  APEMOST_HIP_ERR_INVALID, before any
+ * device work, for a NULL config, n_keep or an index out of range, indices not strictly increasing, n_keep * n_data
+ * above 2^20 series, or more than 512 parameters. */
+int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2], the rows of the
+ * launches issued so far) into the accumulator, in launches of at most 8192 kept steps.  Asynchronous and queued like
+ * apemost_hip_predict_accumulate, on the stream of apemost_hip_samples_read_async.  APEMOST_HIP_ERR_INVALID, before
+ * any device work, without pointwise_begin or with thin == 0. */
+int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                     uint64_t thin);
+/* copies the accumulator out (synchronises with the accumulates issued so far) */
+int apemost_hip_pointwise_get(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v);
+/* loads a view saved by pointwise_get into a fold begun with the same configuration (a resumed run); with n > 0 the
+ * next sample replaces no origin */
+int apemost_hip_pointwise_set(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_pointwise_end(apemost_hip_sampler *s);
+/* out[r][i] = l_i(params[r]), the same term for the caller's parameter rows: params host [n][n_par], out host
+ * [n][n_data], over the sampler's data (of ladder 0 in a batch).  Synchronous; needs no pointwise_begin.
+ * APEMOST_HIP_ERR_INVALID for n < 1, NULL params or out, or n * n_data above 2^26. */
+int apemost_hip_pointwise_loglike(apemost_hip_sampler *s, int32_t n, const double *params, double *out);
+/* the same over the data of ladder `ladder` of a batch (0 for an ordinary sampler); APEMOST_HIP_ERR_INVALID also for a
+ * ladder out of range */
+int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int32_t ladder, int32_t n, const double *params,
+                                         double *out);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
