@@ -132,7 +132,7 @@ class ReplicaFlowView(C.Structure):
 EXPORTS = [
     "apemost_hip_last_error", "apemost_hip_abi_version", "apemost_hip_device_count",
     "apemost_hip_device_info", "apemost_hip_create", "apemost_hip_destroy", "apemost_hip_synchronize",
-    "apemost_hip_stream", "apemost_hip_waves_per_chain", "apemost_hip_launch_policy", "apemost_hip_user_model_compile_seconds", "apemost_hip_set_chain_offset", "apemost_hip_set_data", "apemost_hip_set_state",
+    "apemost_hip_stream", "apemost_hip_waves_per_chain", "apemost_hip_launch_policy", "apemost_hip_user_model_compile_seconds", "apemost_hip_user_hooks", "apemost_hip_set_chain_offset", "apemost_hip_set_data", "apemost_hip_set_state",
     "apemost_hip_get_state", "apemost_hip_set_round", "apemost_hip_get_round", "apemost_hip_calc_model",
     "apemost_hip_loglike", "apemost_hip_launch_round", "apemost_hip_launch_rounds", "apemost_hip_max_rounds_per_launch",
     "apemost_hip_launch_round_for", "apemost_hip_run", "apemost_hip_samples_alloc",
@@ -256,6 +256,7 @@ def lib():
     L.apemost_hip_rng_attempts.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64,
                                            C.c_int32, _dp, _dp, C.POINTER(C.c_int32), _dp]
     L.apemost_hip_user_model_compile_seconds.argtypes = [vp, _dp]
+    L.apemost_hip_user_hooks.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]
     L.apemost_hip_summary_begin.argtypes = [vp, C.POINTER(SummaryConfig)]
     L.apemost_hip_summary_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
     L.apemost_hip_summary_get.argtypes = [vp, C.POINTER(SummaryView)]

@@ -7,6 +7,7 @@
 #include "pt_peaks.h"
 #include "pt_pointwise.h"
 #include "pt_predict.h"
+#include "pt_user_fold.h"
 #include "pt_summary.h"
 #include "pt_text.h"
 
@@ -319,6 +320,16 @@ struct apemost_hip_sampler {
         hipFunction_t round[9], calibrate[9], calc_model[9], loglike[9];
         hipFunction_t round_ob[9], calibrate_ob[9]; // (calibrate_ob: not for the variant instantiations)
     } user;
+    // ... and the kernels of its optional hooks (pt_user_fold.h), a second module compiled on the first predict_* or
+    // pointwise_* call (user_analysis): the functions of an absent hook stay null
+    struct {
+        bool ready; // the hooks are known (and, where there is one, the module is loaded)
+        bool has_curve, has_pointwise;
+        hipModule_t module;
+        hipFunction_t predict_fold, predict_fold_hist, predict_curve, pointwise_fold, pointwise_loglike;
+        double compile_seconds; // hiprtc's time for this sampler's analysis module (0: from the process's cache)
+    } ua;
+    std::string user_source, user_shown; // the model's text as user_model_build read it, its path as a C string literal
     // edge records for in-process shard exchanges (created on first use), one set per side (0 = lower edge,
     // 1 = upper edge): under the even-odd schedule an interior shard exchanges on both edges before one launch
     double *edge_out[2], *edge_in[2];
@@ -396,6 +407,7 @@ struct apemost_hip_sampler {
     struct {
         bool open;
         int n_keep, n_x, nbins, points;
+        int n_cols; // columns of the rows in d_x: 1, or the n_cols of a user model
         double lo, hi;
         u64 n; // kept samples so far (the host knows it without a sync)
         int *d_chains;
@@ -410,7 +422,7 @@ struct apemost_hip_sampler {
         double c; // 1 / (-2 sigma^2)
         u64 n;    // kept samples so far (the host knows it without a sync)
         int *d_chains;
-        double *d_x, *d_y;    // [n_keep][n_data]
+        double *d_x, *d_y;    // [n_keep][n_data] (a user model: d_x [n_keep][n_cols][n_data], no d_y)
         double *d_state;      // the eight [n_keep][n_data] words, one after the other (kPointwiseWords)
         double *d_par;        // par_origin, par_sum: [n_keep][n_par] each
     } pw;
@@ -464,6 +476,7 @@ static hipError_t round_occupancy(int model, int waves, bool producers, bool one
 static size_t ob_lds_bytes(const apemost_hip_sampler *s, bool lds_data);
 static bool ob_wants_helper(const apemost_hip_sampler *s, int n_chains);
 static bool user_may_ob(const apemost_hip_sampler *s);
+static int user_analysis(apemost_hip_sampler *s);
 
 template <class T>
 static int dev_alloc(apemost_hip_sampler *s, T **p, size_t count) {
@@ -599,6 +612,8 @@ static void release(apemost_hip_sampler *s) {
         hipEventDestroy(s->cal.ev);
     if (s->user.module)
         hipModuleUnload(s->user.module);
+    if (s->ua.module)
+        hipModuleUnload(s->ua.module);
     if (s->copy_stream) {
         hipStreamSynchronize(s->copy_stream);
         hipStreamDestroy(s->copy_stream);
@@ -777,6 +792,8 @@ static int user_model_build(apemost_hip_sampler *s) {
             shown += *q;
     }
     const std::string src = "#define APEMOST_USER_MODEL 1\n#include \"pt_kernels.h\"\n#line 1 \"" + shown + "\"\n" + user + "\n";
+    s->user_source = user; // (user_analysis compiles the same text, whatever becomes of the file)
+    s->user_shown = shown;
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, s->cfg.device)); // (before the program exists: nothing to release on failure)
     hiprtcProgram prog = nullptr;
@@ -859,6 +876,116 @@ static int user_model_build(apemost_hip_sampler *s) {
     if (rc == APEMOST_HIP_OK) {
         std::lock_guard<std::mutex> hold(g_user_models_lock);
         g_user_models.push_back(std::move(m));
+    }
+    return rc;
+}
+
+// ---- APEMOST_MODEL_USER: the optional hooks' kernels (pt_user_fold.h), a second run-time module ----
+// Built on the first predict_* or pointwise_* call of a sampler, not at create: a run that never asks for a fold
+// never pays for it.  The translation unit is user_model_build's -- the same prefix, text, options and include
+// directories -- closed by '#include "pt_user_fold.h"', which defines the kernels of the hooks the text announces.
+// Which hooks exist is what the module holds: the entry points are looked up by name.  Kept per process like the
+// round module, keyed by (source text, device architecture, "analysis"); a text without hooks is remembered too, so
+// it is compiled once and no more.
+namespace {
+struct UserAnalysisCode {
+    std::string key;
+    std::vector<char> code;
+};
+std::vector<UserAnalysisCode> g_user_analysis;
+} // namespace
+
+static int user_analysis_load(apemost_hip_sampler *s, const UserAnalysisCode &m) {
+    HIP_TRY(hipModuleLoadData(&s->ua.module, m.code.data()));
+    const struct {
+        const char *name;
+        unsigned long long ours;
+    } prints[] = {{"apemost_rtc_fingerprint", kAbiFingerprint}, {"apemost_rtc_fold_fingerprint", kFoldFingerprint}};
+    for (const auto &fp : prints) {
+        // the headers hiprtc compiled are the ones this library was built from
+        hipDeviceptr_t sym = nullptr;
+        size_t bytes = 0;
+        unsigned long long theirs = 0;
+        if (hipModuleGetGlobal(&sym, &bytes, s->ua.module, fp.name) != hipSuccess || bytes != sizeof theirs)
+            return fail(APEMOST_HIP_ERR_RUNTIME, "the compiled device model's hooks have no layout fingerprint: kernel headers older than this library?");
+        HIP_TRY(hipMemcpyDtoH(&theirs, sym, sizeof theirs));
+        if (theirs != fp.ours)
+            return fail(APEMOST_HIP_ERR_RUNTIME,
+                        "the kernel headers compiled for the device model's hooks (APEMOST_HIP_SOURCE_DIR, or csrc/ beside the "
+                        "library) do not match this library: %s %llx, library %llx", fp.name, theirs, fp.ours);
+    }
+    // a hook is there when all of its kernels are (they share one #ifdef)
+    auto get = [&](hipFunction_t *f, const char *name) {
+        if (hipModuleGetFunction(f, s->ua.module, name) != hipSuccess)
+            *f = nullptr;
+        return *f != nullptr;
+    };
+    const bool c1 = get(&s->ua.predict_fold, "apemost_user_predict_fold"),
+               c2 = get(&s->ua.predict_fold_hist, "apemost_user_predict_fold_hist"),
+               c3 = get(&s->ua.predict_curve, "apemost_user_predict_curve");
+    const bool p1 = get(&s->ua.pointwise_fold, "apemost_user_pointwise_fold"),
+               p2 = get(&s->ua.pointwise_loglike, "apemost_user_pointwise_loglike");
+    (void)hipGetLastError(); // (a lookup that found nothing is an answer, not an error to report later)
+    s->ua.has_curve = c1 && c2 && c3;
+    s->ua.has_pointwise = p1 && p2;
+    return APEMOST_HIP_OK;
+}
+
+// the hooks of this sampler's model, compiled and loaded on first use
+static int user_analysis(apemost_hip_sampler *s) {
+    if (s->ua.ready)
+        return APEMOST_HIP_OK;
+    HipRtc rtc;
+    int rc = hiprtc_load(rtc);
+    if (rc)
+        return rc;
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, s->cfg.device));
+    const std::string key = std::string("analysis|") + prop.gcnArchName + "|" + s->user_source;
+    {
+        std::lock_guard<std::mutex> hold(g_user_models_lock);
+        for (const UserAnalysisCode &m : g_user_analysis)
+            if (m.key == key) {
+                rc = user_analysis_load(s, m);
+                s->ua.compile_seconds = 0;
+                s->ua.ready = rc == APEMOST_HIP_OK;
+                return rc;
+            }
+    }
+    std::string csrc, inc;
+    source_dirs(csrc, inc);
+    const std::string src = "#define APEMOST_USER_MODEL 1\n#include \"pt_kernels.h\"\n#line 1 \"" + s->user_shown + "\"\n" +
+                            s->user_source + "\n#include \"pt_user_fold.h\"\n";
+    hiprtcProgram prog = nullptr;
+    if (rtc.create(&prog, src.c_str(), "apemost_user_model.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
+        return fail(APEMOST_HIP_ERR_RUNTIME, "hiprtcCreateProgram failed");
+    const std::string arch = std::string("--offload-arch=") + prop.gcnArchName, i1 = "-I" + csrc, i2 = "-I" + inc;
+    const char *opts[] = {arch.c_str(), "-O3", "-ffp-contract=off", "-std=c++17", i1.c_str(), i2.c_str(), "-I/opt/rocm/include"};
+    const auto t_compile = std::chrono::steady_clock::now();
+    if (rtc.compile(prog, (int)(sizeof opts / sizeof opts[0]), opts) != HIPRTC_SUCCESS) {
+        size_t n = 0;
+        rtc.log_size(prog, &n);
+        std::string log(n + 1, 0);
+        if (n)
+            rtc.log(prog, &log[0]);
+        rtc.destroy(&prog);
+        return fail(APEMOST_HIP_ERR_INVALID, "the hooks of device model %s (include/apemost_device_model.h) do not compile:\n%s",
+                    s->user_shown.c_str(), log.c_str());
+    }
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_compile).count();
+    UserAnalysisCode m;
+    m.key = key;
+    size_t code_bytes = 0;
+    rtc.code_size(prog, &code_bytes);
+    m.code.resize(code_bytes);
+    rtc.code(prog, m.code.data());
+    rtc.destroy(&prog);
+    rc = user_analysis_load(s, m);
+    if (rc == APEMOST_HIP_OK) {
+        s->ua.compile_seconds = seconds;
+        s->ua.ready = true;
+        std::lock_guard<std::mutex> hold(g_user_models_lock);
+        g_user_analysis.push_back(std::move(m));
     }
     return rc;
 }
@@ -1270,6 +1397,23 @@ extern "C" int apemost_hip_user_model_compile_seconds(apemost_hip_sampler *s, do
     if (!s->user.module || !seconds)
         return fail(APEMOST_HIP_ERR_INVALID, "not a sampler of a user-supplied device model");
     *seconds = s->user_compile_seconds;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_user_hooks(apemost_hip_sampler *s, int32_t *has_curve, int32_t *has_pointwise,
+                                      double *compile_seconds) {
+    CHECK_S(s);
+    if (!s->user.module)
+        return fail(APEMOST_HIP_ERR_INVALID, "not a sampler of a user-supplied device model");
+    const int rc = user_analysis(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    if (has_curve)
+        *has_curve = s->ua.has_curve ? 1 : 0;
+    if (has_pointwise)
+        *has_pointwise = s->ua.has_pointwise ? 1 : 0;
+    if (compile_seconds)
+        *compile_seconds = s->ua.compile_seconds;
     return APEMOST_HIP_OK;
 }
 
@@ -2907,15 +3051,41 @@ extern "C" int apemost_hip_autocorr_end(apemost_hip_sampler *s) {
 }
 
 // ---- on-device posterior predictive (pt_predict.h) ----
-#define PREDICT_BUILTIN(s, what)                                                                                \
+// a built-in model, or a user-supplied one with the curve hook (its analysis module is built here on first use)
+#define PREDICT_HAS_CURVE(s, what)                                                                                \
     do {                                                                                                        \
-        if ((s)->cfg.model == APEMOST_MODEL_USER)                                                               \
-            return fail(APEMOST_HIP_ERR_UNSUPPORTED, what ": a user-supplied device model has no curve");       \
+        if ((s)->cfg.model == APEMOST_MODEL_USER) {                                                             \
+            const int rc_hooks = user_analysis(s);                                                              \
+            if (rc_hooks != APEMOST_HIP_OK)                                                                     \
+                return rc_hooks;                                                                                \
+            if (!(s)->ua.has_curve)                                                                             \
+                return fail(APEMOST_HIP_ERR_UNSUPPORTED,                                                        \
+                            what ": this user-supplied device model has no curve: it does not define the hook " \
+                                 "apemost_user_curve (APEMOST_USER_CURVE, include/apemost_device_model.h)");    \
+        }                                                                                                       \
     } while (0)
 
-static void predict_launch_fold(apemost_hip_sampler *s, const PredictArgs &a) {
+static hipError_t user_launch(hipFunction_t f, unsigned grid, unsigned block, size_t lds, hipStream_t stream, void **params) {
+    return hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, (unsigned)lds, stream, params, nullptr);
+}
+
+// host rows [n][n_cols], row-major like m->data -> a ctx's data, [n_cols][n]
+static std::vector<double> rows_by_columns(const double *rows, int n, int n_cols) {
+    std::vector<double> out((size_t)n * n_cols);
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n_cols; j++)
+            out[(size_t)j * n + i] = rows[(size_t)i * n_cols + j];
+    return out;
+}
+
+static hipError_t predict_launch_fold(apemost_hip_sampler *s, const PredictArgs &a) {
     const dim3 grid((unsigned)(a.n_blocks + 1) * (unsigned)a.n_keep), block(kPredictWave);
     const size_t lds = predict_lds_bytes(a.nbins, a.points);
+    if (s->cfg.model == APEMOST_MODEL_USER) {
+        void *params[] = {const_cast<PredictArgs *>(&a)};
+        return user_launch(a.nbins > 0 ? s->ua.predict_fold_hist : s->ua.predict_fold, grid.x, block.x,
+                           a.nbins > 0 ? lds : 0, s->copy_stream, params);
+    }
 #define PREDICT_FOLD(M)                                                                                          \
     do {                                                                                                         \
         if (a.nbins > 0)                                                                                         \
@@ -2930,11 +3100,12 @@ static void predict_launch_fold(apemost_hip_sampler *s, const PredictArgs &a) {
     default: PREDICT_FOLD(APEMOST_MODEL_PULSE_VROT); break;
     }
 #undef PREDICT_FOLD
+    return hipGetLastError();
 }
 
 extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_hip_predict_config *cfg) {
     CHECK_S(s);
-    PREDICT_BUILTIN(s, "predict_begin");
+    PREDICT_HAS_CURVE(s, "predict_begin");
     if (!cfg)
         return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: config is NULL");
     const int np = s->cfg.n_par;
@@ -2949,10 +3120,13 @@ extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_h
     const int n_x = cfg->x ? cfg->n_x : s->cfg.n_data;
     if (n_x < 1)
         return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: n_x %d < 1", n_x);
+    // a user model's abscissae are whole rows: [n_x][n_cols] from the caller, or the sampler's data
+    const bool user = s->cfg.model == APEMOST_MODEL_USER;
+    const int nc = user ? s->cfg.n_cols : 1;
     if (cfg->x)
-        for (int i = 0; i < n_x; i++)
+        for (size_t i = 0; i < (size_t)n_x * nc; i++)
             if (!std::isfinite(cfg->x[i]))
-                return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: x[%d] is not finite", i);
+                return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: x[%zu] is not finite", i);
     if (cfg->nbins < 0 || cfg->nbins > kPredictMaxBins)
         return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: nbins %d outside [0,%d]", cfg->nbins, kPredictMaxBins);
     if (cfg->nbins > 0 && !(std::isfinite(cfg->lo) && std::isfinite(cfg->hi) && cfg->lo < cfg->hi))
@@ -2970,6 +3144,7 @@ extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_h
     predict_free(s);
     s->pr.n_keep = cfg->n_keep;
     s->pr.n_x = n_x;
+    s->pr.n_cols = nc;
     s->pr.nbins = cfg->nbins;
     s->pr.points = predict_points(cfg->nbins);
     s->pr.lo = cfg->lo;
@@ -2977,7 +3152,7 @@ extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_h
     s->pr.n = 0;
     const size_t ns = (size_t)n_series, nk = (size_t)cfg->n_keep, nh = ns * (size_t)cfg->nbins;
     HIP_TRY(hipMalloc((void **)&s->pr.d_chains, nk * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_x, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pr.d_x, ns * nc * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&s->pr.d_origin, ns * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&s->pr.d_sum, ns * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&s->pr.d_sq, ns * sizeof(double)));
@@ -2998,14 +3173,17 @@ extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_h
     HIP_TRY(hipMemcpyAsync(s->pr.d_vmax, ninf.data(), ns * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(s->pr.d_best_prob, ninf.data(), nk * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(s->pr.d_chains, cfg->chains, nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    const std::vector<double> by_cols = cfg->x && user ? rows_by_columns(cfg->x, n_x, nc) : std::vector<double>();
+    const double *host_x = by_cols.empty() ? cfg->x : by_cols.data();
     for (int k = 0; k < cfg->n_keep; k++) {
-        double *dst = s->pr.d_x + (size_t)k * n_x;
+        double *dst = s->pr.d_x + (size_t)k * nc * n_x;
         if (cfg->x) {
-            HIP_TRY(hipMemcpyAsync(dst, cfg->x, (size_t)n_x * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        } else { // column 0 of the kept chain's own ladder (the data is stored by columns, ladder after ladder)
+            HIP_TRY(hipMemcpyAsync(dst, host_x, (size_t)nc * n_x * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        } else { // column 0 of the kept chain's own ladder (the data is stored by columns, ladder after ladder);
+                 // a user model: all of its columns
             const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
             const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * s->cfg.n_data;
-            HIP_TRY(hipMemcpyAsync(dst, col0, (size_t)n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dst, col0, (size_t)nc * n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
         }
     }
     HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's arrays are read until here)
@@ -3018,7 +3196,7 @@ extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_h
 extern "C" int apemost_hip_predict_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
                                               uint64_t skip, uint64_t thin) {
     CHECK_S(s);
-    PREDICT_BUILTIN(s, "predict_accumulate");
+    PREDICT_HAS_CURVE(s, "predict_accumulate");
     if (!s->pr.open)
         return fail(APEMOST_HIP_ERR_INVALID, "predict_accumulate: no predict_begin");
     if (thin < 1 || (!d_samples && n_steps > 0))
@@ -3044,6 +3222,9 @@ extern "C" int apemost_hip_predict_accumulate(apemost_hip_sampler *s, const doub
         a.n0 = s->pr.n;
         a.n_x = s->pr.n_x;
         a.x = s->pr.d_x;
+        a.n_cols = s->pr.n_cols;
+        a.sigma = s->sh.consts.sigma;
+        a.hmin = s->sh.consts.hmin;
         a.nbins = s->pr.nbins;
         a.points = s->pr.points;
         a.n_blocks = (s->pr.n_x + s->pr.points - 1) / s->pr.points;
@@ -3058,8 +3239,7 @@ extern "C" int apemost_hip_predict_accumulate(apemost_hip_sampler *s, const doub
         a.best_prob = s->pr.d_best_prob;
         a.best_params = s->pr.d_best_params;
         a.best_n = s->pr.d_best_n;
-        predict_launch_fold(s, a);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(predict_launch_fold(s, a));
         s->pr.n += a.n;
     }
     return APEMOST_HIP_OK;
@@ -3106,19 +3286,19 @@ static int predict_xfer(apemost_hip_sampler *s, const apemost_hip_predict_view *
 
 extern "C" int apemost_hip_predict_get(apemost_hip_sampler *s, const apemost_hip_predict_view *v) {
     CHECK_S(s);
-    PREDICT_BUILTIN(s, "predict_get");
+    PREDICT_HAS_CURVE(s, "predict_get");
     return predict_xfer(s, v, false);
 }
 
 extern "C" int apemost_hip_predict_set(apemost_hip_sampler *s, const apemost_hip_predict_view *v) {
     CHECK_S(s);
-    PREDICT_BUILTIN(s, "predict_set");
+    PREDICT_HAS_CURVE(s, "predict_set");
     return predict_xfer(s, v, true);
 }
 
 extern "C" int apemost_hip_predict_end(apemost_hip_sampler *s) {
     CHECK_S(s);
-    PREDICT_BUILTIN(s, "predict_end");
+    PREDICT_HAS_CURVE(s, "predict_end");
     if (s->copy_stream)
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     predict_free(s);
@@ -3128,24 +3308,40 @@ extern "C" int apemost_hip_predict_end(apemost_hip_sampler *s) {
 extern "C" int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x,
                                          const double *x, double *out) {
     CHECK_S(s);
-    PREDICT_BUILTIN(s, "predict_curve");
+    PREDICT_HAS_CURVE(s, "predict_curve");
     if (!x)
         n_x = s->cfg.n_data;
     if (n < 1 || !params || !out || n_x < 1 || (u64)n * (u64)n_x > ((u64)1 << 26))
         return fail(APEMOST_HIP_ERR_INVALID, "predict_curve: %d rows x %d abscissae, or a NULL array", n, n_x);
     const int np = s->cfg.n_par;
+    const bool user = s->cfg.model == APEMOST_MODEL_USER;
+    int nc = user ? s->cfg.n_cols : 1; // a user model's abscissae are whole rows [n_x][n_cols], finite
+    std::vector<double> by_cols;
+    if (user && x) {
+        for (size_t i = 0; i < (size_t)n_x * nc; i++)
+            if (!std::isfinite(x[i]))
+                return fail(APEMOST_HIP_ERR_INVALID, "predict_curve: x[%zu] is not finite", i);
+        by_cols = rows_by_columns(x, n_x, nc);
+        x = by_cols.data();
+    }
     double *d_par = nullptr, *d_x = nullptr, *d_out = nullptr;
     hipError_t err = hipMalloc((void **)&d_par, (size_t)n * np * sizeof(double));
     if (err == hipSuccess)
-        err = hipMalloc((void **)&d_x, (size_t)n_x * sizeof(double));
+        err = hipMalloc((void **)&d_x, (size_t)nc * n_x * sizeof(double));
     if (err == hipSuccess)
         err = hipMalloc((void **)&d_out, (size_t)n * n_x * sizeof(double));
     if (err == hipSuccess)
         err = hipMemcpyAsync(d_par, params, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, s->stream);
     if (err == hipSuccess)
-        err = x ? hipMemcpyAsync(d_x, x, (size_t)n_x * sizeof(double), hipMemcpyHostToDevice, s->stream)
-                : hipMemcpyAsync(d_x, s->d.data, (size_t)n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream);
-    if (err == hipSuccess) {
+        err = x ? hipMemcpyAsync(d_x, x, (size_t)nc * n_x * sizeof(double), hipMemcpyHostToDevice, s->stream)
+                : hipMemcpyAsync(d_x, s->d.data, (size_t)nc * n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream);
+    if (err == hipSuccess && user) {
+        int np_ = np;
+        double sigma = s->sh.consts.sigma, hmin = s->sh.consts.hmin;
+        void *params_[] = {&d_par, &np_, &n_x, &nc, &d_x, &sigma, &hmin, &d_out};
+        err = user_launch(s->ua.predict_curve, (unsigned)((n_x + kPredictWave - 1) / kPredictWave) * (unsigned)n,
+                          kPredictWave, 0, s->stream, params_);
+    } else if (err == hipSuccess) {
         const dim3 grid((unsigned)((n_x + kPredictWave - 1) / kPredictWave) * (unsigned)n), block(kPredictWave);
         switch (s->cfg.model) {
         case APEMOST_MODEL_SIMPLESIN:
@@ -3175,10 +3371,19 @@ extern "C" int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, cons
 }
 
 // ---- on-device pointwise log-likelihood (pt_pointwise.h) ----
-#define POINTWISE_BUILTIN(s, what)                                                                              \
+// a built-in model, or a user-supplied one with the pointwise hook
+#define POINTWISE_HAS_TERM(s, what)                                                                              \
     do {                                                                                                        \
-        if ((s)->cfg.model == APEMOST_MODEL_USER)                                                               \
-            return fail(APEMOST_HIP_ERR_UNSUPPORTED, what ": a user-supplied device model has no datum's term"); \
+        if ((s)->cfg.model == APEMOST_MODEL_USER) {                                                             \
+            const int rc_hooks = user_analysis(s);                                                              \
+            if (rc_hooks != APEMOST_HIP_OK)                                                                     \
+                return rc_hooks;                                                                                \
+            if (!(s)->ua.has_pointwise)                                                                         \
+                return fail(APEMOST_HIP_ERR_UNSUPPORTED,                                                        \
+                            what ": this user-supplied device model has no datum's term: it does not define "   \
+                                 "the hook apemost_user_pointwise (APEMOST_USER_POINTWISE, "                    \
+                                 "include/apemost_device_model.h)");                                            \
+        }                                                                                                       \
     } while (0)
 
 constexpr int kPointwiseWords = 8; // origin, sum, sq, m_up, S_up, m_dn, S_dn, S2_dn
@@ -3192,7 +3397,7 @@ static double pointwise_c(const apemost_hip_sampler *s) {
 
 extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg) {
     CHECK_S(s);
-    POINTWISE_BUILTIN(s, "pointwise_begin");
+    POINTWISE_HAS_TERM(s, "pointwise_begin");
     if (!cfg)
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: config is NULL");
     const int np = s->cfg.n_par, nd = s->cfg.n_data;
@@ -3217,9 +3422,12 @@ extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost
     s->pw.c = pointwise_c(s);
     s->pw.n = 0;
     const size_t ns = (size_t)n_series, nk = (size_t)cfg->n_keep;
+    const bool user = s->cfg.model == APEMOST_MODEL_USER;
+    const size_t nc = user ? (size_t)s->cfg.n_cols : 1; // a user model's data: all of its columns, in d_x
     HIP_TRY(hipMalloc((void **)&s->pw.d_chains, nk * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->pw.d_x, ns * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pw.d_y, ns * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->pw.d_x, ns * nc * sizeof(double)));
+    if (!user)
+        HIP_TRY(hipMalloc((void **)&s->pw.d_y, ns * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&s->pw.d_state, kPointwiseWords * ns * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&s->pw.d_par, 2 * nk * np * sizeof(double)));
     HIP_TRY(hipMemsetAsync(s->pw.d_state, 0, kPointwiseWords * ns * sizeof(double), s->stream));
@@ -3229,9 +3437,10 @@ extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost
         // columns 0 and 1 of the kept chain's own ladder (the data is stored by columns, ladder after ladder)
         const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
         const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * nd;
-        HIP_TRY(hipMemcpyAsync(s->pw.d_x + (size_t)k * nd, col0, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice,
+        HIP_TRY(hipMemcpyAsync(s->pw.d_x + (size_t)k * nc * nd, col0, nc * nd * sizeof(double), hipMemcpyDeviceToDevice,
                                s->stream));
-        HIP_TRY(hipMemcpyAsync(s->pw.d_y + (size_t)k * nd, col0 + nd, (size_t)nd * sizeof(double),
+        if (!user)
+            HIP_TRY(hipMemcpyAsync(s->pw.d_y + (size_t)k * nd, col0 + nd, (size_t)nd * sizeof(double),
                                hipMemcpyDeviceToDevice, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's array is read until here)
@@ -3244,7 +3453,7 @@ extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost
 extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
                                                 uint64_t skip, uint64_t thin) {
     CHECK_S(s);
-    POINTWISE_BUILTIN(s, "pointwise_accumulate");
+    POINTWISE_HAS_TERM(s, "pointwise_accumulate");
     if (!s->pw.open)
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: no pointwise_begin");
     if (thin < 1 || (!d_samples && n_steps > 0))
@@ -3274,6 +3483,9 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
         a.x = s->pw.d_x;
         a.y = s->pw.d_y;
         a.c = s->pw.c;
+        a.n_cols = s->cfg.n_cols;
+        a.sigma = s->sh.consts.sigma;
+        a.hmin = s->sh.consts.hmin;
         a.origin = s->pw.d_state;
         a.sum = s->pw.d_state + ns;
         a.sq = s->pw.d_state + 2 * ns;
@@ -3286,6 +3498,11 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
         a.par_sum = s->pw.d_par + (size_t)s->pw.n_keep * s->cfg.n_par;
         const dim3 grid((unsigned)(a.n_blocks + 1) * (unsigned)a.n_keep), block(kPointwiseWave);
         switch (s->cfg.model) {
+        case APEMOST_MODEL_USER: {
+            void *params[] = {&a};
+            HIP_TRY(user_launch(s->ua.pointwise_fold, grid.x, block.x, 0, s->copy_stream, params));
+            break;
+        }
         case APEMOST_MODEL_SIMPLESIN:
             hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->copy_stream, a);
             break;
@@ -3342,19 +3559,19 @@ static int pointwise_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_vi
 
 extern "C" int apemost_hip_pointwise_get(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
     CHECK_S(s);
-    POINTWISE_BUILTIN(s, "pointwise_get");
+    POINTWISE_HAS_TERM(s, "pointwise_get");
     return pointwise_xfer(s, v, false);
 }
 
 extern "C" int apemost_hip_pointwise_set(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
     CHECK_S(s);
-    POINTWISE_BUILTIN(s, "pointwise_set");
+    POINTWISE_HAS_TERM(s, "pointwise_set");
     return pointwise_xfer(s, v, true);
 }
 
 extern "C" int apemost_hip_pointwise_end(apemost_hip_sampler *s) {
     CHECK_S(s);
-    POINTWISE_BUILTIN(s, "pointwise_end");
+    POINTWISE_HAS_TERM(s, "pointwise_end");
     if (s->copy_stream)
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     pointwise_free(s);
@@ -3364,7 +3581,7 @@ extern "C" int apemost_hip_pointwise_end(apemost_hip_sampler *s) {
 extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int32_t ladder, int32_t n,
                                                     const double *params, double *out) {
     CHECK_S(s);
-    POINTWISE_BUILTIN(s, "pointwise_loglike");
+    POINTWISE_HAS_TERM(s, "pointwise_loglike");
     const int np = s->cfg.n_par, nd = s->cfg.n_data;
     if (ladder < 0 || ladder >= (s->batch ? s->n_ladders : 1))
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: ladder %d outside [0,%d)", ladder,
@@ -3383,6 +3600,13 @@ extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int3
         const double *x = s->d.data + (size_t)ladder * s->cfg.n_cols * nd, *y = x + nd;
         const double c = pointwise_c(s);
         switch (s->cfg.model) {
+        case APEMOST_MODEL_USER: { // all n_cols columns of the ladder's rows
+            int np_ = np, nd_ = nd, nc = s->cfg.n_cols;
+            double sigma = s->sh.consts.sigma, hmin = s->sh.consts.hmin;
+            void *params_[] = {&d_par, &np_, &nd_, &nc, &x, &sigma, &hmin, &d_out};
+            err = user_launch(s->ua.pointwise_loglike, grid.x, block.x, 0, s->stream, params_);
+            break;
+        }
         case APEMOST_MODEL_SIMPLESIN:
             hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
             break;
@@ -3396,7 +3620,8 @@ extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int3
             hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
             break;
         }
-        err = hipGetLastError();
+        if (err == hipSuccess)
+            err = hipGetLastError();
     }
     if (err == hipSuccess)
         err = hipMemcpyAsync(out, d_out, (size_t)n * nd * sizeof(double), hipMemcpyDeviceToHost, s->stream);

@@ -14,7 +14,10 @@
 //                       w = y_i / v, a true fp64 division;  l = -(L + w): apps/pulse.c:50.  The parameter-1 offset that
 //                       the reference adds to the sum is not a datum's term and is left out.
 // A non-finite or non-positive v gives whatever IEEE arithmetic gives: there is no filter, and it touches the series
-// of its own chain only.  APEMOST_MODEL_USER has no term: a device model supplies a lane's partial sum, not a datum's.
+// of its own chain only.  APEMOST_MODEL_USER: the term is the optional hook apemost_user_pointwise(ctx, i) of the device
+// model (include/apemost_device_model.h) over all n_cols columns of the data; a model without it has no term (term()
+// is a lane's share of a sum, and finish() may do anything to that sum).  pt_user_fold.h holds that form of the
+// kernels below: a lane keeps its row index i and a ctx over the rows instead of x_i and y_i, nothing else differs.
 //
 // The fold.  A series is s = (kept chain k, datum i), s = k * n_data + i.  Every item is one thread's chain of
 // operations in kept-sample order, its state carried in device memory between calls: equal to a sequential host loop
@@ -100,15 +103,37 @@ struct PointwiseArgs {
     unsigned int n;                   // kept steps of this piece, 1 .. kPointwisePiece
     unsigned long long n0;            // kept samples before this piece
     int n_data, n_blocks;             // n_blocks = ceil(n_data / 64)
-    const double *x, *y;              // [n_keep][n_data]: every kept chain's data
+    const double *x, *y;              // [n_keep][n_data]: every kept chain's data (a user model: x its rows,
+                                      // [n_keep][n_cols][n_data], column-major per kept chain; y unused)
     double c;                         // 1 / (-2 sigma^2) (the sine models)
+    int n_cols;                       // (a user model's ctx: columns of the rows, the sampler's sigma and hmin)
+    double sigma, hmin;
     double *origin, *sum, *sq, *m_up, *S_up, *m_dn, *S_dn, *S2_dn; // [n_keep][n_data]
     double *par_origin, *par_sum;     // [n_keep][n_par]
 };
 
-// grid (n_blocks + 1) * n_keep, one wave each
+// Where a lane's term comes from: its datum in registers and the built-in curve and term.  (pt_user_fold.h: the row
+// index and a ctx.)  at() is called by active lanes only; par may point into LDS.
 template <int MODEL>
-__global__ void __launch_bounds__(kPointwiseWave) pointwise_fold_kernel(PointwiseArgs a) {
+struct PointwiseTermAt {
+    SinConsts sc;
+    double x, y, c;
+    int np;
+    __device__ __forceinline__ void init(const PointwiseArgs &a, int, int, size_t s, bool active) {
+        sc.init();
+        x = active ? a.x[s] : 0.0;
+        y = active ? a.y[s] : 0.0;
+        c = a.c;
+        np = a.n_par;
+    }
+    __device__ __forceinline__ double at(const double *par) const {
+        return pointwise_term<MODEL>(curve<MODEL>(par, np, x, sc), y, c);
+    }
+};
+
+// a workgroup of pointwise_fold_kernel: grid (n_blocks + 1) * n_keep, one wave each
+template <class EVAL>
+__device__ __forceinline__ void pointwise_fold_body(const PointwiseArgs &a) {
 #pragma clang fp contract(off)
     __shared__ double tile[kPointwiseTile];
     const int lane = threadIdx.x;
@@ -131,19 +156,18 @@ __global__ void __launch_bounds__(kPointwiseWave) pointwise_fold_kernel(Pointwis
         }
         return;
     }
-    SinConsts sc;
-    sc.init();
     const int i = blk * kPointwiseWave + lane;
     const bool active = i < a.n_data;
     const size_t s = (size_t)k * a.n_data + (active ? i : 0);
-    const double x = active ? a.x[s] : 0.0, y = active ? a.y[s] : 0.0;
+    EVAL ev;
+    ev.init(a, k, i, s, active);
     const bool first = a.n0 == 0;
     double origin = 0, sum = 0, sq = 0, m_up = 0, S_up = 0, m_dn = 0, S_dn = 0, S2_dn = 0;
     if (active) {
         sum = a.sum[s];
         sq = a.sq[s];
         if (first) { // the first sample ever: the origin and both maxima; its d = l - l enters the sums below
-            origin = pointwise_term<MODEL>(curve<MODEL>(src, np, x, sc), y, a.c);
+            origin = ev.at(src);
             m_up = origin;
             m_dn = -origin;
             S_up = S_dn = S2_dn = 1.0;
@@ -182,7 +206,7 @@ __global__ void __launch_bounds__(kPointwiseWave) pointwise_fold_kernel(Pointwis
                 bool up = false, dn = false;
 #pragma unroll
                 for (int j = 0; j < kPointwiseSide; j++) {
-                    l[j] = pointwise_term<MODEL>(curve<MODEL>(tile + (r + j) * np, np, x, sc), y, a.c);
+                    l[j] = ev.at(tile + (r + j) * np);
                     xd[j] = -l[j];
                     up = up || l[j] > m_up;
                     dn = dn || xd[j] > m_dn;
@@ -222,7 +246,7 @@ __global__ void __launch_bounds__(kPointwiseWave) pointwise_fold_kernel(Pointwis
                 }
             }
             for (; r < cnt; r++) {
-                const double l = pointwise_term<MODEL>(curve<MODEL>(tile + r * np, np, x, sc), y, a.c);
+                const double l = ev.at(tile + r * np);
                 add(l);
                 evidence_lse_step(l, m_up, S_up);
                 pointwise_lse2_step(-l, m_dn, S_dn, S2_dn);
@@ -240,6 +264,11 @@ __global__ void __launch_bounds__(kPointwiseWave) pointwise_fold_kernel(Pointwis
         a.S_dn[s] = S_dn;
         a.S2_dn[s] = S2_dn;
     }
+}
+
+template <int MODEL>
+__global__ void __launch_bounds__(kPointwiseWave) pointwise_fold_kernel(PointwiseArgs a) {
+    pointwise_fold_body<PointwiseTermAt<MODEL>>(a);
 }
 
 // out[r][i] = l_i(params[r]); grid ceil(n_data / 64) * n

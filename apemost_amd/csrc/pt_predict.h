@@ -14,7 +14,9 @@
 //               is the correctly rounded square, so t*t is it);
 //   pulse_vrot  par = lifetime, (unused), vrot, f3, h3, f5, h5:  the four terms of apps/pulse_vrot.c:45-59 in that
 //               order, at the distances f3 - x, (f5 - x) + (-vrot), f5 - x, (f5 - x) + vrot.
-// APEMOST_MODEL_USER has no curve: a device model supplies term() only.
+// APEMOST_MODEL_USER: the curve is the optional hook apemost_user_curve(ctx, i) of the device model
+// (include/apemost_device_model.h); a model without it has no curve.  pt_user_fold.h holds that form of the kernels
+// below: a lane keeps its row index i and a ctx over the rows being evaluated instead of x_i, nothing else differs.
 //
 // The fold.  A series s = (kept chain k, abscissa i) has the samples v_t = curve(parameters of kept sample t of chain k,
 // x_i).  Per series, each equal to a sequential host loop over the kept samples whatever the calls' boundaries are:
@@ -180,7 +182,10 @@ struct PredictArgs {
     unsigned int n;                   // kept steps of this piece, 1 .. kPredictPiece
     unsigned long long n0;            // kept samples before this piece
     int n_x;
-    const double *x;                  // [n_keep][n_x]: every kept chain's abscissae
+    const double *x;                  // [n_keep][n_x]: every kept chain's abscissae (a user model: its rows,
+                                      // [n_keep][n_cols][n_x], column-major per kept chain)
+    int n_cols;                       // (a user model's ctx: columns of the rows, the sampler's sigma and hmin)
+    double sigma, hmin;
     int nbins, points, n_blocks;      // points per workgroup, n_blocks = ceil(n_x / points)
     double lo, hi;
     double *origin, *sum, *sq, *vmin, *vmax; // [n_keep][n_x]
@@ -189,9 +194,25 @@ struct PredictArgs {
     unsigned long long *best_n;       // [n_keep]
 };
 
-// grid (n_blocks + 1) * n_keep, one wave each; dynamic LDS predict_lds_bytes(nbins, points)
-template <int MODEL, bool HIST>
-__global__ void __launch_bounds__(kPredictWave) predict_fold_kernel(PredictArgs a) {
+// Where a lane's value comes from: its abscissa in a register and the built-in curve.  (pt_user_fold.h: the row index
+// and a ctx.)  at() is called by active lanes only; par may point into LDS.
+template <int MODEL>
+struct PredictCurveAt {
+    SinConsts sc;
+    double x;
+    int np;
+    __device__ __forceinline__ void init(const PredictArgs &a, int, int, size_t s, bool active) {
+        sc.init();
+        x = active ? a.x[s] : 0.0;
+        np = a.n_par;
+    }
+    __device__ __forceinline__ double at(const double *par) const { return curve<MODEL>(par, np, x, sc); }
+};
+
+// a workgroup of predict_fold_kernel: grid (n_blocks + 1) * n_keep, one wave each; dynamic LDS
+// predict_lds_bytes(nbins, points)
+template <class EVAL, bool HIST>
+__device__ __forceinline__ void predict_fold_body(const PredictArgs &a) {
 #pragma clang fp contract(off)
     __shared__ double tile[kPredictTile];
     extern __shared__ double predict_lds[];
@@ -237,12 +258,11 @@ __global__ void __launch_bounds__(kPredictWave) predict_fold_kernel(PredictArgs 
         }
         return;
     }
-    SinConsts sc;
-    sc.init();
     const int i0 = blk * a.points, i = i0 + lane;
     const bool active = lane < a.points && i < a.n_x;
     const size_t s = (size_t)k * a.n_x + (active ? i : 0);
-    const double x = active ? a.x[s] : 0.0;
+    EVAL ev;
+    ev.init(a, k, i, s, active);
     double *edges = predict_lds;
     unsigned int *bins = (unsigned int *)(predict_lds + a.nbins + 1);
     const int here = a.n_x - i0 < a.points ? a.n_x - i0 : a.points; // abscissae of this workgroup
@@ -265,7 +285,7 @@ __global__ void __launch_bounds__(kPredictWave) predict_fold_kernel(PredictArgs 
     }
     double origin = 0, sum = 0, sq = 0, vmin = 0, vmax = 0;
     if (active) {
-        origin = a.n0 == 0 ? curve<MODEL>(src, np, x, sc) : a.origin[s];
+        origin = a.n0 == 0 ? ev.at(src) : a.origin[s];
         sum = a.sum[s];
         sq = a.sq[s];
         vmin = a.vmin[s];
@@ -301,7 +321,7 @@ __global__ void __launch_bounds__(kPredictWave) predict_fold_kernel(PredictArgs 
                 double v[kPredictSide];
 #pragma unroll
                 for (int j = 0; j < kPredictSide; j++)
-                    v[j] = curve<MODEL>(tile + (r + j) * np, np, x, sc);
+                    v[j] = ev.at(tile + (r + j) * np);
                 if (HIST) {
                     int b[kPredictSide];
                     if (sorted) {
@@ -330,7 +350,7 @@ __global__ void __launch_bounds__(kPredictWave) predict_fold_kernel(PredictArgs 
                     add(v[j]);
             }
             for (; r < cnt; r++) {
-                const double v = curve<MODEL>(tile + r * np, np, x, sc);
+                const double v = ev.at(tile + r * np);
                 if (HIST)
                     count(predict_bin(v, edges, a.nbins, e0, etop, a.lo, scale, sorted));
                 add(v);
@@ -354,6 +374,11 @@ __global__ void __launch_bounds__(kPredictWave) predict_fold_kernel(PredictArgs 
             hist[b] += bins[p * rw + (b - p * a.nbins)];
         }
     }
+}
+
+template <int MODEL, bool HIST>
+__global__ void __launch_bounds__(kPredictWave) predict_fold_kernel(PredictArgs a) {
+    predict_fold_body<PredictCurveAt<MODEL>, HIST>(a);
 }
 
 // out[r][i] = curve(params[r], x[i]); grid ceil(n_x / 64) * n

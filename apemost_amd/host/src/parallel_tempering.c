@@ -230,13 +230,15 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            write predict.bin and predict.txt, one line per data point with x, the data, the curve's mean and
  *            standard deviation, the residual, the curve's minimum and maximum and the best-fit curve; with
  *            APEMOST_PREDICT_BINS=N and APEMOST_PREDICT_RANGE=lo:hi both set also the median and the 68 % band
- *            (run_predict.h).  Needs a bounded run and a built-in model.  Combines with every other token and writes
- *            no sample file by itself, like autocorr
+ *            (run_predict.h).  Needs a bounded run and a built-in model, or a device model with the curve hook
+ *            (include/apemost_device_model.h).  Combines with every other token and writes no sample file by itself,
+ *            like autocorr
  *   pointwise  fold the log-likelihood term of every datum under chain 0's kept samples on the device: at the end
  *            write pointwise.bin, pointwise.txt (one line per datum with x, y, the term's mean and standard deviation,
  *            lppd, p_waic2, elpd_loo and the effective sample size of the leave-one-out weights) and criteria.txt
- *            (lppd, WAIC, leave-one-out and DIC; run_pointwise.h).  Needs a bounded run and a built-in model.
- *            Combines with every other token and writes no sample file by itself, like predict
+ *            (lppd, WAIC, leave-one-out and DIC; run_pointwise.h).  Needs a bounded run and a built-in model, or a
+ *            device model with the pointwise hook (include/apemost_device_model.h).  Combines with every other token
+ *            and writes no sample file by itself, like predict
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */

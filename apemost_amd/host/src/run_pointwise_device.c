@@ -38,8 +38,18 @@ void run_pointwise_open(run_pointwise *r, apemost_hip_sampler *s, const mcmc *ch
     r->sigma = sigma;
     r->thin = thin;
     r->chain = chain;
+    if (model == APEMOST_MODEL_USER) { /* the term is the device model's optional hook */
+        int32_t has_pointwise = 0;
+        apemost_hip_or_die(apemost_hip_user_hooks(s, NULL, &has_pointwise, NULL), "user_hooks");
+        if (!has_pointwise) {
+            fprintf(stderr, "APEMOST_DUMP=pointwise: the device model of APEMOST_DEVICE_MODEL_SRC has no datum's term: "
+                            "define APEMOST_USER_POINTWISE and apemost_user_pointwise() in it "
+                            "(include/apemost_device_model.h)\n");
+            exit(1);
+        }
+    }
     run_pointwise_alloc(r);
-    for (i = 0; i < r->n_data; i++) {
+    for (i = 0; i < r->n_data; i++) { /* (the file's x and y; a user model's term sees every column) */
         r->x[i] = gsl_matrix_get(chain0->data, i, 0);
         r->y[i] = gsl_matrix_get(chain0->data, i, 1);
     }

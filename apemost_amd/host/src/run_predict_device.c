@@ -63,6 +63,15 @@ void run_predict_open(run_predict *r, apemost_hip_sampler *s, const mcmc *chain0
     r->model = (uint32_t)model;
     r->thin = thin;
     r->chain = chain;
+    if (model == APEMOST_MODEL_USER) { /* the curve is the device model's optional hook */
+        int32_t has_curve = 0;
+        apemost_hip_or_die(apemost_hip_user_hooks(s, &has_curve, NULL, NULL), "user_hooks");
+        if (!has_curve) {
+            fprintf(stderr, "APEMOST_DUMP=predict: the device model of APEMOST_DEVICE_MODEL_SRC has no curve: define "
+                            "APEMOST_USER_CURVE and apemost_user_curve() in it (include/apemost_device_model.h)\n");
+            exit(1);
+        }
+    }
     bins_from_env(r);
     run_predict_alloc(r);
     for (i = 0; i < r->n_x; i++)
@@ -82,7 +91,7 @@ void run_predict_open(run_predict *r, apemost_hip_sampler *s, const mcmc *chain0
     c.n_keep = 1;
     c.chains = &chain;
     c.n_x = 0;
-    c.x = NULL; /* column 0 of the data, as copied above */
+    c.x = NULL; /* column 0 of the data, as copied above (a user model: the data's rows) */
     c.nbins = (int32_t)r->nbins;
     c.lo = r->lo;
     c.hi = r->hi;
@@ -118,8 +127,10 @@ void run_predict_close(run_predict *r, apemost_hip_sampler *s, const mcmc *chain
     apemost_hip_or_die(apemost_hip_predict_end(s), "predict_end");
     for (i = 0; i < r->n_x; i++)
         y[i] = gsl_matrix_get(chain0->data, i, 1);
-    /* the best fit: the same device curve for the best sample's parameters (zeros before there is one) */
-    apemost_hip_or_die(apemost_hip_predict_curve(s, 1, r->best_params, (int32_t)r->n_x, r->x, best), "predict_curve");
+    /* the best fit: the same device curve for the best sample's parameters (zeros before there is one); a user
+     * model's curve takes whole rows: the data's own (x = NULL) */
+    apemost_hip_or_die(apemost_hip_predict_curve(s, 1, r->best_params, (int32_t)r->n_x,
+                                                 r->model == APEMOST_MODEL_USER ? NULL : r->x, best), "predict_curve");
     run_predict_write(RUN_PREDICT_FILE, r);
     run_predict_write_text(RUN_PREDICT_TEXT, r, y, best);
     free(y);

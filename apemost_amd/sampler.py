@@ -16,6 +16,7 @@ from . import capi
 from .state import LadderState
 
 LADDER_CHEBYSHEV_BETA = 0
+MODEL_USER = 4   # APEMOST_MODEL_USER (include/apemost_hip.h)
 
 
 def ladder_beta(kind, i, n_beta, beta_0):
@@ -149,6 +150,17 @@ class HipSampler:
             self._x0[b] = data[:, 0].copy()   # the abscissae: what predict_begin(x=None) folds over
             self._y0[b] = data[:, 1].copy()   # with them the data of pointwise_begin
 
+    def _user_rows(self, x):
+        """a user model's abscissae are whole rows [n_x][n_cols]; a 1-D x is column 0, the other columns zero"""
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            rows = np.zeros((len(x), self.cfg.n_cols))
+            rows[:, 0] = x
+            return rows
+        if x.ndim != 2 or x.shape[1] != self.cfg.n_cols:
+            raise ValueError("x of a user model: [n_x] or [n_x][%d]" % self.cfg.n_cols)
+        return np.ascontiguousarray(x)
+
     def ladder_view(self, arr, b):
         """ladder b's part of a ladder-major array or of sample rows of this sampler (module-level ladder_view)"""
         return ladder_view(arr, b, self.n_ladders)
@@ -186,6 +198,15 @@ class HipSampler:
         t = C.c_double(0)
         capi.check(self.L.apemost_hip_user_model_compile_seconds(self._h, C.byref(t)))
         return t.value
+
+    @property
+    def user_hooks(self):
+        """(has the curve hook, has the pointwise hook, hiprtc's seconds for the analysis module -- 0: the process had
+        compiled the same source's hooks before) of this sampler's device model (include/apemost_device_model.h); the
+        first call, like the first predict_* or pointwise_* call, compiles that module"""
+        c, p, t = C.c_int32(0), C.c_int32(0), C.c_double(0)
+        capi.check(self.L.apemost_hip_user_hooks(self._h, C.byref(c), C.byref(p), C.byref(t)))
+        return bool(c.value), bool(p.value), t.value
 
     @property
     def launch_policy(self):
@@ -540,7 +561,8 @@ class HipSampler:
     # -- on-device posterior predictive (apemost_amd/predict.py) ------------------------------------
     def predict_begin(self, chains=(0,), x=None, nbins=0, lo=None, hi=None, thin=1):
         """start the fold of the model curve at the abscissae x (None: column 0 of the data, for every kept chain that
-        of its own ladder) over the kept samples of the local chains `chains` (strictly increasing).  nbins > 0 adds a
+        of its own ladder; a user model with the curve hook: rows [n_x][n_cols], a 1-D x being column 0 with the other
+        columns zero, None: the data's rows) over the kept samples of the local chains `chains` (strictly increasing).  nbins > 0 adds a
         histogram of the curve's values over [lo, hi] at every abscissa: medians and credible bands.  thin is recorded
         in the result."""
         self._pr_chains = np.ascontiguousarray(chains, dtype=np.int32)
@@ -553,6 +575,10 @@ class HipSampler:
             xs = xs if len(xs) == len(self._pr_chains) else [self._x0[0]] * len(self._pr_chains)
             self._pr_x = np.array(xs, dtype=np.float64).reshape(len(self._pr_chains), -1)
             xp, n_x = None, 0
+        elif self.cfg.model == MODEL_USER:   # whole rows [n_x][n_cols]; the result's x is their column 0
+            x = self._user_rows(x)
+            self._pr_x = np.tile(x[:, 0], (len(self._pr_chains), 1))
+            xp, n_x = x.ctypes.data_as(capi._dp), len(x)
         else:
             x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
             self._pr_x = np.tile(x, (len(self._pr_chains), 1))
@@ -591,6 +617,9 @@ class HipSampler:
         params = params.reshape(-1, self.n_par)
         if x is None:
             xp, n_x = None, self.cfg.n_data
+        elif self.cfg.model == MODEL_USER:
+            x = self._user_rows(x)
+            xp, n_x = x.ctypes.data_as(capi._dp), len(x)
         else:
             x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
             xp, n_x = x.ctypes.data_as(capi._dp), len(x)

@@ -341,6 +341,15 @@ int apemost_hip_launch_policy(apemost_hip_sampler *s, int32_t *one_barrier, int3
  * user's likelihood for 1, 2, 4 and 8 waves per chain); 0 when the process had compiled the same source
  * before.  Fails for the built-in models. */
 int apemost_hip_user_model_compile_seconds(apemost_hip_sampler *s, double *seconds);
+/* Which of the optional hooks of include/apemost_device_model.h this sampler's device model defines: *has_curve
+ * (apemost_user_curve: apemost_hip_predict_* work) and *has_pointwise (apemost_user_pointwise: apemost_hip_pointwise_*
+ * work), each 0 or 1.  The hooks' kernels are a second run-time module, compiled on the first call of this function
+ * or of any predict_* / pointwise_* entry point of the sampler -- never at create -- and kept per process by source
+ * text like the first; *compile_seconds is hiprtc's time for it, 0 when it came from that cache (a source without
+ * hooks is compiled once per process too).  Any pointer may be NULL.  APEMOST_HIP_ERR_INVALID for a sampler of a
+ * built-in model, or when a source announces a hook (APEMOST_USER_CURVE, APEMOST_USER_POINTWISE) and does not define
+ * its function. */
+int apemost_hip_user_hooks(apemost_hip_sampler *s, int32_t *has_curve, int32_t *has_pointwise, double *compile_seconds);
 /* move the shard along the ladder (single-chain API of the C host layer: the chain's ladder
  * position selects its RNG streams); offset + n_chains must stay <= n_chains_global */
 int apemost_hip_set_chain_offset(apemost_hip_sampler *s, int64_t chain_offset);
@@ -855,13 +864,21 @@ int apemost_hip_autocorr_end(apemost_hip_sampler *s);
  * calls: all of them are bitwise equal to a sequential host loop whatever the boundaries of the accumulate calls are.
  * Ladder batches: chains are local chain indices of the grid, ladder-major; with x = NULL a kept chain takes the data
  * of its own ladder.  Sharded ladders: begin on the shard that holds the chain.
- * APEMOST_MODEL_USER has no curve (a device model supplies term() only): every apemost_hip_predict_* entry point
- * returns APEMOST_HIP_ERR_UNSUPPORTED for such a sampler. */
+ * APEMOST_MODEL_USER: the curve is the device model's optional hook apemost_user_curve(ctx, i)
+ * (include/apemost_device_model.h), and an abscissa is a whole row of n_cols values, because that is what a hook reads:
+ *   x == NULL   the rows are all n_cols columns of the sampler's data as they are at begin (of the kept chain's own
+ *               ladder in a batch), n_x = n_data;
+ *   x != NULL   host [n_x][n_cols], row-major like m->data, every value finite; uploaded column-major as the ctx's data
+ *               with ctx->n_data = n_x.  The same holds for apemost_hip_predict_curve, which needs no begin.
+ * set / get / end, a resumed run, the limits and every APEMOST_HIP_ERR_INVALID rule are the built-in models'.  A device
+ * model without the hook has no curve: every apemost_hip_predict_* entry point returns APEMOST_HIP_ERR_UNSUPPORTED for
+ * such a sampler, with a message that names the hook (apemost_hip_user_hooks asks without failing). */
 typedef struct {
     int32_t n_keep;           /* 1 .. n_chains */
     const int32_t *chains;    /* host [n_keep], local chain indices, strictly increasing */
     int32_t n_x;              /* >= 1; ignored when x is NULL */
-    const double *x;          /* host [n_x], finite; NULL: column 0 of the sampler's data as it is at begin, n_x = n_data */
+    const double *x;          /* host [n_x], finite; NULL: column 0 of the sampler's data as it is at begin, n_x = n_data
+                               * (APEMOST_MODEL_USER: host [n_x][n_cols]; NULL: the data's rows) */
     int32_t nbins;            /* 0: no histograms; else 1 .. 4096 */
     double lo, hi;            /* the histograms' range: finite, lo < hi (ignored when nbins is 0) */
 } apemost_hip_predict_config;
@@ -894,8 +911,9 @@ int apemost_hip_predict_set(apemost_hip_sampler *s, const apemost_hip_predict_vi
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_predict_end(apemost_hip_sampler *s);
 /* out[r][i] = the same curve for the caller's parameter rows: params host [n][n_par], x host [n_x] (NULL: column 0 of
- * the sampler's data -- of ladder 0 in a batch --, n_x = n_data), out host [n][n_x].  Synchronous; needs no
- * predict_begin.  APEMOST_HIP_ERR_INVALID for n < 1, NULL params or out, n_x < 1 or n * n_x above 2^26. */
+ * the sampler's data -- of ladder 0 in a batch --, n_x = n_data), out host [n][n_x].  APEMOST_MODEL_USER: x host
+ * [n_x][n_cols], finite (NULL: the data's rows).  Synchronous; needs no predict_begin.  APEMOST_HIP_ERR_INVALID for
+ * n < 1, NULL params or out, n_x < 1 or n * n_x above 2^26. */
 int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x, const double *x,
                               double *out);
 
@@ -924,8 +942,14 @@ int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, const double *p
  * calls: all of them equal a sequential host loop whatever the boundaries of the accumulate calls are.
  * Ladder batches: chains are local chain indices of the grid, ladder-major; a kept chain takes the data of its own
  * ladder.  Sharded ladders: begin on the shard that holds the chain.
- * APEMOST_MODEL_USER has no datum's term (a device model supplies a lane's partial sum): every
- * apemost_hip_pointwise_* entry point returns APEMOST_HIP_ERR_UNSUPPORTED for such a sampler. */
+ * APEMOST_MODEL_USER: the term is the device model's optional hook apemost_user_pointwise(ctx, i)
+ * (include/apemost_device_model.h) and a datum is a whole row: all n_cols columns of the sampler's data as they are at
+ * begin (of the kept chain's own ladder in a batch), copied, so that a later set_data does not move them.
+ * apemost_hip_pointwise_loglike[_ladder] read the data as it is at the call and need no begin.  set / get / end, a
+ * resumed run, the limits (n_keep * n_data <= 2^20) and every APEMOST_HIP_ERR_INVALID rule are the built-in models'.
+ * The engine cannot check the hook against term() and finish(): it is taken on trust.  A device model without the hook
+ * has no datum's term (term() is a lane's share of a sum): every apemost_hip_pointwise_* entry point returns
+ * APEMOST_HIP_ERR_UNSUPPORTED for such a sampler, with a message that names the hook. */
 typedef struct {
     int32_t n_keep;           /* 1 .. n_chains */
     const int32_t *chains;    /* host [n_keep], local chain indices, strictly increasing */
