@@ -120,6 +120,10 @@ class PointwiseView(C.Structure):
                 ("S_dn", _dp), ("S2_dn", _dp), ("par_origin", _dp), ("par_sum", _dp)]
 
 
+class PointwiseTailView(C.Structure):
+    _fields_ = [("count", _up), ("values", _dp)]
+
+
 PEAKS_MAX = 99   # peaks described per column (include/apemost_hip.h)
 
 
@@ -164,6 +168,8 @@ EXPORTS = [
     "apemost_hip_pointwise_begin", "apemost_hip_pointwise_accumulate", "apemost_hip_pointwise_get",
     "apemost_hip_pointwise_set", "apemost_hip_pointwise_end", "apemost_hip_pointwise_loglike",
     "apemost_hip_pointwise_loglike_ladder",
+    "apemost_hip_pointwise_tail_begin", "apemost_hip_pointwise_tail_get", "apemost_hip_pointwise_tail_set",
+    "apemost_hip_pointwise_tail_capacity",
 ]
 
 _lib = None
@@ -304,6 +310,10 @@ def lib():
     L.apemost_hip_pointwise_end.argtypes = [vp]
     L.apemost_hip_pointwise_loglike.argtypes = [vp, C.c_int32, _dp, _dp]
     L.apemost_hip_pointwise_loglike_ladder.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
+    L.apemost_hip_pointwise_tail_begin.argtypes = [vp, C.c_int32]
+    L.apemost_hip_pointwise_tail_get.argtypes = [vp, C.POINTER(PointwiseTailView)]
+    L.apemost_hip_pointwise_tail_set.argtypes = [vp, C.POINTER(PointwiseTailView)]
+    L.apemost_hip_pointwise_tail_capacity.argtypes = [vp, C.POINTER(C.c_int32)]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

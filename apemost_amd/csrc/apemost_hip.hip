@@ -6,6 +6,7 @@
 #include "pt_kernels.h"
 #include "pt_peaks.h"
 #include "pt_pointwise.h"
+#include "pt_pointwise_tail.h"
 #include "pt_predict.h"
 #include "pt_user_fold.h"
 #include "pt_summary.h"
@@ -326,7 +327,7 @@ struct apemost_hip_sampler {
         bool ready; // the hooks are known (and, where there is one, the module is loaded)
         bool has_curve, has_pointwise;
         hipModule_t module;
-        hipFunction_t predict_fold, predict_fold_hist, predict_curve, pointwise_fold, pointwise_loglike;
+        hipFunction_t predict_fold, predict_fold_hist, predict_curve, pointwise_fold, pointwise_loglike, pointwise_tail_append;
         double compile_seconds; // hiprtc's time for this sampler's analysis module (0: from the process's cache)
     } ua;
     std::string user_source, user_shown; // the model's text as user_model_build read it, its path as a C string literal
@@ -425,6 +426,15 @@ struct apemost_hip_sampler {
         double *d_x, *d_y;    // [n_keep][n_data] (a user model: d_x [n_keep][n_cols][n_data], no d_y)
         double *d_state;      // the eight [n_keep][n_data] words, one after the other (kPointwiseWords)
         double *d_par;        // par_origin, par_sum: [n_keep][n_par] each
+        bool n_set;           // n is what pointwise_set put there: nothing has been accumulated since
+        // its tail (apemost_hip_pointwise_tail_begin, pt_pointwise_tail.h); capacity 0: none
+        struct {
+            int capacity, B;
+            bool awaits_set; // begun on a fold whose state was set: no accumulate before tail_set
+            double *d_buf;               // [n_keep][n_blocks][B][64]
+            unsigned int *d_slots;       // [n_keep][n_data]
+            unsigned long long *d_thr;   // [n_keep][n_data]
+        } tail;
     } pw;
 };
 
@@ -582,7 +592,15 @@ static void predict_free(apemost_hip_sampler *s) {
     s->pr = {};
 }
 
+static void pointwise_tail_free(apemost_hip_sampler *s) {
+    for (void *p : {(void *)s->pw.tail.d_buf, (void *)s->pw.tail.d_slots, (void *)s->pw.tail.d_thr})
+        if (p)
+            hipFree(p);
+    s->pw.tail = {};
+}
+
 static void pointwise_free(apemost_hip_sampler *s) {
+    pointwise_tail_free(s);
     for (void *p : {(void *)s->pw.d_chains, (void *)s->pw.d_x, (void *)s->pw.d_y, (void *)s->pw.d_state,
                     (void *)s->pw.d_par})
         if (p)
@@ -924,10 +942,11 @@ static int user_analysis_load(apemost_hip_sampler *s, const UserAnalysisCode &m)
                c2 = get(&s->ua.predict_fold_hist, "apemost_user_predict_fold_hist"),
                c3 = get(&s->ua.predict_curve, "apemost_user_predict_curve");
     const bool p1 = get(&s->ua.pointwise_fold, "apemost_user_pointwise_fold"),
-               p2 = get(&s->ua.pointwise_loglike, "apemost_user_pointwise_loglike");
+               p2 = get(&s->ua.pointwise_loglike, "apemost_user_pointwise_loglike"),
+               p3 = get(&s->ua.pointwise_tail_append, "apemost_user_pointwise_tail_append");
     (void)hipGetLastError(); // (a lookup that found nothing is an answer, not an error to report later)
     s->ua.has_curve = c1 && c2 && c3;
-    s->ua.has_pointwise = p1 && p2;
+    s->ua.has_pointwise = p1 && p2 && p3;
     return APEMOST_HIP_OK;
 }
 
@@ -3448,6 +3467,68 @@ extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost
     return APEMOST_HIP_OK;
 }
 
+// ---- the tail of the pointwise fold (pt_pointwise_tail.h) ----
+static PointwiseTailArgs pointwise_tail_args(const apemost_hip_sampler *s, bool force) {
+    PointwiseTailArgs t;
+    t.buf = s->pw.tail.d_buf;
+    t.slots = s->pw.tail.d_slots;
+    t.thr = s->pw.tail.d_thr;
+    t.capacity = s->pw.tail.capacity;
+    t.B = s->pw.tail.B;
+    t.n_data = s->cfg.n_data;
+    t.n_blocks = (s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+    t.force = force ? 1 : 0;
+    t.dense = nullptr;
+    t.count = nullptr;
+    return t;
+}
+
+static int pointwise_tail_compact(apemost_hip_sampler *s, bool force) {
+    const PointwiseTailArgs t = pointwise_tail_args(s, force);
+    const dim3 grid((unsigned)s->pw.n_keep * (unsigned)s->cfg.n_data), block(kTailThreads);
+    hipLaunchKernelGGL(pointwise_tail_compact_kernel, grid, block, (size_t)t.B * sizeof(unsigned long long), s->copy_stream, t);
+    HIP_TRY(hipGetLastError());
+    return APEMOST_HIP_OK;
+}
+
+// the kept steps of the fold piece `fold` (already launched), in tail pieces: append, then compact, on copy_stream
+static int pointwise_tail_pieces(apemost_hip_sampler *s, const PointwiseArgs &fold) {
+    const PointwiseTailArgs t = pointwise_tail_args(s, false);
+    const unsigned int piece = (unsigned int)tail_piece(t.capacity);
+    for (unsigned int k0 = 0; k0 < fold.n; k0 += piece) {
+        PointwiseArgs a = fold;
+        a.skip = fold.skip + (u64)k0 * fold.thin;
+        a.n = fold.n - k0 < piece ? fold.n - k0 : piece;
+        a.n0 = fold.n0 + k0;
+        const dim3 grid((unsigned)a.n_blocks * (unsigned)a.n_keep), block(kPointwiseWave);
+        PointwiseTailArgs tt = t;
+        switch (s->cfg.model) {
+        case APEMOST_MODEL_USER: {
+            void *params[] = {&a, &tt};
+            HIP_TRY(user_launch(s->ua.pointwise_tail_append, grid.x, block.x, 0, s->copy_stream, params));
+            break;
+        }
+        case APEMOST_MODEL_SIMPLESIN:
+            hipLaunchKernelGGL(pointwise_tail_append_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->copy_stream, a, tt);
+            break;
+        case APEMOST_MODEL_SINE3:
+            hipLaunchKernelGGL(pointwise_tail_append_kernel<APEMOST_MODEL_SINE3>, grid, block, 0, s->copy_stream, a, tt);
+            break;
+        case APEMOST_MODEL_PULSE:
+            hipLaunchKernelGGL(pointwise_tail_append_kernel<APEMOST_MODEL_PULSE>, grid, block, 0, s->copy_stream, a, tt);
+            break;
+        default:
+            hipLaunchKernelGGL(pointwise_tail_append_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->copy_stream, a, tt);
+            break;
+        }
+        HIP_TRY(hipGetLastError());
+        const int rc = pointwise_tail_compact(s, false);
+        if (rc != APEMOST_HIP_OK)
+            return rc;
+    }
+    return APEMOST_HIP_OK;
+}
+
 // Queued on copy_stream behind everything launched so far on the sampler's stream, like
 // apemost_hip_predict_accumulate; apemost_hip_samples_wait covers it.
 extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
@@ -3458,6 +3539,10 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: no pointwise_begin");
     if (thin < 1 || (!d_samples && n_steps > 0))
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: bad arguments");
+    if (s->pw.tail.awaits_set)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: the tail was begun on a fold of %llu samples that "
+                    "pointwise_set loaded: pointwise_tail_set must load the tail of those samples first",
+                    (unsigned long long)s->pw.n);
     const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
     if (kept == 0)
         return APEMOST_HIP_OK;
@@ -3517,7 +3602,13 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
             break;
         }
         HIP_TRY(hipGetLastError());
+        if (s->pw.tail.capacity > 0) {
+            rc = pointwise_tail_pieces(s, a);
+            if (rc != APEMOST_HIP_OK)
+                return rc;
+        }
         s->pw.n += a.n;
+        s->pw.n_set = false;
     }
     return APEMOST_HIP_OK;
 }
@@ -3549,9 +3640,10 @@ static int pointwise_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_vi
 #undef POINTWISE_COPY
     HIP_TRY(hipStreamSynchronize(s->copy_stream));
     if (v->n) {
-        if (up)
+        if (up) {
             s->pw.n = *v->n;
-        else
+            s->pw.n_set = true;
+        } else
             *v->n = s->pw.n;
     }
     return APEMOST_HIP_OK;
@@ -3576,6 +3668,150 @@ extern "C" int apemost_hip_pointwise_end(apemost_hip_sampler *s) {
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     pointwise_free(s);
     return APEMOST_HIP_OK;
+}
+
+// padded series (64 per block of data) times the slots of a series' buffer
+static u64 pointwise_tail_slots(const apemost_hip_sampler *s, int B) {
+    const u64 n_blocks = ((u64)s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+    return (u64)s->pw.n_keep * n_blocks * kPointwiseWave * (u64)B;
+}
+
+extern "C" int apemost_hip_pointwise_tail_begin(apemost_hip_sampler *s, int32_t capacity) {
+    if (!s)
+        return fail(APEMOST_HIP_ERR_INVALID, "sampler is NULL");
+    if (capacity < 2 || capacity > kTailMaxCapacity)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: capacity %d outside [2,%d]", capacity, kTailMaxCapacity);
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_tail_begin");
+    if (!s->pw.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: no pointwise_begin");
+    if (s->pw.n > 0 && !s->pw.n_set)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: the fold has accumulated %llu samples whose tail is "
+                    "lost: begin the tail before the first accumulate, or right behind pointwise_set",
+                    (unsigned long long)s->pw.n);
+    const u64 limit = (u64)1 << 28;
+    const int B = tail_buffer(capacity);
+    if (pointwise_tail_slots(s, B) > limit) {
+        int fits = 0; // the largest capacity whose buffers fit
+        for (int b = kTailMaxB; b >= 2 * kTailMinP && !fits; b >>= 1)
+            if (pointwise_tail_slots(s, b) <= limit)
+                fits = b / 2;
+        if (fits)
+            return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: %d chains x %d data (in blocks of 64) x %d slots "
+                        "for capacity %d: more than 2^28 slots (2 GiB); the largest capacity that fits is %d",
+                        s->pw.n_keep, s->cfg.n_data, B, capacity, fits);
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: %d chains x %d data (in blocks of 64) x %d slots for "
+                    "capacity %d: more than 2^28 slots (2 GiB); the largest capacity that fits is 0: no capacity fits, "
+                    "keep fewer chains", s->pw.n_keep, s->cfg.n_data, B, capacity);
+    }
+    if (s->copy_stream)
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    pointwise_tail_free(s);
+    const size_t ns = (size_t)s->pw.n_keep * s->cfg.n_data;
+    double *buf = nullptr;
+    unsigned int *slots = nullptr;
+    unsigned long long *thr = nullptr;
+    hipError_t err = hipMalloc((void **)&buf, (size_t)pointwise_tail_slots(s, B) * sizeof(double));
+    if (err == hipSuccess)
+        err = hipMalloc((void **)&slots, ns * sizeof(unsigned int));
+    if (err == hipSuccess)
+        err = hipMalloc((void **)&thr, ns * sizeof(unsigned long long));
+    if (err == hipSuccess)
+        err = hipMemsetAsync(slots, 0, ns * sizeof(unsigned int), s->stream);
+    if (err == hipSuccess)
+        err = hipMemsetAsync(thr, 0, ns * sizeof(unsigned long long), s->stream);
+    if (err == hipSuccess)
+        err = hipStreamSynchronize(s->stream);
+    if (err != hipSuccess) { // the fold stays as it was, without a tail
+        for (void *p : {(void *)buf, (void *)slots, (void *)thr})
+            if (p)
+                hipFree(p);
+        HIP_TRY(err);
+    }
+    s->pw.tail.capacity = capacity;
+    s->pw.tail.B = B;
+    s->pw.tail.d_buf = buf;
+    s->pw.tail.d_slots = slots;
+    s->pw.tail.d_thr = thr;
+    s->pw.tail.awaits_set = s->pw.n > 0;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_tail_capacity(apemost_hip_sampler *s, int32_t *capacity) {
+    if (!s)
+        return fail(APEMOST_HIP_ERR_INVALID, "sampler is NULL");
+    if (!capacity)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_capacity: capacity is NULL");
+    *capacity = s->pw.open ? s->pw.tail.capacity : 0;
+    return APEMOST_HIP_OK;
+}
+
+static int pointwise_tail_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v, bool up) {
+    const char *what = up ? "set" : "get";
+    if (!s->pw.open || s->pw.tail.capacity == 0)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_%s: no pointwise_tail_begin", what);
+    if (!v || !v->count || !v->values)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_%s: the view or one of its arrays is NULL", what);
+    const size_t ns = (size_t)s->pw.n_keep * s->cfg.n_data, cap = (size_t)s->pw.tail.capacity;
+    if (up)
+        for (size_t q = 0; q < ns; q++) {
+            if (v->count[q] > cap)
+                return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_set: count[%zu] = %llu, more than the capacity %zu", q,
+                            (unsigned long long)v->count[q], cap);
+            for (size_t j = 0; j < (size_t)v->count[q]; j++)
+                if (v->values[q * cap + j] != v->values[q * cap + j])
+                    return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_set: values[%zu][%zu] is NaN: a tail holds none", q, j);
+        }
+    int rc = ensure_copy_stream(s);
+    if (rc != APEMOST_HIP_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
+    PointwiseTailArgs t = pointwise_tail_args(s, true);
+    hipError_t err = hipMalloc((void **)&t.dense, ns * cap * sizeof(double));
+    if (err == hipSuccess)
+        err = hipMalloc((void **)&t.count, ns * sizeof(unsigned long long));
+    const dim3 grid((unsigned)ns, (unsigned)((cap + kTailThreads - 1) / kTailThreads)), block(kTailThreads);
+    if (err == hipSuccess && up) {
+        err = hipMemcpyAsync(t.dense, v->values, ns * cap * sizeof(double), hipMemcpyHostToDevice, s->copy_stream);
+        if (err == hipSuccess)
+            err = hipMemcpyAsync(t.count, v->count, ns * sizeof(unsigned long long), hipMemcpyHostToDevice, s->copy_stream);
+        if (err == hipSuccess) {
+            hipLaunchKernelGGL(pointwise_tail_scatter_kernel, grid, block, 0, s->copy_stream, t);
+            err = hipGetLastError();
+        }
+        if (err == hipSuccess) // sorts what was loaded and sets every threshold from it
+            err = pointwise_tail_compact(s, true) == APEMOST_HIP_OK ? hipSuccess : hipErrorLaunchFailure;
+    } else if (err == hipSuccess) {
+        err = pointwise_tail_compact(s, true) == APEMOST_HIP_OK ? hipSuccess : hipErrorLaunchFailure;
+        if (err == hipSuccess) {
+            hipLaunchKernelGGL(pointwise_tail_gather_kernel, grid, block, 0, s->copy_stream, t);
+            err = hipGetLastError();
+        }
+        if (err == hipSuccess)
+            err = hipMemcpyAsync(v->values, t.dense, ns * cap * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream);
+        if (err == hipSuccess)
+            err = hipMemcpyAsync(v->count, t.count, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->copy_stream);
+    }
+    const hipError_t sync = hipStreamSynchronize(s->copy_stream);
+    for (void *p : {(void *)t.dense, (void *)t.count})
+        if (p)
+            hipFree(p);
+    HIP_TRY(err);
+    HIP_TRY(sync);
+    if (up)
+        s->pw.tail.awaits_set = false;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_tail_get(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v) {
+    CHECK_S(s);
+    return pointwise_tail_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_pointwise_tail_set(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v) {
+    CHECK_S(s);
+    return pointwise_tail_xfer(s, v, true);
 }
 
 extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int32_t ladder, int32_t n,

@@ -23,6 +23,7 @@
 #pragma once
 
 #include "pt_pointwise.h"
+#include "pt_pointwise_tail.h"
 #include "pt_predict.h"
 
 namespace apemost {
@@ -32,7 +33,8 @@ namespace apemost {
 constexpr unsigned long long kFoldFingerprint =
     (unsigned long long)sizeof(PredictArgs) ^ ((unsigned long long)sizeof(PointwiseArgs) << 12) ^
     ((unsigned long long)kPredictPiece << 24) ^ ((unsigned long long)kPredictTile << 40) ^
-    ((unsigned long long)kPredictSide << 52) ^ 0x666f6c6400000000ull;
+    ((unsigned long long)kPredictSide << 52) ^ ((unsigned long long)sizeof(PointwiseTailArgs) << 4) ^
+    0x666f6c6400000000ull;
 
 } // namespace apemost
 
@@ -114,6 +116,11 @@ struct UserTermAt {
 
 extern "C" __global__ void __launch_bounds__(apemost::kPointwiseWave) apemost_user_pointwise_fold(apemost::PointwiseArgs a) {
     apemost::pointwise_fold_body<apemost::UserTermAt>(a);
+}
+// the tail of the fold (pt_pointwise_tail.h): the same term, the built-in models' append body
+extern "C" __global__ void __launch_bounds__(apemost::kPointwiseWave)
+apemost_user_pointwise_tail_append(apemost::PointwiseArgs a, apemost::PointwiseTailArgs t) {
+    apemost::pointwise_tail_append_body<apemost::UserTermAt>(a, t);
 }
 // out[r][i] = apemost_user_pointwise at params[r] and row i of the rows [n_cols][n_data]; grid ceil(n_data / 64) * n
 extern "C" __global__ void __launch_bounds__(apemost::kPointwiseWave)

@@ -238,7 +238,10 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            lppd, p_waic2, elpd_loo and the effective sample size of the leave-one-out weights) and criteria.txt
  *            (lppd, WAIC, leave-one-out and DIC; run_pointwise.h).  Needs a bounded run and a built-in model, or a
  *            device model with the pointwise hook (include/apemost_device_model.h).  Combines with every other token
- *            and writes no sample file by itself, like predict
+ *            and writes no sample file by itself, like predict.  With APEMOST_POINTWISE_TAIL=auto|N (a capacity in
+ *            2 .. 4096; auto sizes it for the samples the run plans) the fold keeps its tail, the largest
+ *            leave-one-out log weights of every datum, and writes pointwise_tail.bin as well: `python -m
+ *            apemost_amd.psis DIR` turns the two files into Pareto-smoothed leave-one-out and the Pareto k table
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -317,6 +320,8 @@ static void sink_parse(sample_sink *k) {
     }
     k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr || k->predict || k->pointwise) ||
                format_given;
+    if (k->pointwise) /* a malformed APEMOST_POINTWISE_TAIL ends the program here, before any file is opened */
+        (void)run_pointwise_tail_from_env();
 #ifdef HISTOGRAMS_MINMAX
     if (k->summary) {
         fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
@@ -716,10 +721,11 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
                          mode[0] == 'a');
     }
     if (sink.pointwise) { /* chain 0 lives on shard 0 */
-        (void)planned_samples("pointwise", "pointwise.bin, pointwise.txt and criteria.txt are written when the run ends",
-                              n_swap, iter, max_iterations, sink.thin);
+        const uint64_t planned =
+            planned_samples("pointwise", "pointwise.bin, pointwise.txt and criteria.txt are written when the run ends",
+                            n_swap, iter, max_iterations, sink.thin);
         run_pointwise_open(&pointwise, apemost_ladder_shard(l, 0), chains[0], apemost_ladder_model(l),
-                           apemost_ladder_sigma(l), sink.thin, mode[0] == 'a');
+                           apemost_ladder_sigma(l), sink.thin, mode[0] == 'a', planned);
     }
     for (i = 0; i < 2 && device_pack; i++)
         apemost_hip_or_die(apemost_hip_samples_alloc(apemost_ladder_shard(l, 0), max_rounds * n_swap, &d_packed[i]),

@@ -10,6 +10,8 @@
 
 #define RUN_POINTWISE_MAGIC "APEMOSTW"
 #define RUN_POINTWISE_VERSION 1
+#define RUN_POINTWISE_TAIL_MAGIC "APEMOSTT"
+#define RUN_POINTWISE_TAIL_VERSION 1
 
 static void *alloc_or_die(size_t count, size_t size) {
     void *p = calloc(count > 0 ? count : 1, size);
@@ -44,7 +46,25 @@ void run_pointwise_free(run_pointwise *r) {
     free(r->par_origin);
     free(r->par_sum);
     free(r->at_mean);
+    run_pointwise_tail_free(&r->tail);
     memset(r, 0, sizeof *r);
+}
+
+uint32_t run_pointwise_tail_capacity_for(uint64_t n) {
+    const double a = 0.2 * (double)n, b = 3.0 * sqrt((double)n);
+    const double m = ceil(a < b ? a : b) + 1.0;
+    return m > 4096.0 ? 4096u : m < 2.0 ? 2u : (uint32_t)m;
+}
+
+void run_pointwise_tail_alloc(run_pointwise_tail *t) {
+    t->count = (uint64_t *)alloc_or_die(t->n_data, sizeof(uint64_t));
+    t->values = (double *)alloc_or_die((size_t)t->n_data * t->capacity, sizeof(double));
+}
+
+void run_pointwise_tail_free(run_pointwise_tail *t) {
+    free(t->count);
+    free(t->values);
+    memset(t, 0, sizeof *t);
 }
 
 static void read_or_die(void *p, size_t size, size_t count, FILE *f, const char *path) {
@@ -97,6 +117,42 @@ int run_pointwise_read(const char *path, run_pointwise *r) {
     return 0;
 }
 
+int run_pointwise_tail_read(const char *path, run_pointwise_tail *t) {
+    FILE *f = fopen(path, "rb");
+    char magic[8];
+    uint32_t u32[8], i;
+    uint64_t u64[2];
+    memset(t, 0, sizeof *t);
+    if (f == NULL)
+        return -1;
+    read_or_die(magic, 1, 8, f, path);
+    read_or_die(u32, sizeof(uint32_t), 8, f, path);
+    if (memcmp(magic, RUN_POINTWISE_TAIL_MAGIC, 8) != 0 || u32[0] != RUN_POINTWISE_TAIL_VERSION) {
+        fprintf(stderr, "%s: not a pointwise tail file of version %d\n", path, RUN_POINTWISE_TAIL_VERSION);
+        exit(1);
+    }
+    read_or_die(u64, sizeof(uint64_t), 2, f, path);
+    if (u32[1] != 1 || u32[4] != 1 || u32[2] < 1 || u32[2] > (1u << 20) || u32[3] < 2 || u32[3] > 4096) {
+        fclose(f);
+        return 1;
+    }
+    t->n_data = u32[2];
+    t->capacity = u32[3];
+    t->n = u64[0];
+    t->thin = u64[1];
+    run_pointwise_tail_alloc(t);
+    read_or_die(&t->chain, sizeof(int32_t), 1, f, path);
+    read_or_die(t->count, sizeof(uint64_t), t->n_data, f, path);
+    read_or_die(t->values, sizeof(double), (size_t)t->n_data * t->capacity, f, path);
+    fclose(f);
+    for (i = 0; i < t->n_data; i++)
+        if (t->count[i] > t->capacity) {
+            run_pointwise_tail_free(t);
+            return 1;
+        }
+    return 0;
+}
+
 static FILE *open_or_die(const char *path, const char *mode) {
     FILE *f = fopen(path, mode);
     if (f == NULL) {
@@ -142,6 +198,30 @@ void run_pointwise_write(const char *path, const run_pointwise *r) {
     fwrite(r->par_origin, sizeof(double), r->n_par, f);
     fwrite(r->par_sum, sizeof(double), r->n_par, f);
     fwrite(r->at_mean, sizeof(double), nd, f);
+    close_or_die(f, path);
+}
+
+void run_pointwise_tail_write(const char *path, const run_pointwise_tail *t) {
+    FILE *f = open_or_die(path, "wb");
+    const double zero = 0.0;
+    uint32_t u32[8], i, j;
+    uint64_t u64[2];
+    u32[0] = RUN_POINTWISE_TAIL_VERSION;
+    u32[1] = 1;
+    u32[2] = t->n_data;
+    u32[3] = t->capacity;
+    u32[4] = 1;
+    u32[5] = u32[6] = u32[7] = 0;
+    u64[0] = t->n;
+    u64[1] = t->thin;
+    fwrite(RUN_POINTWISE_TAIL_MAGIC, 1, 8, f);
+    fwrite(u32, sizeof(uint32_t), 8, f);
+    fwrite(u64, sizeof(uint64_t), 2, f);
+    fwrite(&t->chain, sizeof(int32_t), 1, f);
+    fwrite(t->count, sizeof(uint64_t), t->n_data, f);
+    for (i = 0; i < t->n_data; i++)
+        for (j = 0; j < t->capacity; j++)
+            fwrite(j < t->count[i] ? &t->values[(size_t)i * t->capacity + j] : &zero, sizeof(double), 1, f);
     close_or_die(f, path);
 }
 

@@ -22,9 +22,60 @@ static void pointwise_view(run_pointwise *r, apemost_hip_pointwise_view *v) {
     v->par_sum = r->par_sum;
 }
 
+int run_pointwise_tail_from_env(void) {
+    const char *text = getenv("APEMOST_POINTWISE_TAIL");
+    char *end;
+    long v;
+    if (text == NULL || *text == 0)
+        return 0;
+    if (strcmp(text, "auto") == 0)
+        return -1;
+    v = strtol(text, &end, 10);
+    if (*end != 0 || v < 2 || v > 4096) {
+        fprintf(stderr, "APEMOST_POINTWISE_TAIL: expected auto or a capacity in 2 .. 4096; got '%s'\n", text);
+        exit(1);
+    }
+    return (int)v;
+}
+
+/* begins the tail on the fold just begun (and, resuming, just set); `resumed`: pointwise.bin was loaded */
+static void tail_open(run_pointwise *r, apemost_hip_sampler *s, int asked, int resumed, uint64_t planned) {
+    apemost_hip_pointwise_tail_view v;
+    run_pointwise_tail old;
+    int found = -1;
+    memset(&old, 0, sizeof old);
+    if (resumed) {
+        found = run_pointwise_tail_read(RUN_POINTWISE_TAIL_FILE, &old);
+        if (found < 0) {
+            fprintf(stderr, "--append: %s holds %lu samples but there is no %s: their tail is lost; cannot append with "
+                            "APEMOST_POINTWISE_TAIL\n", RUN_POINTWISE_FILE, (unsigned long)r->n, RUN_POINTWISE_TAIL_FILE);
+            exit(1);
+        }
+        if (found != 0 || old.chain != 0 || old.n_data != r->n_data || old.n != r->n || old.thin != r->thin ||
+            (asked > 0 && old.capacity != (uint32_t)asked)) {
+            fprintf(stderr, "%s: written by a run of another shape (data, capacity, thin:N, or not the samples of %s); "
+                            "cannot append\n", RUN_POINTWISE_TAIL_FILE, RUN_POINTWISE_FILE);
+            exit(1);
+        }
+    }
+    r->tail.n_data = r->n_data;
+    r->tail.capacity = found == 0 ? old.capacity : asked > 0 ? (uint32_t)asked : run_pointwise_tail_capacity_for(planned);
+    r->tail.chain = 0;
+    r->tail.thin = r->thin;
+    run_pointwise_tail_alloc(&r->tail);
+    apemost_hip_or_die(apemost_hip_pointwise_tail_begin(s, (int32_t)r->tail.capacity), "pointwise_tail_begin");
+    if (found == 0) {
+        v.count = old.count;
+        v.values = old.values;
+        apemost_hip_or_die(apemost_hip_pointwise_tail_set(s, &v), "pointwise_tail_set");
+        run_pointwise_tail_free(&old);
+    }
+}
+
 void run_pointwise_open(run_pointwise *r, apemost_hip_sampler *s, const mcmc *chain0, int model, double sigma,
-                        uint64_t thin, int append) {
+                        uint64_t thin, int append, uint64_t planned) {
     const int32_t chain = 0;
+    const int tail = run_pointwise_tail_from_env();
     apemost_hip_pointwise_config c;
     apemost_hip_pointwise_view v;
     run_pointwise old;
@@ -78,6 +129,8 @@ void run_pointwise_open(run_pointwise *r, apemost_hip_sampler *s, const mcmc *ch
         apemost_hip_or_die(apemost_hip_pointwise_set(s, &v), "pointwise_set");
         run_pointwise_free(&old);
     }
+    if (tail != 0)
+        tail_open(r, s, tail, found == 0, planned);
 }
 
 void run_pointwise_close(run_pointwise *r, apemost_hip_sampler *s) {
@@ -90,6 +143,14 @@ void run_pointwise_close(run_pointwise *r, apemost_hip_sampler *s) {
     }
     pointwise_view(r, &v);
     apemost_hip_or_die(apemost_hip_pointwise_get(s, &v), "pointwise_get");
+    if (r->tail.capacity > 0) {
+        apemost_hip_pointwise_tail_view tv;
+        tv.count = r->tail.count;
+        tv.values = r->tail.values;
+        apemost_hip_or_die(apemost_hip_pointwise_tail_get(s, &tv), "pointwise_tail_get");
+        r->tail.n = r->n;
+        run_pointwise_tail_write(RUN_POINTWISE_TAIL_FILE, &r->tail);
+    }
     apemost_hip_or_die(apemost_hip_pointwise_end(s), "pointwise_end");
     /* the term at the posterior mean parameters, by the same device code (left NaN before there is a sample) */
     if (r->n > 0) {

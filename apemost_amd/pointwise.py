@@ -21,9 +21,11 @@ Per datum i (all of these return [n_data] arrays; the criteria are their sums):
     p_dic        = 2 (sum at_mean - sum mean_loglike)      dic = -2 sum at_mean + 2 p_dic
 
 The standard errors (waic_se, compare) are sqrt(n_data * variance over the data of the pointwise values), the variance
-divided by n_data - 1: the standard error of the summed elpd; that of waic = -2 elpd is twice it.  Pareto smoothing of
-the weights is not done: loo_ess is the diagnostic offered in its place -- where it collapses towards 1, one sample
-carries the leave-one-out estimate of that datum and elpd_loo is not to be trusted there (loo_unreliable).
+divided by n_data - 1: the standard error of the summed elpd; that of waic = -2 elpd is twice it.  elpd_loo here is
+plain importance sampling; loo_ess says where it collapses -- towards 1, one sample carries the leave-one-out estimate
+of that datum and elpd_loo is not to be trusted there (loo_unreliable).  Pareto smoothing of the weights, with the
+Pareto k of every datum as the diagnostic, is apemost_amd/psis.py: it takes this object and the fold's tail
+(HipSampler.pointwise_begin(tail=...), pointwise_tail()), the sorted largest weights per datum kept on the device.
 
 Keep in mind:
   * The criteria mean what they say for a chain at beta = 1, which is chain 0 and the default: a tempered chain samples

@@ -629,11 +629,13 @@ class HipSampler:
         return out[0] if one else out
 
     # -- on-device pointwise log-likelihood (apemost_amd/pointwise.py) -------------------------------
-    def pointwise_begin(self, chains=(0,), thin=1):
+    def pointwise_begin(self, chains=(0,), thin=1, tail=None):
         """start the fold of the pointwise log-likelihood of every datum (columns 0 and 1 of the data as they are now,
         for every kept chain those of its own ladder) over the kept samples of the local chains `chains` (strictly
         increasing).  The criteria mean what they say for a chain at beta = 1: chain 0, the default.  thin is recorded
-        in the result."""
+        in the result.  tail: also keep, per kept chain and datum, the largest leave-one-out log weights
+        (pointwise_tail(), apemost_amd/psis.py): a capacity (2 .. 4096), or "auto:<expected kept samples>" for
+        psis.capacity_for of that many; None keeps none."""
         self._pw_chains = np.ascontiguousarray(chains, dtype=np.int32)
         assert self._pw_chains.ndim == 1
         self._pw_thin = int(thin)
@@ -645,6 +647,42 @@ class HipSampler:
         cfg = capi.PointwiseConfig(n_keep=len(self._pw_chains),
                                    chains=self._pw_chains.ctypes.data_as(C.POINTER(C.c_int32)))
         capi.check(self.L.apemost_hip_pointwise_begin(self._h, C.byref(cfg)))
+        if tail is not None:
+            self.pointwise_tail_begin(tail)
+
+    def pointwise_tail_begin(self, tail):
+        """attach a tail to the open fold, before its first accumulate or right behind pointwise_set (then
+        pointwise_tail_set must follow); `tail` as in pointwise_begin"""
+        from . import psis
+        if isinstance(tail, str):
+            kind, _, expected = tail.partition(":")
+            if kind != "auto" or not expected.strip().isdigit():
+                raise ValueError("tail %r: a capacity or \"auto:<expected kept samples>\"" % (tail,))
+            tail = psis.capacity_for(int(expected))
+        capi.check(self.L.apemost_hip_pointwise_tail_begin(self._h, int(tail)))
+
+    def pointwise_tail_capacity(self):
+        """the capacity of the open fold's tail, 0 where there is none"""
+        c = C.c_int32(0)
+        capi.check(self.L.apemost_hip_pointwise_tail_capacity(self._h, C.byref(c)))
+        return c.value
+
+    def pointwise_tail(self):
+        """the tail so far as a psis.PointwiseTail (synchronises with the accumulates issued so far)"""
+        from .psis import PointwiseTail
+        n = C.c_uint64(0)
+        capi.check(self.L.apemost_hip_pointwise_get(self._h, C.byref(capi.PointwiseView(n=C.pointer(n)))))
+        t = PointwiseTail.empty(self._pw_chains, self.cfg.n_data, self.pointwise_tail_capacity(), n.value, self._pw_thin,
+                                self.n_ladders)
+        capi.check(self.L.apemost_hip_pointwise_tail_get(self._h, C.byref(t.view())))
+        t.clear_unused()
+        return t
+
+    def pointwise_tail_set(self, tail):
+        """load a PointwiseTail (a resumed run) into the tail begun with the same capacity"""
+        assert tail.count.shape == self._pw_data[:, 0].shape and np.array_equal(tail.chains, self._pw_chains)
+        assert tail.capacity == self.pointwise_tail_capacity()
+        capi.check(self.L.apemost_hip_pointwise_tail_set(self._h, C.byref(tail.view())))
 
     def pointwise_accumulate(self, d_samples, n_steps, skip=0, thin=1):
         """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]; asynchronous

@@ -987,6 +987,45 @@ int apemost_hip_pointwise_loglike(apemost_hip_sampler *s, int32_t n, const doubl
 int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int32_t ladder, int32_t n, const double *params,
                                          double *out);
 
+/* ---- the tail of a pointwise fold (pt_pointwise_tail.h): what Pareto-smoothed leave-one-out needs ----
+ * Per series s = (kept chain k, datum i) the `capacity` largest values of x = -l over the kept samples, exactly, where l
+ * is the fold's own term of the same row (the same device function, so the same bits).  The order is the total order of
+ * the bit patterns in which -0 lies below +0 and -inf and +inf are the ends; a NaN is never stored.  After any number of
+ * accumulate calls
+ *   count[s]              = min(capacity, samples so far whose term is not NaN),
+ *   values[s][0 .. count) = the count[s] largest x, descending.
+ * A selection under a total order does not depend on how the kept samples were cut into calls: the same kept samples
+ * give the same bits.  With m_dn and S_dn of the fold this gives PSIS-LOO and the Pareto k of every datum
+ * (apemost_amd/psis.py; the fit is not restated in C): the M + 1 largest log weights, M = ceil(min(0.2 n, 3 sqrt(n))),
+ * so capacity = M + 1 (at most 4096: runs above 1.86e6 kept samples get a shorter tail).
+ *
+ * The tail attaches to an open fold: apemost_hip_pointwise_accumulate then launches two more kernels per piece behind the
+ * fold's, on the same stream over the same kept steps; the fold's own results are bitwise what they are without a
+ * tail, and a sampler without a tail launches nothing new.  pointwise_begin and pointwise_end drop the tail,
+ * pointwise_set does not touch it.  Device memory: n_keep * ceil(n_data / 64) * 64 * B doubles with
+ * B = 2 * max(1024, capacity rounded up to a power of two). */
+typedef struct {
+    uint64_t *count; /* [n_keep][n_data] */
+    double *values;  /* [n_keep][n_data][capacity], descending; slots >= count are unspecified on get, ignored on set */
+} apemost_hip_pointwise_tail_view; /* host arrays, both required */
+/* Needs an open pointwise fold that has no sample yet, or whose state apemost_hip_pointwise_set has just loaded (nothing
+ * accumulated since): the tail of those samples must then be loaded by pointwise_tail_set, and until it is
+ * apemost_hip_pointwise_accumulate returns APEMOST_HIP_ERR_INVALID.  A tail begun before is replaced.
+ * APEMOST_HIP_ERR_INVALID, before any device work: no pointwise_begin; a fold that has accumulated samples of its own;
+ * capacity outside [2, 4096]; more than 2^28 buffer slots (2 GiB) -- the message names the largest capacity that fits.
+ * APEMOST_HIP_ERR_UNSUPPORTED where pointwise_begin gives it.  A refused call leaves the fold, and a tail it has, as
+ * they were. */
+int apemost_hip_pointwise_tail_begin(apemost_hip_sampler *s, int32_t capacity);
+/* sorts every series and copies count and values out (synchronises with the accumulates issued so far); the state's
+ * selection is not changed by it.  APEMOST_HIP_ERR_INVALID without a tail or with a NULL array. */
+int apemost_hip_pointwise_tail_get(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v);
+/* loads a view saved by pointwise_tail_get into a tail begun with the same capacity on a fold of the same configuration
+ * (a resumed run); the values need not be sorted, every threshold is recomputed from them.  APEMOST_HIP_ERR_INVALID, before
+ * any device work, for a count above the capacity or a NaN among the first count values of a series. */
+int apemost_hip_pointwise_tail_set(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v);
+/* *capacity = the capacity of the open fold's tail, 0 where there is none */
+int apemost_hip_pointwise_tail_capacity(apemost_hip_sampler *s, int32_t *capacity);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
