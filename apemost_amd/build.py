@@ -36,15 +36,20 @@ MODEL_TUS = (0, 1, 2, 3, 8, 9, 10, 11)   # the built-in models and their variant
 
 
 def _sources():
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
+    """the ABI unit, the model unit and every header either may include: the kernel headers in csrc/, the parts of the
+    ABI unit in csrc/abi/ (host text only; their names differ from those in csrc/, _sources_sha1 keys by basename)
+    and the public header"""
+    abi = os.path.join(CSRC, "abi")
+    headers = sorted(os.path.join(d, f) for d in (CSRC, abi) for f in os.listdir(d) if f.endswith(".h")) + [
         os.path.join(ROOT, "include", "apemost_hip.h")]
     return os.path.join(CSRC, "apemost_hip.hip"), os.path.join(CSRC, "apemost_model.hip"), headers
 
 
 def build_hip(force=False, verbose=False):
     """libapemost_hip.so from nine translation units compiled side by side: the host side of the C ABI
-    (apemost_hip.hip) and one unit per likelihood model holding all of that model's kernels
-    (apemost_model.hip with -DAPEMOST_TU_MODEL=k).  Only what is older than its sources is rebuilt."""
+    (apemost_hip.hip, which includes its parts from csrc/abi/: the sampler and the on-device folds) and one unit per
+    likelihood model holding all of that model's kernels (apemost_model.hip with -DAPEMOST_TU_MODEL=k).  Only what is
+    older than its sources is rebuilt."""
     from concurrent.futures import ThreadPoolExecutor
     abi_src, model_src, headers = _sources()
     os.makedirs(OBJ, exist_ok=True)

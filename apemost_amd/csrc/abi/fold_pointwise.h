@@ -1,0 +1,384 @@
+// abi/fold_pointwise.h -- on-device pointwise log-likelihood (pt_pointwise.h) and its tail (pt_pointwise_tail.h), which
+// shares the fold's state (PointwiseFold and its PointwiseTailFold; protocol: abi/fold_common.h)
+#pragma once
+
+// a built-in model, or a user-supplied one with the pointwise hook
+#define POINTWISE_HAS_TERM(s, what)                                                                              \
+    do {                                                                                                        \
+        if ((s)->cfg.model == APEMOST_MODEL_USER) {                                                             \
+            const int rc_hooks = user_analysis(s);                                                              \
+            if (rc_hooks != APEMOST_HIP_OK)                                                                     \
+                return rc_hooks;                                                                                \
+            if (!(s)->ua.has_pointwise)                                                                         \
+                return fail(APEMOST_HIP_ERR_UNSUPPORTED,                                                        \
+                            what ": this user-supplied device model has no datum's term: it does not define "   \
+                                 "the hook apemost_user_pointwise (APEMOST_USER_POINTWISE, "                    \
+                                 "include/apemost_device_model.h)");                                            \
+        }                                                                                                       \
+    } while (0)
+
+constexpr int kPointwiseWords = 8; // origin, sum, sq, m_up, S_up, m_dn, S_dn, S2_dn
+
+static double pointwise_c(const apemost_hip_sampler *s) {
+    const double sigma = s->sh.consts.sigma;
+    const double t = -2.0 * sigma;
+    const double denom = t * sigma;
+    return 1.0 / denom;
+}
+
+extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg) {
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_begin");
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: config is NULL");
+    const int np = s->cfg.n_par, nd = s->cfg.n_data;
+    FOLD_TRY(fold_check_chains(s, "pointwise", cfg->n_keep, cfg->chains));
+    const u64 n_series = (u64)cfg->n_keep * (u64)nd;
+    if (n_series > ((u64)1 << 20))
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d chains x %d data: more than 2^20 series", cfg->n_keep,
+                    nd);
+    if (np > kPointwiseTile)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d parameters, more than %d", np, kPointwiseTile);
+    FOLD_TRY(fold_reset(s, s->pw));
+    PointwiseFold &f = s->pw;
+    f.n_keep = cfg->n_keep;
+    f.c = pointwise_c(s);
+    f.n = 0;
+    const size_t ns = (size_t)n_series, nk = (size_t)cfg->n_keep;
+    const bool user = s->cfg.model == APEMOST_MODEL_USER;
+    const size_t nc = user ? (size_t)s->cfg.n_cols : 1; // a user model's data: all of its columns, in d_x
+    FOLD_TRY(fold_alloc(s, f.mem, &f.d_chains, nk, false));
+    FOLD_TRY(fold_alloc(s, f.mem, &f.d_x, ns * nc, false));
+    if (!user)
+        FOLD_TRY(fold_alloc(s, f.mem, &f.d_y, ns, false));
+    FOLD_TRY(fold_alloc(s, f.mem, &f.d_state, kPointwiseWords * ns, true));
+    FOLD_TRY(fold_alloc(s, f.mem, &f.d_par, 2 * nk * np, true));
+    HIP_TRY(hipMemcpyAsync(f.d_chains, cfg->chains, nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    for (int k = 0; k < cfg->n_keep; k++) {
+        // columns 0 and 1 of the kept chain's own ladder (the data is stored by columns, ladder after ladder)
+        const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
+        const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * nd;
+        HIP_TRY(hipMemcpyAsync(f.d_x + (size_t)k * nc * nd, col0, nc * nd * sizeof(double), hipMemcpyDeviceToDevice,
+                               s->stream));
+        if (!user)
+            HIP_TRY(hipMemcpyAsync(f.d_y + (size_t)k * nd, col0 + nd, (size_t)nd * sizeof(double),
+                                   hipMemcpyDeviceToDevice, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's array is read until here)
+    f.open = true;
+    return APEMOST_HIP_OK;
+}
+
+// ---- the tail of the pointwise fold (pt_pointwise_tail.h) ----
+static PointwiseTailArgs pointwise_tail_args(const apemost_hip_sampler *s, bool force) {
+    PointwiseTailArgs t;
+    t.buf = s->pw.tail.d_buf;
+    t.slots = s->pw.tail.d_slots;
+    t.thr = s->pw.tail.d_thr;
+    t.capacity = s->pw.tail.capacity;
+    t.B = s->pw.tail.B;
+    t.n_data = s->cfg.n_data;
+    t.n_blocks = (s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+    t.force = force ? 1 : 0;
+    t.dense = nullptr;
+    t.count = nullptr;
+    return t;
+}
+
+static int pointwise_tail_compact(apemost_hip_sampler *s, bool force) {
+    const PointwiseTailArgs t = pointwise_tail_args(s, force);
+    const dim3 grid((unsigned)s->pw.n_keep * (unsigned)s->cfg.n_data), block(kTailThreads);
+    hipLaunchKernelGGL(pointwise_tail_compact_kernel, grid, block, (size_t)t.B * sizeof(unsigned long long), s->copy_stream, t);
+    HIP_TRY(hipGetLastError());
+    return APEMOST_HIP_OK;
+}
+
+// the kept steps of the fold piece `fold` (already launched), in tail pieces: append, then compact, on copy_stream
+static int pointwise_tail_pieces(apemost_hip_sampler *s, const PointwiseArgs &fold) {
+    const PointwiseTailArgs t = pointwise_tail_args(s, false);
+    const unsigned int piece = (unsigned int)tail_piece(t.capacity);
+    for (unsigned int k0 = 0; k0 < fold.n; k0 += piece) {
+        PointwiseArgs a = fold;
+        a.skip = fold.skip + (u64)k0 * fold.thin;
+        a.n = fold.n - k0 < piece ? fold.n - k0 : piece;
+        a.n0 = fold.n0 + k0;
+        const dim3 grid((unsigned)a.n_blocks * (unsigned)a.n_keep), block(kPointwiseWave);
+        PointwiseTailArgs tt = t;
+        if (s->cfg.model == APEMOST_MODEL_USER) {
+            void *params[] = {&a, &tt};
+            HIP_TRY(user_launch(s->ua.pointwise_tail_append, grid.x, block.x, 0, s->copy_stream, params));
+        } else {
+            with_builtin_model(s->cfg.model, [&](auto m) {
+                hipLaunchKernelGGL(pointwise_tail_append_kernel<decltype(m)::value>, grid, block, 0, s->copy_stream, a, tt);
+            });
+        }
+        HIP_TRY(hipGetLastError());
+        FOLD_TRY(pointwise_tail_compact(s, false));
+    }
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
+                                                uint64_t skip, uint64_t thin) {
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_accumulate");
+    PointwiseFold &f = s->pw;
+    u64 kept;
+    FOLD_TRY(fold_accumulate_check("pointwise", f.open, d_samples, n_steps, skip, thin, &kept));
+    if (f.tail.awaits_set)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: the tail was begun on a fold of %llu samples that "
+                    "pointwise_set loaded: pointwise_tail_set must load the tail of those samples first",
+                    (unsigned long long)f.n);
+    if (kept == 0)
+        return APEMOST_HIP_OK;
+    FOLD_TRY(fold_order_behind_stream(s));
+    const size_t ns = (size_t)f.n_keep * s->cfg.n_data;
+    for (u64 k0 = 0; k0 < kept; k0 += kPointwisePiece) {
+        PointwiseArgs a;
+        a.rows = d_samples;
+        a.n_chains = s->cfg.n_chains;
+        a.n_par = s->cfg.n_par;
+        a.n_keep = f.n_keep;
+        a.chains = f.d_chains;
+        a.skip = skip + k0 * thin;
+        a.thin = thin;
+        a.n = (unsigned int)(kept - k0 < (u64)kPointwisePiece ? kept - k0 : (u64)kPointwisePiece);
+        a.n0 = f.n;
+        a.n_data = s->cfg.n_data;
+        a.n_blocks = (s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+        a.x = f.d_x;
+        a.y = f.d_y;
+        a.c = f.c;
+        a.n_cols = s->cfg.n_cols;
+        a.sigma = s->sh.consts.sigma;
+        a.hmin = s->sh.consts.hmin;
+        a.origin = f.d_state;
+        a.sum = f.d_state + ns;
+        a.sq = f.d_state + 2 * ns;
+        a.m_up = f.d_state + 3 * ns;
+        a.S_up = f.d_state + 4 * ns;
+        a.m_dn = f.d_state + 5 * ns;
+        a.S_dn = f.d_state + 6 * ns;
+        a.S2_dn = f.d_state + 7 * ns;
+        a.par_origin = f.d_par;
+        a.par_sum = f.d_par + (size_t)f.n_keep * s->cfg.n_par;
+        const dim3 grid((unsigned)(a.n_blocks + 1) * (unsigned)a.n_keep), block(kPointwiseWave);
+        if (s->cfg.model == APEMOST_MODEL_USER) {
+            void *params[] = {&a};
+            HIP_TRY(user_launch(s->ua.pointwise_fold, grid.x, block.x, 0, s->copy_stream, params));
+        } else {
+            with_builtin_model(s->cfg.model, [&](auto m) {
+                hipLaunchKernelGGL(pointwise_fold_kernel<decltype(m)::value>, grid, block, 0, s->copy_stream, a);
+            });
+        }
+        HIP_TRY(hipGetLastError());
+        if (f.tail.capacity > 0)
+            FOLD_TRY(pointwise_tail_pieces(s, a));
+        f.n += a.n;
+        f.n_set = false;
+    }
+    return APEMOST_HIP_OK;
+}
+
+static int pointwise_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v, bool up) {
+    PointwiseFold &f = s->pw;
+    FOLD_TRY(fold_xfer_check("pointwise", f.open, v, up));
+    const size_t nk = (size_t)f.n_keep, ns = nk * s->cfg.n_data, np = (size_t)s->cfg.n_par;
+    FOLD_TRY(fold_order_behind_stream(s));
+    const FoldCopy copy{s, up};
+    double *const host[kPointwiseWords] = {v->origin, v->sum, v->sq, v->m_up, v->S_up, v->m_dn, v->S_dn, v->S2_dn};
+    for (int q = 0; q < kPointwiseWords; q++)
+        FOLD_TRY(copy(f.d_state + (size_t)q * ns, host[q], ns * sizeof(double)));
+    FOLD_TRY(copy(f.d_par, v->par_origin, nk * np * sizeof(double)));
+    FOLD_TRY(copy(f.d_par + nk * np, v->par_sum, nk * np * sizeof(double)));
+    FOLD_TRY(fold_xfer_wait(s));
+    fold_xfer_count(f.n, v->n, up);
+    if (up && v->n)
+        f.n_set = true;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_get(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_get");
+    return pointwise_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_pointwise_set(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_set");
+    return pointwise_xfer(s, v, true);
+}
+
+extern "C" int apemost_hip_pointwise_end(apemost_hip_sampler *s) {
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_end");
+    return fold_reset(s, s->pw);
+}
+
+// padded series (64 per block of data) times the slots of a series' buffer
+static u64 pointwise_tail_slots(const apemost_hip_sampler *s, int B) {
+    const u64 n_blocks = ((u64)s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+    return (u64)s->pw.n_keep * n_blocks * kPointwiseWave * (u64)B;
+}
+
+extern "C" int apemost_hip_pointwise_tail_begin(apemost_hip_sampler *s, int32_t capacity) {
+    if (!s)
+        return fail(APEMOST_HIP_ERR_INVALID, "sampler is NULL");
+    if (capacity < 2 || capacity > kTailMaxCapacity)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: capacity %d outside [2,%d]", capacity, kTailMaxCapacity);
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_tail_begin");
+    PointwiseFold &f = s->pw;
+    if (!f.open)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: no pointwise_begin");
+    if (f.n > 0 && !f.n_set)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: the fold has accumulated %llu samples whose tail is "
+                    "lost: begin the tail before the first accumulate, or right behind pointwise_set",
+                    (unsigned long long)f.n);
+    const u64 limit = (u64)1 << 28;
+    const int B = tail_buffer(capacity);
+    if (pointwise_tail_slots(s, B) > limit) {
+        int fits = 0; // the largest capacity whose buffers fit
+        for (int b = kTailMaxB; b >= 2 * kTailMinP && !fits; b >>= 1)
+            if (pointwise_tail_slots(s, b) <= limit)
+                fits = b / 2;
+        if (fits)
+            return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: %d chains x %d data (in blocks of 64) x %d slots "
+                        "for capacity %d: more than 2^28 slots (2 GiB); the largest capacity that fits is %d",
+                        f.n_keep, s->cfg.n_data, B, capacity, fits);
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: %d chains x %d data (in blocks of 64) x %d slots for "
+                    "capacity %d: more than 2^28 slots (2 GiB); the largest capacity that fits is 0: no capacity fits, "
+                    "keep fewer chains", f.n_keep, s->cfg.n_data, B, capacity);
+    }
+    FOLD_TRY(fold_reset(s, f.tail));
+    PointwiseTailFold &t = f.tail;
+    const size_t ns = (size_t)f.n_keep * s->cfg.n_data;
+    const int rc = [&]() -> int {
+        FOLD_TRY(fold_alloc(s, t.mem, &t.d_buf, (size_t)pointwise_tail_slots(s, B), false));
+        FOLD_TRY(fold_alloc(s, t.mem, &t.d_slots, ns, true));
+        FOLD_TRY(fold_alloc(s, t.mem, &t.d_thr, ns, true));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        return APEMOST_HIP_OK;
+    }();
+    if (rc != APEMOST_HIP_OK) { // the fold stays as it was, without a tail
+        fold_free(t);
+        return rc;
+    }
+    t.capacity = capacity;
+    t.B = B;
+    t.awaits_set = f.n > 0;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_tail_capacity(apemost_hip_sampler *s, int32_t *capacity) {
+    if (!s)
+        return fail(APEMOST_HIP_ERR_INVALID, "sampler is NULL");
+    if (!capacity)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_capacity: capacity is NULL");
+    *capacity = s->pw.open ? s->pw.tail.capacity : 0;
+    return APEMOST_HIP_OK;
+}
+
+// A tail's view holds dense arrays, which a scatter or gather kernel takes to or from the buffers: its xfer shares
+// the stream order with the other folds', not the copies.
+static int pointwise_tail_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v, bool up) {
+    CHECK_S(s);
+    const char *what = up ? "set" : "get";
+    if (!s->pw.open || s->pw.tail.capacity == 0)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_%s: no pointwise_tail_begin", what);
+    if (!v || !v->count || !v->values)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_%s: the view or one of its arrays is NULL", what);
+    const size_t ns = (size_t)s->pw.n_keep * s->cfg.n_data, cap = (size_t)s->pw.tail.capacity;
+    if (up)
+        for (size_t q = 0; q < ns; q++) {
+            if (v->count[q] > cap)
+                return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_set: count[%zu] = %llu, more than the capacity %zu", q,
+                            (unsigned long long)v->count[q], cap);
+            for (size_t j = 0; j < (size_t)v->count[q]; j++)
+                if (v->values[q * cap + j] != v->values[q * cap + j])
+                    return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_set: values[%zu][%zu] is NaN: a tail holds none", q, j);
+        }
+    FOLD_TRY(fold_order_behind_stream(s));
+    PointwiseTailArgs t = pointwise_tail_args(s, true);
+    FoldScratch scratch;
+    const int rc = [&]() -> int { // (whatever fails, the stream is waited for before the scratch goes)
+        FOLD_TRY(fold_alloc(s, scratch, &t.dense, ns * cap, false));
+        FOLD_TRY(fold_alloc(s, scratch, &t.count, ns, false));
+        const dim3 grid((unsigned)ns, (unsigned)((cap + kTailThreads - 1) / kTailThreads)), block(kTailThreads);
+        if (up) {
+            HIP_TRY(hipMemcpyAsync(t.dense, v->values, ns * cap * sizeof(double), hipMemcpyHostToDevice, s->copy_stream));
+            HIP_TRY(hipMemcpyAsync(t.count, v->count, ns * sizeof(unsigned long long), hipMemcpyHostToDevice, s->copy_stream));
+            hipLaunchKernelGGL(pointwise_tail_scatter_kernel, grid, block, 0, s->copy_stream, t);
+            HIP_TRY(hipGetLastError());
+            FOLD_TRY(pointwise_tail_compact(s, true)); // sorts what was loaded and sets every threshold from it
+        } else {
+            FOLD_TRY(pointwise_tail_compact(s, true));
+            hipLaunchKernelGGL(pointwise_tail_gather_kernel, grid, block, 0, s->copy_stream, t);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(v->values, t.dense, ns * cap * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
+            HIP_TRY(hipMemcpyAsync(v->count, t.count, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->copy_stream));
+        }
+        return APEMOST_HIP_OK;
+    }();
+    const hipError_t sync = hipStreamSynchronize(s->copy_stream);
+    FOLD_TRY(rc);
+    HIP_TRY(sync);
+    if (up)
+        s->pw.tail.awaits_set = false;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_tail_get(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v) {
+    return pointwise_tail_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_pointwise_tail_set(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v) {
+    return pointwise_tail_xfer(s, v, true);
+}
+
+// the term of every datum of ladder `ladder` under n parameter rows, by the fold's own function: no fold need be open
+extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int32_t ladder, int32_t n,
+                                                    const double *params, double *out) {
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_loglike");
+    const int np = s->cfg.n_par, nd = s->cfg.n_data;
+    if (ladder < 0 || ladder >= (s->batch ? s->n_ladders : 1))
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: ladder %d outside [0,%d)", ladder,
+                    s->batch ? s->n_ladders : 1);
+    if (n < 1 || !params || !out || (u64)n * (u64)nd > ((u64)1 << 26))
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: %d rows x %d data, or a NULL array", n, nd);
+    FoldScratch scratch;
+    double *d_par = nullptr, *d_out = nullptr;
+    const int rc = [&]() -> int { // (whatever fails, the stream is waited for before the scratch goes)
+        FOLD_TRY(fold_alloc(s, scratch, &d_par, (size_t)n * np, false));
+        FOLD_TRY(fold_alloc(s, scratch, &d_out, (size_t)n * nd, false));
+        HIP_TRY(hipMemcpyAsync(d_par, params, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        const dim3 grid((unsigned)((nd + kPointwiseWave - 1) / kPointwiseWave) * (unsigned)n), block(kPointwiseWave);
+        // the ladder's columns 0 and 1 (the data is stored by columns, ladder after ladder)
+        const double *x = s->d.data + (size_t)ladder * s->cfg.n_cols * nd, *y = x + nd;
+        const double c = pointwise_c(s);
+        if (s->cfg.model == APEMOST_MODEL_USER) { // all n_cols columns of the ladder's rows
+            int np_ = np, nd_ = nd, nc = s->cfg.n_cols;
+            double sigma = s->sh.consts.sigma, hmin = s->sh.consts.hmin;
+            void *params_[] = {&d_par, &np_, &nd_, &nc, &x, &sigma, &hmin, &d_out};
+            HIP_TRY(user_launch(s->ua.pointwise_loglike, grid.x, block.x, 0, s->stream, params_));
+        } else {
+            with_builtin_model(s->cfg.model, [&](auto m) {
+                hipLaunchKernelGGL(pointwise_loglike_kernel<decltype(m)::value>, grid, block, 0, s->stream, d_par, np, nd, x,
+                                   y, c, d_out);
+            });
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * nd * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        return APEMOST_HIP_OK;
+    }();
+    const hipError_t sync = hipStreamSynchronize(s->stream);
+    FOLD_TRY(rc);
+    HIP_TRY(sync);
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_loglike(apemost_hip_sampler *s, int32_t n, const double *params, double *out) {
+    return apemost_hip_pointwise_loglike_ladder(s, 0, n, params, out);
+}

@@ -255,188 +255,7 @@ static hipError_t dispatch(int model, int waves, const OccupancyOp<false> &f) {
     return dispatch_any(model, waves, op);
 }
 
-static thread_local std::string g_last_error;
-
-static int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                            \
-    do {                                                                                         \
-        hipError_t err__ = (expr);                                                               \
-        if (err__ != hipSuccess)                                                                 \
-            return fail(APEMOST_HIP_ERR_RUNTIME, "%s failed: %s (%s:%d)", #expr,                 \
-                        hipGetErrorString(err__), __FILE__, __LINE__);                           \
-    } while (0)
-
-struct apemost_hip_sampler {
-    apemost_hip_config cfg;
-    DevArrays d;
-    ChainShape sh;
-    int waves;
-    bool producers; // candidate-producer wavefronts in the round / calibrate kernels
-    bool lds_data;
-    size_t lds_bytes, lds_fixed_bytes;
-    bool resident_ok; // the whole grid of the round kernel fits the device at once ...
-    bool resident_lds, resident_plain; // ... with / without the data vector staged in LDS
-    int cur;
-    u64 round;
-    int swap_pending;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    u64 launches, launches_at_begin;
-    std::vector<void *> allocations;
-    // a calibration in progress (calibrate_begin .. calibrate_end): launched in segments
-    struct {
-        bool open;      // between begin and end
-        bool in_flight; // a segment has been launched and its records not collected yet
-        bool cancelled;
-        int first, count, burn_in_only, capacity, progress_slot, progress_cap;
-        apemost_hip_calib_config cfg;
-        CalibRec *d_rec;
-        double *d_orig, *d_progress;
-        int *d_list;
-        CalibRec *h_rec; // pinned [capacity]
-        int *h_list;     // pinned [capacity]: slots still calibrating
-        int n_active;
-        hipEvent_t ev;
-        u64 segments, launches_by_waves[9];
-        double seconds_by_waves[9]; // wall time of the segments of each workgroup shape (launch to collection)
-        std::chrono::steady_clock::time_point segment_start;
-        int segment_waves;
-    } cal;
-    unsigned big_lds_set; // bit w: the LDS opt-in of the w-wave kernels has been made
-    // APEMOST_MODEL_USER: the kernels of the user's likelihood, compiled by hiprtc at create time
-    // (indexed by the waves per chain of the two-phase kernels: 1, 2, 4, 8; with
-    // APEMOST_HIP_FLAG_USER_ONE_BARRIER also the one-barrier kernels of 4 and 8 likelihood waves, which decide
-    // through the user's finish() instead of the built-in models' threshold form)
-    struct {
-        hipModule_t module;
-        hipFunction_t round[9], calibrate[9], calc_model[9], loglike[9];
-        hipFunction_t round_ob[9], calibrate_ob[9]; // (calibrate_ob: not for the variant instantiations)
-    } user;
-    // ... and the kernels of its optional hooks (pt_user_fold.h), a second module compiled on the first predict_* or
-    // pointwise_* call (user_analysis): the functions of an absent hook stay null
-    struct {
-        bool ready; // the hooks are known (and, where there is one, the module is loaded)
-        bool has_curve, has_pointwise;
-        hipModule_t module;
-        hipFunction_t predict_fold, predict_fold_hist, predict_curve, pointwise_fold, pointwise_loglike, pointwise_tail_append;
-        double compile_seconds; // hiprtc's time for this sampler's analysis module (0: from the process's cache)
-    } ua;
-    std::string user_source, user_shown; // the model's text as user_model_build read it, its path as a C string literal
-    // edge records for in-process shard exchanges (created on first use), one set per side (0 = lower edge,
-    // 1 = upper edge): under the even-odd schedule an interior shard exchanges on both edges before one launch
-    double *edge_out[2], *edge_in[2];
-    hipEvent_t ev_exported[2], ev_imported[2];
-    hipStream_t copy_stream; // drains sample rows while the next launch runs (created on first use)
-    hipEvent_t ev_copy;
-    u64 *h_word;             // pinned copy of the launch error word, refreshed by every async read
-    bool one_barrier;    // stepping launches use pt_round_ob_kernel
-    bool ob_helper;      // ... in its form with a helper wavefront (see ob_wants_helper), where the betas allow it:
-    bool betas_split_ok; // every beta on the device is > 0 with a finite 1/beta (betas_allow_split; true until betas arrive)
-    int cus;             // compute units of the device
-    int kmodel;          // template argument of this sampler's kernels: cfg.model, + kVariantModel when a
-                         // non-default proposal law or swap schedule is asked for (pt_device.h)
-    bool cooperative;    // multi-round launches through hipLaunchCooperativeKernel
-    bool handoff_failed; // an in-launch hand-off timed out once: single-round launches from then on
-    double user_compile_seconds; // hiprtc's time for this sampler's user model (0: taken from the process's cache)
-    double *rwm_keep;            // APEMOST_HIP_FLAG_RWM: what the extra step of a round must not be seen to change
-    bool in_rwm;
-    // the run summary (apemost_hip_summary_begin .. end): accumulated by summary_kernel on copy_stream
-    // a ladder batch (apemost_hip_create_batch): n_ladders independent ladders of `per_ladder` chains in one grid;
-    // cfg.n_chains = cfg.n_chains_global = their product, sh.n_global = per_ladder, cfg.seed = seeds[0]
-    bool batch;
-    bool track; // APEMOST_HIP_FLAG_TRACK_REPLICAS: the flow words behind the ladder words exist
-    int n_ladders, per_ladder;
-    std::vector<u64> seeds;        // [n_ladders] (empty for an ordinary sampler)
-    std::vector<double> x_abs_max; // [n_ladders] of each ladder's data
-    struct {
-        bool open;
-        int n_hist, nbins;
-        u64 bs, max_batches;
-        u64 n; // kept samples so far (the host knows it without a sync)
-        double *d_lo, *d_hi, *d_prob_sum, *d_batch;
-        u64 *d_hist;
-    } sum;
-    // on-device peaks (apemost_hip_peaks_begin .. end): the kept chains' parameter columns, appended on copy_stream
-    struct {
-        bool open;
-        int n_keep;
-        u64 capacity;
-        u64 n; // samples stored per column (the host knows it without a sync)
-        int *d_chains;
-        double *d_lo, *d_hi, *d_cols;
-    } pk;
-    // on-device joint marginals (apemost_hip_joint_begin .. end): pair histograms and moments, on copy_stream
-    struct {
-        bool open;
-        int n_keep, nbins, n_pairs;
-        u64 chunk; // kept steps staged per launch
-        u64 n;     // kept samples so far (the host knows it without a sync)
-        int *d_chains, *d_pairs;
-        double *d_lo, *d_hi, *d_vals, *d_origin, *d_sum, *d_cross;
-        unsigned short *d_bins;
-        u64 *d_counts;
-    } jt;
-    // on-device evidence fold (apemost_hip_evidence_begin .. end): moments, batch sums and log-sum-exps of column
-    // n_par+1 of every chain, on copy_stream
-    struct {
-        bool open;
-        u64 bs, max_batches;
-        u64 chunk; // kept steps staged per launch
-        u64 n;     // kept samples so far (the host knows it without a sync)
-        double *d_coef, *d_vals, *d_origin, *d_sum, *d_sq, *d_batch, *d_m, *d_S;
-    } ev;
-    // on-device autocorrelation (apemost_hip_autocorr_begin .. end): lag sums of kept chains' columns, on copy_stream
-    struct {
-        bool open;
-        int n_keep, n_cols, max_lag;
-        u64 chunk; // kept steps staged per launch
-        u64 n;     // kept samples so far (the host knows it without a sync)
-        int *d_chains, *d_cols;
-        double *d_buf, *d_origin, *d_sum, *d_lag, *d_head, *d_tail;
-    } ac;
-    // on-device posterior predictive (apemost_hip_predict_begin .. end): the model curve of kept chains' samples at
-    // n_x abscissae, on copy_stream
-    struct {
-        bool open;
-        int n_keep, n_x, nbins, points;
-        int n_cols; // columns of the rows in d_x: 1, or the n_cols of a user model
-        double lo, hi;
-        u64 n; // kept samples so far (the host knows it without a sync)
-        int *d_chains;
-        double *d_x, *d_origin, *d_sum, *d_sq, *d_vmin, *d_vmax, *d_best_prob, *d_best_params;
-        u64 *d_hist, *d_best_n;
-    } pr;
-    // on-device pointwise log-likelihood (apemost_hip_pointwise_begin .. end): the term of every datum under the kept
-    // chains' samples, on copy_stream
-    struct {
-        bool open;
-        int n_keep;
-        double c; // 1 / (-2 sigma^2)
-        u64 n;    // kept samples so far (the host knows it without a sync)
-        int *d_chains;
-        double *d_x, *d_y;    // [n_keep][n_data] (a user model: d_x [n_keep][n_cols][n_data], no d_y)
-        double *d_state;      // the eight [n_keep][n_data] words, one after the other (kPointwiseWords)
-        double *d_par;        // par_origin, par_sum: [n_keep][n_par] each
-        bool n_set;           // n is what pointwise_set put there: nothing has been accumulated since
-        // its tail (apemost_hip_pointwise_tail_begin, pt_pointwise_tail.h); capacity 0: none
-        struct {
-            int capacity, B;
-            bool awaits_set; // begun on a fold whose state was set: no accumulate before tail_set
-            double *d_buf;               // [n_keep][n_blocks][B][64]
-            unsigned int *d_slots;       // [n_keep][n_data]
-            unsigned long long *d_thr;   // [n_keep][n_data]
-        } tail;
-    } pw;
-};
+#include "abi/sampler.h"
 
 extern "C" const char *apemost_hip_last_error(void) { return g_last_error.c_str(); }
 extern "C" int apemost_hip_abi_version(void) { return APEMOST_HIP_ABI_VERSION; }
@@ -538,128 +357,6 @@ static int choose_waves(const apemost_hip_config &c) {
     while (by_data < 8 && c.n_data >= by_data * 2 * kWave * 2)
         by_data *= 2;
     return by_chip < by_data ? by_chip : by_data;
-}
-
-// the run summary's device arrays (the caller has synchronised the streams that use them)
-static void summary_free(apemost_hip_sampler *s) {
-    for (void *p : {(void *)s->sum.d_lo, (void *)s->sum.d_hi, (void *)s->sum.d_prob_sum, (void *)s->sum.d_batch,
-                    (void *)s->sum.d_hist})
-        if (p)
-            hipFree(p);
-    s->sum = {};
-}
-
-static void peaks_free(apemost_hip_sampler *s) {
-    for (void *p : {(void *)s->pk.d_chains, (void *)s->pk.d_lo, (void *)s->pk.d_hi, (void *)s->pk.d_cols})
-        if (p)
-            hipFree(p);
-    s->pk = {};
-}
-
-static void joint_free(apemost_hip_sampler *s) {
-    for (void *p : {(void *)s->jt.d_chains, (void *)s->jt.d_pairs, (void *)s->jt.d_lo, (void *)s->jt.d_hi,
-                    (void *)s->jt.d_vals, (void *)s->jt.d_origin, (void *)s->jt.d_sum, (void *)s->jt.d_cross,
-                    (void *)s->jt.d_bins, (void *)s->jt.d_counts})
-        if (p)
-            hipFree(p);
-    s->jt = {};
-}
-
-static void evidence_free(apemost_hip_sampler *s) {
-    for (double *p : {s->ev.d_coef, s->ev.d_vals, s->ev.d_origin, s->ev.d_sum, s->ev.d_sq, s->ev.d_batch, s->ev.d_m,
-                      s->ev.d_S})
-        if (p)
-            hipFree(p);
-    s->ev = {};
-}
-
-static void autocorr_free(apemost_hip_sampler *s) {
-    for (int *p : {s->ac.d_chains, s->ac.d_cols})
-        if (p)
-            hipFree(p);
-    for (double *p : {s->ac.d_buf, s->ac.d_origin, s->ac.d_sum, s->ac.d_lag, s->ac.d_head, s->ac.d_tail})
-        if (p)
-            hipFree(p);
-    s->ac = {};
-}
-
-static void predict_free(apemost_hip_sampler *s) {
-    for (void *p : {(void *)s->pr.d_chains, (void *)s->pr.d_x, (void *)s->pr.d_origin, (void *)s->pr.d_sum,
-                    (void *)s->pr.d_sq, (void *)s->pr.d_vmin, (void *)s->pr.d_vmax, (void *)s->pr.d_best_prob,
-                    (void *)s->pr.d_best_params, (void *)s->pr.d_hist, (void *)s->pr.d_best_n})
-        if (p)
-            hipFree(p);
-    s->pr = {};
-}
-
-static void pointwise_tail_free(apemost_hip_sampler *s) {
-    for (void *p : {(void *)s->pw.tail.d_buf, (void *)s->pw.tail.d_slots, (void *)s->pw.tail.d_thr})
-        if (p)
-            hipFree(p);
-    s->pw.tail = {};
-}
-
-static void pointwise_free(apemost_hip_sampler *s) {
-    pointwise_tail_free(s);
-    for (void *p : {(void *)s->pw.d_chains, (void *)s->pw.d_x, (void *)s->pw.d_y, (void *)s->pw.d_state,
-                    (void *)s->pw.d_par})
-        if (p)
-            hipFree(p);
-    s->pw = {};
-}
-
-// everything a sampler owns on the device; safe on a half-built sampler
-static void release(apemost_hip_sampler *s) {
-    if (s->stream)
-        hipStreamSynchronize(s->stream);
-    for (void *p : s->allocations)
-        hipFree(p);
-    if (s->cal.d_rec)
-        hipFree(s->cal.d_rec);
-    if (s->cal.d_orig)
-        hipFree(s->cal.d_orig);
-    if (s->cal.d_progress)
-        hipFree(s->cal.d_progress);
-    if (s->cal.d_list)
-        hipFree(s->cal.d_list);
-    if (s->cal.h_rec)
-        hipHostFree(s->cal.h_rec);
-    if (s->cal.h_list)
-        hipHostFree(s->cal.h_list);
-    if (s->cal.ev)
-        hipEventDestroy(s->cal.ev);
-    if (s->user.module)
-        hipModuleUnload(s->user.module);
-    if (s->ua.module)
-        hipModuleUnload(s->ua.module);
-    if (s->copy_stream) {
-        hipStreamSynchronize(s->copy_stream);
-        hipStreamDestroy(s->copy_stream);
-    }
-    summary_free(s); // (its kernels ran on copy_stream)
-    peaks_free(s);
-    joint_free(s);
-    evidence_free(s);
-    autocorr_free(s);
-    predict_free(s);
-    pointwise_free(s);
-    if (s->ev_copy)
-        hipEventDestroy(s->ev_copy);
-    for (int k = 0; k < 2; k++) {
-        if (s->ev_exported[k])
-            hipEventDestroy(s->ev_exported[k]);
-        if (s->ev_imported[k])
-            hipEventDestroy(s->ev_imported[k]);
-    }
-    if (s->h_word)
-        hipHostFree(s->h_word);
-    if (s->ev0)
-        hipEventDestroy(s->ev0);
-    if (s->ev1)
-        hipEventDestroy(s->ev1);
-    if (s->stream)
-        hipStreamDestroy(s->stream);
-    delete s;
 }
 
 // ---- APEMOST_MODEL_USER: the user's likelihood compiled into the two-phase kernels at run time ----
@@ -1359,13 +1056,6 @@ extern "C" int apemost_hip_destroy(apemost_hip_sampler *s) {
     release(s);
     return APEMOST_HIP_OK;
 }
-
-#define CHECK_S(s)                                                                               \
-    do {                                                                                         \
-        if (!(s))                                                                                \
-            return fail(APEMOST_HIP_ERR_INVALID, "sampler is NULL");                             \
-        HIP_TRY(hipSetDevice((s)->cfg.device));                                                  \
-    } while (0)
 
 // Words the kernels raise instead of spinning for ever: 1 = an in-launch swap hand-off timed out (a
 // partner workgroup was not resident), 2 = an in-launch swap picked a pair that straddles the shard,
@@ -2125,1754 +1815,15 @@ extern "C" int apemost_hip_samples_wait(apemost_hip_sampler *s) {
     return APEMOST_HIP_OK;
 }
 
-// ---- run summary (pt_summary.h) ----
-// batches of batch_means_error() closed after n samples: sample n (counted from 1) closes one when
-// n % bs == bs - 1 -- for bs >= 2 the first batch holds bs - 1 samples, every later one bs
-static u64 summary_closed(u64 n, u64 bs) { return bs == 1 ? n : (n + 1) / bs; }
-// samples still to come before the batch that is open after n samples closes (1 .. bs)
-static u64 summary_left(u64 n, u64 bs) {
-    const u64 m = (bs - (n + 1) % bs) % bs;
-    return m == 0 ? bs : m;
-}
-
-static int ensure_copy_stream(apemost_hip_sampler *s) {
-    if (!s->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_copy, hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc((void **)&s->h_word, sizeof(u64), hipHostMallocDefault));
-        *s->h_word = 0;
-    }
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_summary_begin(apemost_hip_sampler *s, const apemost_hip_summary_config *cfg) {
-    CHECK_S(s);
-    if (!cfg)
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: config is NULL");
-    const int np = s->cfg.n_par;
-    if (cfg->nbins < 1 || cfg->nbins > kSummaryMaxBins)
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: nbins %d outside [1,%d]", cfg->nbins, kSummaryMaxBins);
-    if (cfg->n_hist_chains < 0 || cfg->n_hist_chains > s->cfg.n_chains)
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: n_hist_chains %d outside [0,%d]", cfg->n_hist_chains,
-                    s->cfg.n_chains);
-    if (cfg->batch_size < 1)
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: batch_size must be >= 1");
-    if (cfg->n_hist_chains > 0 && (!cfg->lo || !cfg->hi))
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: histograms need lo and hi");
-    for (int p = 0; p < np && cfg->lo && cfg->hi; p++)
-        if (!std::isfinite(cfg->lo[p]) || !std::isfinite(cfg->hi[p]) || !(cfg->lo[p] < cfg->hi[p]) ||
-            !std::isfinite(cfg->hi[p] - cfg->lo[p])) // (a width that overflows: the bin guess divides by it)
-            return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: parameter %d: range [%g, %g] invalid", p, cfg->lo[p],
-                        cfg->hi[p]);
-    const size_t n_hp = (size_t)cfg->n_hist_chains * np;
-    if (cfg->max_batches > ((size_t)1 << 40) || (n_hp > 0 && cfg->max_batches + 1 > ((size_t)1 << 40) / n_hp))
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_begin: max_batches %llu too large",
-                    (unsigned long long)cfg->max_batches);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a summary before this one may still be accumulating
-    summary_free(s);
-    s->sum.n_hist = cfg->n_hist_chains;
-    s->sum.nbins = cfg->nbins;
-    s->sum.bs = cfg->batch_size;
-    s->sum.max_batches = cfg->max_batches;
-    s->sum.n = 0;
-    const size_t nb = n_hp * (cfg->max_batches + 1), nh = n_hp * cfg->nbins;
-    HIP_TRY(hipMalloc((void **)&s->sum.d_prob_sum, s->cfg.n_chains * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->sum.d_lo, np * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->sum.d_hi, np * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->sum.d_batch, (nb > 0 ? nb : 1) * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->sum.d_hist, (nh > 0 ? nh : 1) * sizeof(u64)));
-    HIP_TRY(hipMemsetAsync(s->sum.d_prob_sum, 0, s->cfg.n_chains * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->sum.d_batch, 0, (nb > 0 ? nb : 1) * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->sum.d_hist, 0, (nh > 0 ? nh : 1) * sizeof(u64), s->stream));
-    HIP_TRY(hipMemsetAsync(s->sum.d_lo, 0, np * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->sum.d_hi, 0, np * sizeof(double), s->stream));
-    if (cfg->lo && cfg->hi) {
-        HIP_TRY(hipMemcpyAsync(s->sum.d_lo, cfg->lo, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(s->sum.d_hi, cfg->hi, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->sum.open = true;
-    return APEMOST_HIP_OK;
-}
-
-// Queued on copy_stream behind everything launched so far on the sampler's stream, like
-// apemost_hip_samples_read_async: launches issued after this call overlap with it, and
-// apemost_hip_samples_wait / apemost_hip_summary_get wait for it -- the caller does one of them before
-// d_samples is written again.
-extern "C" int apemost_hip_summary_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
-                                              uint64_t skip, uint64_t thin) {
-    CHECK_S(s);
-    if (!s->sum.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_accumulate: no summary_begin");
-    if (thin < 1 || (!d_samples && n_steps > 0))
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_accumulate: bad arguments");
-    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
-    if (summary_closed(s->sum.n + kept, s->sum.bs) > s->sum.max_batches)
-        return fail(APEMOST_HIP_ERR_INVALID,
-                    "summary_accumulate: %llu samples would close batch %llu, beyond max_batches = %llu",
-                    (unsigned long long)(s->sum.n + kept), (unsigned long long)summary_closed(s->sum.n + kept, s->sum.bs),
-                    (unsigned long long)s->sum.max_batches);
-    if (kept == 0)
-        return APEMOST_HIP_OK;
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const int n_hp = s->sum.n_hist * s->cfg.n_par;
-    const int grid = n_hp + (s->cfg.n_chains + kSummaryThreads - 1) / kSummaryThreads;
-    // (the LDS bins count in 32 bits: at most 2^31 samples per launch)
-    for (u64 k0 = 0; k0 < kept; k0 += (u64)1 << 31) {
-        SummaryArgs a;
-        a.rows = d_samples;
-        a.n_chains = s->cfg.n_chains;
-        a.n_par = s->cfg.n_par;
-        a.skip = skip + k0 * thin;
-        a.thin = thin;
-        a.n_kept = kept - k0 < ((u64)1 << 31) ? kept - k0 : (u64)1 << 31;
-        a.n_hist = s->sum.n_hist;
-        a.nbins = s->sum.nbins;
-        a.lo = s->sum.d_lo;
-        a.hi = s->sum.d_hi;
-        a.bs = s->sum.bs;
-        a.left = summary_left(s->sum.n, s->sum.bs);
-        a.n_closed = summary_closed(s->sum.n, s->sum.bs);
-        a.prob_sum = s->sum.d_prob_sum;
-        a.hist = s->sum.d_hist;
-        a.batch = s->sum.d_batch;
-        a.batch_stride = s->sum.max_batches + 1;
-        hipLaunchKernelGGL(summary_kernel, dim3(grid), dim3(kSummaryThreads), 0, s->copy_stream, a);
-        HIP_TRY(hipGetLastError());
-        s->sum.n += a.n_kept;
-    }
-    return APEMOST_HIP_OK;
-}
-
-static int summary_xfer(apemost_hip_sampler *s, const apemost_hip_summary_view *v, bool up) {
-    if (!s->sum.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "summary_%s: no summary_begin", up ? "set" : "get");
-    if (!v)
-        return fail(APEMOST_HIP_ERR_INVALID, "summary view is NULL");
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    const size_t n_hp = (size_t)s->sum.n_hist * s->cfg.n_par;
-    const size_t nb = n_hp * (s->sum.max_batches + 1), nh = n_hp * s->sum.nbins;
-    if (up && v->n) {
-        if (summary_closed(*v->n, s->sum.bs) > s->sum.max_batches)
-            return fail(APEMOST_HIP_ERR_INVALID, "summary_set: %llu samples close more than max_batches batches",
-                        (unsigned long long)*v->n);
-        if (v->n_batches && *v->n_batches != summary_closed(*v->n, s->sum.bs))
-            return fail(APEMOST_HIP_ERR_INVALID, "summary_set: n_batches %llu does not follow from n = %llu",
-                        (unsigned long long)*v->n_batches, (unsigned long long)*v->n);
-    }
-    // stream order: behind every accumulate queued so far, on the stream they run on
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-#define SUMMARY_COPY(dev, host, bytes)                                                                          \
-    do {                                                                                                       \
-        if ((host) && (bytes) > 0)                                                                             \
-            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
-                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
-    } while (0)
-    SUMMARY_COPY(s->sum.d_prob_sum, v->prob_sum, s->cfg.n_chains * sizeof(double));
-    SUMMARY_COPY(s->sum.d_hist, v->hist, nh * sizeof(u64));
-    SUMMARY_COPY(s->sum.d_batch, v->batch_sums, nb * sizeof(double));
-#undef SUMMARY_COPY
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    if (up) {
-        if (v->n)
-            s->sum.n = *v->n;
-    } else {
-        if (v->n)
-            *v->n = s->sum.n;
-        if (v->n_batches)
-            *v->n_batches = summary_closed(s->sum.n, s->sum.bs);
-    }
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_summary_get(apemost_hip_sampler *s, const apemost_hip_summary_view *v) {
-    CHECK_S(s);
-    return summary_xfer(s, v, false);
-}
-
-extern "C" int apemost_hip_summary_set(apemost_hip_sampler *s, const apemost_hip_summary_view *v) {
-    CHECK_S(s);
-    return summary_xfer(s, v, true);
-}
-
-extern "C" int apemost_hip_summary_end(apemost_hip_sampler *s) {
-    CHECK_S(s);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    summary_free(s);
-    return APEMOST_HIP_OK;
-}
-
-// ---- on-device peaks (pt_peaks.h) ----
-extern "C" int apemost_hip_peaks_begin(apemost_hip_sampler *s, const apemost_hip_peaks_config *cfg) {
-    CHECK_S(s);
-    if (!cfg)
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: config is NULL");
-    const int np = s->cfg.n_par;
-    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
-                    s->cfg.n_chains);
-    if ((long long)cfg->n_keep * np > 65535)
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: %d chains of %d parameters are more than 65535 columns",
-                    cfg->n_keep, np);
-    for (int k = 0; k < cfg->n_keep; k++)
-        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
-            return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing",
-                        k, cfg->chains[k], s->cfg.n_chains);
-    if (cfg->capacity < 1 || cfg->capacity > ((u64)1 << 30))
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: capacity %llu outside [1, 2^30]",
-                    (unsigned long long)cfg->capacity);
-    if (!cfg->lo || !cfg->hi)
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: lo and hi are needed");
-    for (int p = 0; p < np; p++)
-        if (!std::isfinite(cfg->lo[p]) || !std::isfinite(cfg->hi[p]) || !(cfg->lo[p] < cfg->hi[p]) ||
-            !std::isfinite(cfg->hi[p] - cfg->lo[p]))
-            return fail(APEMOST_HIP_ERR_INVALID, "peaks_begin: parameter %d: range [%g, %g] invalid", p, cfg->lo[p],
-                        cfg->hi[p]);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // columns begun before may still be filling
-    peaks_free(s);
-    s->pk.n_keep = cfg->n_keep;
-    s->pk.capacity = cfg->capacity;
-    s->pk.n = 0;
-    HIP_TRY(hipMalloc((void **)&s->pk.d_chains, cfg->n_keep * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->pk.d_lo, np * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pk.d_hi, np * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pk.d_cols, (size_t)cfg->n_keep * np * cfg->capacity * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(s->pk.d_chains, cfg->chains, cfg->n_keep * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->pk.d_lo, cfg->lo, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->pk.d_hi, cfg->hi, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->pk.open = true;
-    return APEMOST_HIP_OK;
-}
-
-// Queued on copy_stream behind everything launched so far on the sampler's stream, like
-// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
-extern "C" int apemost_hip_peaks_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
-                                            uint64_t skip, uint64_t thin) {
-    CHECK_S(s);
-    if (!s->pk.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_accumulate: no peaks_begin");
-    if (thin < 1 || (!d_samples && n_steps > 0))
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_accumulate: bad arguments");
-    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
-    if (kept > s->pk.capacity - s->pk.n)
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_accumulate: %llu samples stored, %llu more are beyond capacity = %llu",
-                    (unsigned long long)s->pk.n, (unsigned long long)kept, (unsigned long long)s->pk.capacity);
-    if (kept == 0)
-        return APEMOST_HIP_OK;
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    PeaksAppendArgs a;
-    a.rows = d_samples;
-    a.n_chains = s->cfg.n_chains;
-    a.n_par = s->cfg.n_par;
-    a.n_keep = s->pk.n_keep;
-    a.chains = s->pk.d_chains;
-    a.skip = skip;
-    a.thin = thin;
-    a.n_kept = kept;
-    a.cols = s->pk.d_cols;
-    a.capacity = s->pk.capacity;
-    a.n = s->pk.n;
-    const dim3 grid((unsigned)((kept + kPeaksThreads - 1) / kPeaksThreads), (unsigned)(s->pk.n_keep * s->cfg.n_par));
-    hipLaunchKernelGGL(peaks_append_kernel, grid, dim3(kPeaksThreads), 0, s->copy_stream, a);
-    HIP_TRY(hipGetLastError());
-    s->pk.n += kept;
-    return APEMOST_HIP_OK;
-}
-
-namespace {
-struct PeaksScratch { // freed on every way out of peaks_get (hipFree waits for the kernels that use it)
-    void *p = nullptr;
-    ~PeaksScratch() {
-        if (p)
-            hipFree(p);
-    }
-};
-} // namespace
-
-extern "C" int apemost_hip_peaks_get(apemost_hip_sampler *s, const apemost_hip_peaks_view *v) {
-    CHECK_S(s);
-    if (!s->pk.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks_get: no peaks_begin");
-    if (!v)
-        return fail(APEMOST_HIP_ERR_INVALID, "peaks view is NULL");
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    const int np = s->cfg.n_par, n_cols = s->pk.n_keep * np;
-    const u64 n = s->pk.n;
-    u64 padded = kPeaksTile;
-    while (padded < n)
-        padded <<= 1;
-    const u64 n_segments = n > 0 ? (n + kPeaksSegment - 1) / kPeaksSegment : 1;
-    // the scratch: keys, segment counts and offsets, and the results, each 256-byte aligned
-    size_t at = 0;
-    auto region = [&at](size_t bytes) {
-        const size_t here = at;
-        at = (at + bytes + 255) & ~(size_t)255;
-        return here;
-    };
-    const size_t at_keys = region((size_t)n_cols * padded * sizeof(u64));
-    const size_t at_count = region((size_t)n_cols * n_segments * sizeof(unsigned int));
-    const size_t at_off = region((size_t)n_cols * n_segments * sizeof(u64));
-    const size_t at_values = region((size_t)n_cols * sizeof(u64));
-    const size_t at_peaks = region((size_t)n_cols * sizeof(unsigned int));
-    const size_t at_cuts = region((size_t)n_cols * kPeaksMax * sizeof(u64));
-    const size_t at_left = region((size_t)n_cols * kPeaksMax * sizeof(u64));
-    const size_t at_right = region((size_t)n_cols * kPeaksMax * sizeof(u64));
-    const size_t at_q = region((size_t)n_cols * kPeaksMax * 3 * sizeof(double));
-    const size_t at_set = region((size_t)n_cols * kPeaksMax);
-    PeaksScratch scratch;
-    HIP_TRY(hipMalloc(&scratch.p, at));
-    char *base = (char *)scratch.p;
-    PeaksArgs a;
-    a.cols = s->pk.d_cols;
-    a.capacity = s->pk.capacity;
-    a.n = n;
-    a.padded = padded;
-    a.n_par = np;
-    a.lo = s->pk.d_lo;
-    a.hi = s->pk.d_hi;
-    a.keys = (unsigned long long *)(base + at_keys);
-    a.n_segments = n_segments;
-    a.seg_count = (unsigned int *)(base + at_count);
-    a.seg_off = (unsigned long long *)(base + at_off);
-    a.n_values = (unsigned long long *)(base + at_values);
-    a.n_peaks = (unsigned int *)(base + at_peaks);
-    a.cuts = (unsigned long long *)(base + at_cuts);
-    a.left = (unsigned long long *)(base + at_left);
-    a.right = (unsigned long long *)(base + at_right);
-    a.q = (double *)(base + at_q);
-    a.q_set = (unsigned char *)(base + at_set);
-    // stream order: behind every accumulate queued so far, on the stream they run on
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    hipStream_t st = s->copy_stream;
-    // (peaks beyond those a column has leave their slots 0)
-    HIP_TRY(hipMemsetAsync(base + at_cuts, 0, at - at_cuts, st));
-    const dim3 threads(kPeaksThreads);
-    hipLaunchKernelGGL(peaks_keys_kernel, dim3((unsigned)(padded / kPeaksThreads), n_cols), threads, 0, st, a);
-    const dim3 tiles((unsigned)(padded / kPeaksTile), n_cols), pairs((unsigned)(padded / 2 / kPeaksThreads), n_cols);
-    hipLaunchKernelGGL(peaks_sort_tile_kernel, tiles, threads, 0, st, a.keys, (unsigned long long)padded, 2ull,
-                       (unsigned long long)kPeaksTile);
-    for (u64 k = 2 * (u64)kPeaksTile; k <= padded; k <<= 1) {
-        for (u64 j = k / 2; j >= (u64)kPeaksTile; j >>= 1)
-            hipLaunchKernelGGL(peaks_sort_global_kernel, pairs, threads, 0, st, a.keys, (unsigned long long)padded,
-                               (unsigned long long)k, (unsigned long long)j);
-        hipLaunchKernelGGL(peaks_sort_tile_kernel, tiles, threads, 0, st, a.keys, (unsigned long long)padded,
-                           (unsigned long long)k, (unsigned long long)k);
-    }
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(peaks_nvalues_kernel, dim3((n_cols + kPeaksThreads - 1) / kPeaksThreads), threads, 0, st, a, n_cols);
-    hipLaunchKernelGGL(peaks_cut_count_kernel, dim3((unsigned)n_segments, n_cols), threads, 0, st, a);
-    hipLaunchKernelGGL(peaks_cut_scan_kernel, dim3(n_cols), threads, 0, st, a);
-    hipLaunchKernelGGL(peaks_cut_write_kernel, dim3((unsigned)((n_segments + kPeaksThreads - 1) / kPeaksThreads), n_cols),
-                       threads, 0, st, a);
-    hipLaunchKernelGGL(peaks_select_kernel, dim3(n_cols), dim3(128), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    std::vector<u64> h_values(n_cols), h_left((size_t)n_cols * kPeaksMax), h_right((size_t)n_cols * kPeaksMax);
-    std::vector<unsigned int> h_peaks(n_cols);
-    std::vector<double> h_q((size_t)n_cols * kPeaksMax * 3);
-    std::vector<unsigned char> h_set((size_t)n_cols * kPeaksMax);
-    HIP_TRY(hipMemcpyAsync(h_values.data(), a.n_values, h_values.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_peaks.data(), a.n_peaks, h_peaks.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_left.data(), a.left, h_left.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_right.data(), a.right, h_right.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_q.data(), a.q, h_q.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_set.data(), a.q_set, h_set.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (v->n)
-        *v->n = n;
-    if (v->n_values)
-        memcpy(v->n_values, h_values.data(), h_values.size() * sizeof(u64));
-    if (v->n_peaks)
-        memcpy(v->n_peaks, h_peaks.data(), h_peaks.size() * sizeof(unsigned int));
-    if (v->left)
-        memcpy(v->left, h_left.data(), h_left.size() * sizeof(u64));
-    if (v->right)
-        memcpy(v->right, h_right.data(), h_right.size() * sizeof(u64));
-    if (v->q)
-        memcpy(v->q, h_q.data(), h_q.size() * sizeof(double));
-    if (v->q_set)
-        memcpy(v->q_set, h_set.data(), h_set.size());
-    for (int col = 0; col < n_cols; col++)
-        if (h_peaks[col] > (unsigned int)kPeaksMax)
-            return fail(APEMOST_HIP_ERR_INVALID, "peaks_get: kept chain %d, parameter %d: %u peaks, more than %d "
-                        "(the reference asserts npeaks < 100)", col / np, col % np, h_peaks[col], kPeaksMax);
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_peaks_end(apemost_hip_sampler *s) {
-    CHECK_S(s);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    peaks_free(s);
-    return APEMOST_HIP_OK;
-}
-
-// ---- on-device joint marginals (pt_joint.h) ----
-extern "C" int apemost_hip_joint_begin(apemost_hip_sampler *s, const apemost_hip_joint_config *cfg) {
-    CHECK_S(s);
-    if (!cfg)
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: config is NULL");
-    const int np = s->cfg.n_par;
-    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
-                    s->cfg.n_chains);
-    if ((long long)cfg->n_keep * np > 65535)
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: %d chains of %d parameters are more than 65535 columns",
-                    cfg->n_keep, np);
-    for (int k = 0; k < cfg->n_keep; k++)
-        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
-            return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing",
-                        k, cfg->chains[k], s->cfg.n_chains);
-    if (cfg->nbins < 1 || cfg->nbins > kJointMaxBins)
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: nbins %d outside [1,%d]", cfg->nbins, kJointMaxBins);
-    std::vector<int> pairs;
-    if (!cfg->pairs) { // all i < j in lexicographic order
-        for (int i = 0; i < np; i++)
-            for (int j = i + 1; j < np; j++) {
-                pairs.push_back(i);
-                pairs.push_back(j);
-            }
-    } else {
-        const long long all = (long long)np * (np - 1) / 2;
-        if (cfg->n_pairs < 0 || cfg->n_pairs > all)
-            return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: n_pairs %d outside [0,%lld]", cfg->n_pairs, all);
-        std::vector<char> seen((size_t)np * np, 0);
-        for (int q = 0; q < cfg->n_pairs; q++) {
-            const int i = cfg->pairs[2 * q], j = cfg->pairs[2 * q + 1];
-            if (i < 0 || j >= np || i >= j || seen[(size_t)i * np + j])
-                return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: pairs[%d] = (%d, %d): 0 <= i < j < %d, no duplicates", q, i,
-                            j, np);
-            seen[(size_t)i * np + j] = 1;
-            pairs.push_back(i);
-            pairs.push_back(j);
-        }
-    }
-    const int n_pairs = (int)(pairs.size() / 2);
-    if (!cfg->lo || !cfg->hi)
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: lo and hi are needed");
-    for (int p = 0; p < np; p++)
-        if (!std::isfinite(cfg->lo[p]) || !std::isfinite(cfg->hi[p]) || !(cfg->lo[p] < cfg->hi[p]) ||
-            !std::isfinite(cfg->hi[p] - cfg->lo[p]))
-            return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: parameter %d: range [%g, %g] invalid", p, cfg->lo[p],
-                        cfg->hi[p]);
-    const u64 n_counts = (u64)cfg->n_keep * n_pairs * cfg->nbins * cfg->nbins; // (< 2^16 2^16 2^18: no overflow)
-    if (n_pairs > 65535 || n_counts * sizeof(u64) > ((u64)1 << 30))
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_begin: %d chains x %d pairs x %d^2 bins: counts above 2^30 bytes",
-                    cfg->n_keep, n_pairs, cfg->nbins);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a joint begun before may still be accumulating
-    joint_free(s);
-    const size_t n_cols = (size_t)cfg->n_keep * np, tri = (size_t)np * (np + 1) / 2;
-    // the staged columns: about 4 Mi values over all of them, at least 256 and at most 2^18 kept steps per launch
-    // (the LDS counters are 32 bits wide)
-    u64 chunk = ((u64)1 << 22) / n_cols;
-    chunk = chunk < 256 ? 256 : chunk > ((u64)1 << 18) ? (u64)1 << 18 : chunk;
-    s->jt.n_keep = cfg->n_keep;
-    s->jt.nbins = cfg->nbins;
-    s->jt.n_pairs = n_pairs;
-    s->jt.chunk = chunk;
-    s->jt.n = 0;
-    HIP_TRY(hipMalloc((void **)&s->jt.d_chains, cfg->n_keep * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_pairs, (n_pairs > 0 ? n_pairs : 1) * 2 * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_lo, np * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_hi, np * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_vals, n_cols * chunk * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_bins, n_cols * chunk * sizeof(unsigned short)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_origin, n_cols * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_sum, n_cols * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_cross, cfg->n_keep * tri * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->jt.d_counts, (n_counts > 0 ? n_counts : 1) * sizeof(u64)));
-    HIP_TRY(hipMemsetAsync(s->jt.d_origin, 0, n_cols * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->jt.d_sum, 0, n_cols * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->jt.d_cross, 0, cfg->n_keep * tri * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->jt.d_counts, 0, (n_counts > 0 ? n_counts : 1) * sizeof(u64), s->stream));
-    HIP_TRY(hipMemcpyAsync(s->jt.d_chains, cfg->chains, cfg->n_keep * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    if (n_pairs > 0)
-        HIP_TRY(hipMemcpyAsync(s->jt.d_pairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->jt.d_lo, cfg->lo, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->jt.d_hi, cfg->hi, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream)); // (`pairs` and the caller's arrays are read until here)
-    s->jt.open = true;
-    return APEMOST_HIP_OK;
-}
-
-// Queued on copy_stream behind everything launched so far on the sampler's stream, like
-// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
-extern "C" int apemost_hip_joint_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
-                                            uint64_t skip, uint64_t thin) {
-    CHECK_S(s);
-    if (!s->jt.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_accumulate: no joint_begin");
-    if (thin < 1 || (!d_samples && n_steps > 0))
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_accumulate: bad arguments");
-    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
-    if (kept == 0)
-        return APEMOST_HIP_OK;
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const int np = s->cfg.n_par, n_cols = s->jt.n_keep * np;
-    const int band_rows = joint_band_rows(s->jt.nbins), n_bands = (s->jt.nbins + band_rows - 1) / band_rows;
-    const int entries = s->jt.n_keep * (np + np * (np + 1) / 2);
-    for (u64 k0 = 0; k0 < kept; k0 += s->jt.chunk) {
-        JointArgs a;
-        a.rows = d_samples;
-        a.n_chains = s->cfg.n_chains;
-        a.n_par = np;
-        a.n_keep = s->jt.n_keep;
-        a.chains = s->jt.d_chains;
-        a.skip = skip + k0 * thin;
-        a.thin = thin;
-        a.n = (unsigned int)(kept - k0 < s->jt.chunk ? kept - k0 : s->jt.chunk);
-        a.chunk = s->jt.chunk;
-        a.nbins = s->jt.nbins;
-        a.n_pairs = s->jt.n_pairs;
-        a.pairs = s->jt.d_pairs;
-        a.lo = s->jt.d_lo;
-        a.hi = s->jt.d_hi;
-        a.vals = s->jt.d_vals;
-        a.bins = s->jt.d_bins;
-        a.first = s->jt.n == 0;
-        a.counts = s->jt.d_counts;
-        a.origin = s->jt.d_origin;
-        a.sum = s->jt.d_sum;
-        a.cross = s->jt.d_cross;
-        hipLaunchKernelGGL(joint_gather_kernel, dim3((a.n + kJointGatherPer - 1) / kJointGatherPer, (unsigned)n_cols),
-                           dim3(kJointThreads), 0, s->copy_stream, a);
-        HIP_TRY(hipGetLastError());
-        if (s->jt.n_pairs > 0) {
-            hipLaunchKernelGGL(joint_pair_kernel, dim3((unsigned)n_bands, (unsigned)s->jt.n_pairs, (unsigned)s->jt.n_keep),
-                               dim3(kJointThreads), 0, s->copy_stream, a);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(joint_moments_kernel, dim3((unsigned)((entries + kJointMomentThreads - 1) / kJointMomentThreads)),
-                           dim3(kJointMomentThreads), 0, s->copy_stream, a);
-        HIP_TRY(hipGetLastError());
-        s->jt.n += a.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-static int joint_xfer(apemost_hip_sampler *s, const apemost_hip_joint_view *v, bool up) {
-    if (!s->jt.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "joint_%s: no joint_begin", up ? "set" : "get");
-    if (!v)
-        return fail(APEMOST_HIP_ERR_INVALID, "joint view is NULL");
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    const size_t np = s->cfg.n_par, n_cols = (size_t)s->jt.n_keep * np, tri = np * (np + 1) / 2;
-    const size_t n_counts = (size_t)s->jt.n_keep * s->jt.n_pairs * s->jt.nbins * s->jt.nbins;
-    // stream order: behind every accumulate queued so far, on the stream they run on
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-#define JOINT_COPY(dev, host, bytes)                                                                            \
-    do {                                                                                                       \
-        if ((host) && (bytes) > 0)                                                                             \
-            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
-                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
-    } while (0)
-    JOINT_COPY(s->jt.d_counts, v->counts, n_counts * sizeof(u64));
-    JOINT_COPY(s->jt.d_origin, v->origin, n_cols * sizeof(double));
-    JOINT_COPY(s->jt.d_sum, v->sum, n_cols * sizeof(double));
-    JOINT_COPY(s->jt.d_cross, v->cross, s->jt.n_keep * tri * sizeof(double));
-#undef JOINT_COPY
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    if (v->n) {
-        if (up)
-            s->jt.n = *v->n;
-        else
-            *v->n = s->jt.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_joint_get(apemost_hip_sampler *s, const apemost_hip_joint_view *v) {
-    CHECK_S(s);
-    return joint_xfer(s, v, false);
-}
-
-extern "C" int apemost_hip_joint_set(apemost_hip_sampler *s, const apemost_hip_joint_view *v) {
-    CHECK_S(s);
-    return joint_xfer(s, v, true);
-}
-
-extern "C" int apemost_hip_joint_end(apemost_hip_sampler *s) {
-    CHECK_S(s);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    joint_free(s);
-    return APEMOST_HIP_OK;
-}
-
-// ---- on-device evidence fold (pt_evidence.h) ----
-extern "C" int apemost_hip_evidence_begin(apemost_hip_sampler *s, const apemost_hip_evidence_config *cfg) {
-    CHECK_S(s);
-    if (!cfg)
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: config is NULL");
-    if (cfg->batch_size < 1)
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: batch_size must be >= 1");
-    if (!cfg->coef_up || !cfg->coef_down)
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: coef_up and coef_down are needed");
-    const size_t nc = (size_t)s->cfg.n_chains;
-    for (size_t c = 0; c < nc; c++)
-        if (!std::isfinite(cfg->coef_up[c]) || !std::isfinite(cfg->coef_down[c]))
-            return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: chain %zu: coefficients (%g, %g) are not finite", c,
-                        cfg->coef_up[c], cfg->coef_down[c]);
-    if (cfg->max_batches > ((size_t)1 << 40) || cfg->max_batches + 1 > ((size_t)1 << 40) / nc)
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence_begin: max_batches %llu too large",
-                    (unsigned long long)cfg->max_batches);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a fold begun before may still be accumulating
-    evidence_free(s);
-    // the staged column: about 1 Mi values over all chains, at least 256 and at most 2^18 kept steps per launch
-    u64 chunk = ((u64)1 << 20) / nc;
-    chunk = chunk < 256 ? 256 : chunk > ((u64)1 << 18) ? (u64)1 << 18 : chunk;
-    s->ev.bs = cfg->batch_size;
-    s->ev.max_batches = cfg->max_batches;
-    s->ev.chunk = chunk;
-    s->ev.n = 0;
-    const size_t nb = nc * (cfg->max_batches + 1);
-    HIP_TRY(hipMalloc((void **)&s->ev.d_coef, 2 * nc * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ev.d_vals, nc * chunk * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ev.d_origin, nc * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ev.d_sum, nc * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ev.d_sq, nc * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ev.d_batch, nb * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ev.d_m, 2 * nc * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ev.d_S, 2 * nc * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(s->ev.d_origin, 0, nc * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ev.d_sum, 0, nc * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ev.d_sq, 0, nc * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ev.d_batch, 0, nb * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ev.d_m, 0, 2 * nc * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ev.d_S, 0, 2 * nc * sizeof(double), s->stream));
-    HIP_TRY(hipMemcpyAsync(s->ev.d_coef, cfg->coef_up, nc * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->ev.d_coef + nc, cfg->coef_down, nc * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's arrays are read until here)
-    s->ev.open = true;
-    return APEMOST_HIP_OK;
-}
-
-// Queued on copy_stream behind everything launched so far on the sampler's stream, like
-// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
-extern "C" int apemost_hip_evidence_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
-                                               uint64_t skip, uint64_t thin) {
-    CHECK_S(s);
-    if (!s->ev.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence_accumulate: no evidence_begin");
-    if (thin < 1 || (!d_samples && n_steps > 0))
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence_accumulate: bad arguments");
-    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
-    if (summary_closed(s->ev.n + kept, s->ev.bs) > s->ev.max_batches)
-        return fail(APEMOST_HIP_ERR_INVALID,
-                    "evidence_accumulate: %llu samples would close batch %llu, beyond max_batches = %llu",
-                    (unsigned long long)(s->ev.n + kept), (unsigned long long)summary_closed(s->ev.n + kept, s->ev.bs),
-                    (unsigned long long)s->ev.max_batches);
-    if (kept == 0)
-        return APEMOST_HIP_OK;
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const int nc = s->cfg.n_chains;
-    for (u64 k0 = 0; k0 < kept; k0 += s->ev.chunk) {
-        EvidenceArgs a;
-        a.rows = d_samples;
-        a.n_chains = nc;
-        a.n_par = s->cfg.n_par;
-        a.skip = skip + k0 * thin;
-        a.thin = thin;
-        a.n = (unsigned int)(kept - k0 < s->ev.chunk ? kept - k0 : s->ev.chunk);
-        a.first = s->ev.n == 0;
-        a.bs = s->ev.bs;
-        a.left = summary_left(s->ev.n, s->ev.bs);
-        a.n_closed = summary_closed(s->ev.n, s->ev.bs);
-        a.batch_stride = s->ev.max_batches + 1;
-        a.coef = s->ev.d_coef;
-        a.vals = s->ev.d_vals;
-        a.origin = s->ev.d_origin;
-        a.sum = s->ev.d_sum;
-        a.sq = s->ev.d_sq;
-        a.batch = s->ev.d_batch;
-        a.m = s->ev.d_m;
-        a.S = s->ev.d_S;
-        hipLaunchKernelGGL(evidence_gather_kernel,
-                           dim3((unsigned)((nc + kEvidenceGatherThreads - 1) / kEvidenceGatherThreads), (a.n + 7u) / 8u),
-                           dim3(kEvidenceGatherThreads), 0, s->copy_stream, a);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(evidence_fold_kernel,
-                           dim3((unsigned)((nc + kEvidenceThreads - 1) / kEvidenceThreads), (unsigned)kEvidenceQuantities),
-                           dim3(kEvidenceThreads), 0, s->copy_stream, a);
-        HIP_TRY(hipGetLastError());
-        s->ev.n += a.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-static int evidence_xfer(apemost_hip_sampler *s, const apemost_hip_evidence_view *v, bool up) {
-    if (!s->ev.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence_%s: no evidence_begin", up ? "set" : "get");
-    if (!v)
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence view is NULL");
-    if (up && v->n && summary_closed(*v->n, s->ev.bs) > s->ev.max_batches)
-        return fail(APEMOST_HIP_ERR_INVALID, "evidence_set: %llu samples close more than max_batches batches",
-                    (unsigned long long)*v->n);
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    const size_t nc = (size_t)s->cfg.n_chains;
-    // stream order: behind every accumulate queued so far, on the stream they run on
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-#define EVIDENCE_COPY(dev, host, bytes)                                                                        \
-    do {                                                                                                       \
-        if ((host) && (bytes) > 0)                                                                             \
-            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
-                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
-    } while (0)
-    EVIDENCE_COPY(s->ev.d_origin, v->origin, nc * sizeof(double));
-    EVIDENCE_COPY(s->ev.d_sum, v->sum, nc * sizeof(double));
-    EVIDENCE_COPY(s->ev.d_sq, v->sq, nc * sizeof(double));
-    EVIDENCE_COPY(s->ev.d_batch, v->batch, nc * (s->ev.max_batches + 1) * sizeof(double));
-    EVIDENCE_COPY(s->ev.d_m, v->m, 2 * nc * sizeof(double));
-    EVIDENCE_COPY(s->ev.d_S, v->S, 2 * nc * sizeof(double));
-#undef EVIDENCE_COPY
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    if (v->n) {
-        if (up)
-            s->ev.n = *v->n;
-        else
-            *v->n = s->ev.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_evidence_get(apemost_hip_sampler *s, const apemost_hip_evidence_view *v) {
-    CHECK_S(s);
-    return evidence_xfer(s, v, false);
-}
-
-extern "C" int apemost_hip_evidence_set(apemost_hip_sampler *s, const apemost_hip_evidence_view *v) {
-    CHECK_S(s);
-    return evidence_xfer(s, v, true);
-}
-
-extern "C" int apemost_hip_evidence_end(apemost_hip_sampler *s) {
-    CHECK_S(s);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    evidence_free(s);
-    return APEMOST_HIP_OK;
-}
-
-// ---- on-device autocorrelation (pt_autocorr.h) ----
-extern "C" int apemost_hip_autocorr_begin(apemost_hip_sampler *s, const apemost_hip_autocorr_config *cfg) {
-    CHECK_S(s);
-    if (!cfg)
-        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_begin: config is NULL");
-    const int np = s->cfg.n_par;
-    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
-        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
-                    s->cfg.n_chains);
-    for (int k = 0; k < cfg->n_keep; k++)
-        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
-            return fail(APEMOST_HIP_ERR_INVALID,
-                        "autocorr_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing", k,
-                        cfg->chains[k], s->cfg.n_chains);
-    if (cfg->max_lag < 1 || cfg->max_lag > kAutocorrMaxLag)
-        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_begin: max_lag %d outside [1,%d]", cfg->max_lag, kAutocorrMaxLag);
-    std::vector<int> cols;
-    if (!cfg->cols) { // the parameters and prob - prior
-        for (int p = 0; p < np; p++)
-            cols.push_back(p);
-        cols.push_back(np + 1);
-    } else {
-        if (cfg->n_cols < 1 || cfg->n_cols > np + 2)
-            return fail(APEMOST_HIP_ERR_INVALID, "autocorr_begin: n_cols %d outside [1,%d]", cfg->n_cols, np + 2);
-        for (int c = 0; c < cfg->n_cols; c++) {
-            if (cfg->cols[c] < 0 || cfg->cols[c] > np + 1 || (c > 0 && cfg->cols[c] <= cfg->cols[c - 1]))
-                return fail(APEMOST_HIP_ERR_INVALID,
-                            "autocorr_begin: cols[%d] = %d: column indices in [0,%d], strictly increasing", c, cfg->cols[c],
-                            np + 1);
-            cols.push_back(cfg->cols[c]);
-        }
-    }
-    const u64 n_series = (u64)cfg->n_keep * cols.size();
-    const u64 L = (u64)cfg->max_lag, H = L - 1;
-    if (n_series > 65535 || n_series * L > ((u64)1 << 24))
-        return fail(APEMOST_HIP_ERR_INVALID,
-                    "autocorr_begin: %d chains x %zu columns x %d lags: more than 65535 series or 2^24 lag sums",
-                    cfg->n_keep, cols.size(), cfg->max_lag);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a fold begun before may still be accumulating
-    autocorr_free(s);
-    // the staged series: about 1 Mi values over all of them, at least 256 and at most 2^16 kept steps per launch
-    u64 chunk = ((u64)1 << 20) / n_series;
-    chunk = chunk < 256 ? 256 : chunk > ((u64)1 << 16) ? (u64)1 << 16 : chunk;
-    s->ac.n_keep = cfg->n_keep;
-    s->ac.n_cols = (int)cols.size();
-    s->ac.max_lag = cfg->max_lag;
-    s->ac.chunk = chunk;
-    s->ac.n = 0;
-    const size_t nh = (size_t)(n_series * (H > 0 ? H : 1));
-    HIP_TRY(hipMalloc((void **)&s->ac.d_chains, cfg->n_keep * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->ac.d_cols, cols.size() * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->ac.d_buf, n_series * (H + chunk) * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ac.d_origin, n_series * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ac.d_sum, n_series * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ac.d_lag, n_series * L * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ac.d_head, nh * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->ac.d_tail, nh * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(s->ac.d_origin, 0, n_series * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ac.d_sum, 0, n_series * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ac.d_lag, 0, n_series * L * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ac.d_head, 0, nh * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->ac.d_tail, 0, nh * sizeof(double), s->stream));
-    HIP_TRY(hipMemcpyAsync(s->ac.d_chains, cfg->chains, cfg->n_keep * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->ac.d_cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream)); // (`cols` and the caller's arrays are read until here)
-    s->ac.open = true;
-    return APEMOST_HIP_OK;
-}
-
-// Queued on copy_stream behind everything launched so far on the sampler's stream, like
-// apemost_hip_summary_accumulate; apemost_hip_samples_wait covers it.
-extern "C" int apemost_hip_autocorr_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
-                                               uint64_t skip, uint64_t thin) {
-    CHECK_S(s);
-    if (!s->ac.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_accumulate: no autocorr_begin");
-    if (thin < 1 || (!d_samples && n_steps > 0))
-        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_accumulate: bad arguments");
-    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
-    if (kept == 0)
-        return APEMOST_HIP_OK;
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const unsigned n_series = (unsigned)(s->ac.n_keep * s->ac.n_cols);
-    const unsigned H = (unsigned)s->ac.max_lag - 1u;
-    for (u64 k0 = 0; k0 < kept; k0 += s->ac.chunk) {
-        AutocorrArgs a;
-        a.rows = d_samples;
-        a.n_chains = s->cfg.n_chains;
-        a.n_par = s->cfg.n_par;
-        a.n_keep = s->ac.n_keep;
-        a.n_cols = s->ac.n_cols;
-        a.chains = s->ac.d_chains;
-        a.cols = s->ac.d_cols;
-        a.skip = skip + k0 * thin;
-        a.thin = thin;
-        a.n = (unsigned int)(kept - k0 < s->ac.chunk ? kept - k0 : s->ac.chunk);
-        a.n0 = s->ac.n;
-        a.max_lag = s->ac.max_lag;
-        a.n_groups = (s->ac.max_lag + kAutocorrGroup - 1) / kAutocorrGroup;
-        a.stride = H + s->ac.chunk;
-        a.buf = s->ac.d_buf;
-        a.origin = s->ac.d_origin;
-        a.sum = s->ac.d_sum;
-        a.lag = s->ac.d_lag;
-        a.head = s->ac.d_head;
-        a.tail = s->ac.d_tail;
-        hipLaunchKernelGGL(autocorr_gather_kernel, dim3((H + a.n + kAutocorrThreads - 1) / kAutocorrThreads, n_series),
-                           dim3(kAutocorrThreads), 0, s->copy_stream, a);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(autocorr_fold_kernel, dim3((unsigned)a.n_groups + 1u, n_series), dim3(kAutocorrWave), 0,
-                           s->copy_stream, a);
-        HIP_TRY(hipGetLastError());
-        if (H > 0) {
-            hipLaunchKernelGGL(autocorr_carry_kernel, dim3((H + kAutocorrThreads - 1) / kAutocorrThreads, n_series),
-                               dim3(kAutocorrThreads), 0, s->copy_stream, a);
-            HIP_TRY(hipGetLastError());
-        }
-        s->ac.n += a.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-static int autocorr_xfer(apemost_hip_sampler *s, const apemost_hip_autocorr_view *v, bool up) {
-    if (!s->ac.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "autocorr_%s: no autocorr_begin", up ? "set" : "get");
-    if (!v)
-        return fail(APEMOST_HIP_ERR_INVALID, "autocorr view is NULL");
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    const size_t n_series = (size_t)s->ac.n_keep * s->ac.n_cols, L = (size_t)s->ac.max_lag, H = L - 1;
-    // stream order: behind every accumulate queued so far, on the stream they run on
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-#define AUTOCORR_COPY(dev, host, bytes)                                                                        \
-    do {                                                                                                       \
-        if ((host) && (bytes) > 0)                                                                             \
-            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
-                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
-    } while (0)
-    AUTOCORR_COPY(s->ac.d_origin, v->origin, n_series * sizeof(double));
-    AUTOCORR_COPY(s->ac.d_sum, v->sum, n_series * sizeof(double));
-    AUTOCORR_COPY(s->ac.d_lag, v->lag, n_series * L * sizeof(double));
-    AUTOCORR_COPY(s->ac.d_head, v->head, n_series * H * sizeof(double));
-    AUTOCORR_COPY(s->ac.d_tail, v->tail, n_series * H * sizeof(double));
-#undef AUTOCORR_COPY
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    if (v->n) {
-        if (up)
-            s->ac.n = *v->n;
-        else
-            *v->n = s->ac.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_autocorr_get(apemost_hip_sampler *s, const apemost_hip_autocorr_view *v) {
-    CHECK_S(s);
-    return autocorr_xfer(s, v, false);
-}
-
-extern "C" int apemost_hip_autocorr_set(apemost_hip_sampler *s, const apemost_hip_autocorr_view *v) {
-    CHECK_S(s);
-    return autocorr_xfer(s, v, true);
-}
-
-extern "C" int apemost_hip_autocorr_end(apemost_hip_sampler *s) {
-    CHECK_S(s);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    autocorr_free(s);
-    return APEMOST_HIP_OK;
-}
-
-// ---- on-device posterior predictive (pt_predict.h) ----
-// a built-in model, or a user-supplied one with the curve hook (its analysis module is built here on first use)
-#define PREDICT_HAS_CURVE(s, what)                                                                                \
-    do {                                                                                                        \
-        if ((s)->cfg.model == APEMOST_MODEL_USER) {                                                             \
-            const int rc_hooks = user_analysis(s);                                                              \
-            if (rc_hooks != APEMOST_HIP_OK)                                                                     \
-                return rc_hooks;                                                                                \
-            if (!(s)->ua.has_curve)                                                                             \
-                return fail(APEMOST_HIP_ERR_UNSUPPORTED,                                                        \
-                            what ": this user-supplied device model has no curve: it does not define the hook " \
-                                 "apemost_user_curve (APEMOST_USER_CURVE, include/apemost_device_model.h)");    \
-        }                                                                                                       \
-    } while (0)
-
-static hipError_t user_launch(hipFunction_t f, unsigned grid, unsigned block, size_t lds, hipStream_t stream, void **params) {
-    return hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, (unsigned)lds, stream, params, nullptr);
-}
-
-// host rows [n][n_cols], row-major like m->data -> a ctx's data, [n_cols][n]
-static std::vector<double> rows_by_columns(const double *rows, int n, int n_cols) {
-    std::vector<double> out((size_t)n * n_cols);
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n_cols; j++)
-            out[(size_t)j * n + i] = rows[(size_t)i * n_cols + j];
-    return out;
-}
-
-static hipError_t predict_launch_fold(apemost_hip_sampler *s, const PredictArgs &a) {
-    const dim3 grid((unsigned)(a.n_blocks + 1) * (unsigned)a.n_keep), block(kPredictWave);
-    const size_t lds = predict_lds_bytes(a.nbins, a.points);
-    if (s->cfg.model == APEMOST_MODEL_USER) {
-        void *params[] = {const_cast<PredictArgs *>(&a)};
-        return user_launch(a.nbins > 0 ? s->ua.predict_fold_hist : s->ua.predict_fold, grid.x, block.x,
-                           a.nbins > 0 ? lds : 0, s->copy_stream, params);
-    }
-#define PREDICT_FOLD(M)                                                                                          \
-    do {                                                                                                         \
-        if (a.nbins > 0)                                                                                         \
-            hipLaunchKernelGGL((predict_fold_kernel<M, true>), grid, block, lds, s->copy_stream, a);            \
-        else                                                                                                     \
-            hipLaunchKernelGGL((predict_fold_kernel<M, false>), grid, block, 0, s->copy_stream, a);             \
-    } while (0)
-    switch (s->cfg.model) {
-    case APEMOST_MODEL_SIMPLESIN: PREDICT_FOLD(APEMOST_MODEL_SIMPLESIN); break;
-    case APEMOST_MODEL_SINE3: PREDICT_FOLD(APEMOST_MODEL_SINE3); break;
-    case APEMOST_MODEL_PULSE: PREDICT_FOLD(APEMOST_MODEL_PULSE); break;
-    default: PREDICT_FOLD(APEMOST_MODEL_PULSE_VROT); break;
-    }
-#undef PREDICT_FOLD
-    return hipGetLastError();
-}
-
-extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_hip_predict_config *cfg) {
-    CHECK_S(s);
-    PREDICT_HAS_CURVE(s, "predict_begin");
-    if (!cfg)
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: config is NULL");
-    const int np = s->cfg.n_par;
-    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
-                    s->cfg.n_chains);
-    for (int k = 0; k < cfg->n_keep; k++)
-        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
-            return fail(APEMOST_HIP_ERR_INVALID,
-                        "predict_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing", k,
-                        cfg->chains[k], s->cfg.n_chains);
-    const int n_x = cfg->x ? cfg->n_x : s->cfg.n_data;
-    if (n_x < 1)
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: n_x %d < 1", n_x);
-    // a user model's abscissae are whole rows: [n_x][n_cols] from the caller, or the sampler's data
-    const bool user = s->cfg.model == APEMOST_MODEL_USER;
-    const int nc = user ? s->cfg.n_cols : 1;
-    if (cfg->x)
-        for (size_t i = 0; i < (size_t)n_x * nc; i++)
-            if (!std::isfinite(cfg->x[i]))
-                return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: x[%zu] is not finite", i);
-    if (cfg->nbins < 0 || cfg->nbins > kPredictMaxBins)
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: nbins %d outside [0,%d]", cfg->nbins, kPredictMaxBins);
-    if (cfg->nbins > 0 && !(std::isfinite(cfg->lo) && std::isfinite(cfg->hi) && cfg->lo < cfg->hi))
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: the histogram range [%g, %g] is not finite with lo < hi",
-                    cfg->lo, cfg->hi);
-    const u64 n_series = (u64)cfg->n_keep * (u64)n_x;
-    if (n_series > ((u64)1 << 20) || n_series * (u64)cfg->nbins > ((u64)1 << 26))
-        return fail(APEMOST_HIP_ERR_INVALID,
-                    "predict_begin: %d chains x %d abscissae x %d bins: more than 2^20 series or 2^26 counts", cfg->n_keep,
-                    n_x, cfg->nbins);
-    if (np > kPredictTile)
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: %d parameters, more than %d", np, kPredictTile);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a fold begun before may still be accumulating
-    predict_free(s);
-    s->pr.n_keep = cfg->n_keep;
-    s->pr.n_x = n_x;
-    s->pr.n_cols = nc;
-    s->pr.nbins = cfg->nbins;
-    s->pr.points = predict_points(cfg->nbins);
-    s->pr.lo = cfg->lo;
-    s->pr.hi = cfg->hi;
-    s->pr.n = 0;
-    const size_t ns = (size_t)n_series, nk = (size_t)cfg->n_keep, nh = ns * (size_t)cfg->nbins;
-    HIP_TRY(hipMalloc((void **)&s->pr.d_chains, nk * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_x, ns * nc * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_origin, ns * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_sum, ns * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_sq, ns * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_vmin, ns * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_vmax, ns * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_hist, (nh ? nh : 1) * sizeof(u64)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_best_prob, nk * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_best_params, nk * np * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pr.d_best_n, nk * sizeof(u64)));
-    HIP_TRY(hipMemsetAsync(s->pr.d_origin, 0, ns * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->pr.d_sum, 0, ns * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->pr.d_sq, 0, ns * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->pr.d_hist, 0, (nh ? nh : 1) * sizeof(u64), s->stream));
-    HIP_TRY(hipMemsetAsync(s->pr.d_best_params, 0, nk * np * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->pr.d_best_n, 0, nk * sizeof(u64), s->stream));
-    std::vector<double> pinf(ns, INFINITY), ninf(ns, -INFINITY);
-    HIP_TRY(hipMemcpyAsync(s->pr.d_vmin, pinf.data(), ns * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->pr.d_vmax, ninf.data(), ns * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->pr.d_best_prob, ninf.data(), nk * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->pr.d_chains, cfg->chains, nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    const std::vector<double> by_cols = cfg->x && user ? rows_by_columns(cfg->x, n_x, nc) : std::vector<double>();
-    const double *host_x = by_cols.empty() ? cfg->x : by_cols.data();
-    for (int k = 0; k < cfg->n_keep; k++) {
-        double *dst = s->pr.d_x + (size_t)k * nc * n_x;
-        if (cfg->x) {
-            HIP_TRY(hipMemcpyAsync(dst, host_x, (size_t)nc * n_x * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        } else { // column 0 of the kept chain's own ladder (the data is stored by columns, ladder after ladder);
-                 // a user model: all of its columns
-            const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
-            const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * s->cfg.n_data;
-            HIP_TRY(hipMemcpyAsync(dst, col0, (size_t)nc * n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's arrays are read until here)
-    s->pr.open = true;
-    return APEMOST_HIP_OK;
-}
-
-// Queued on copy_stream behind everything launched so far on the sampler's stream, like
-// apemost_hip_autocorr_accumulate; apemost_hip_samples_wait covers it.
-extern "C" int apemost_hip_predict_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
-                                              uint64_t skip, uint64_t thin) {
-    CHECK_S(s);
-    PREDICT_HAS_CURVE(s, "predict_accumulate");
-    if (!s->pr.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_accumulate: no predict_begin");
-    if (thin < 1 || (!d_samples && n_steps > 0))
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_accumulate: bad arguments");
-    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
-    if (kept == 0)
-        return APEMOST_HIP_OK;
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    for (u64 k0 = 0; k0 < kept; k0 += kPredictPiece) {
-        PredictArgs a;
-        a.rows = d_samples;
-        a.n_chains = s->cfg.n_chains;
-        a.n_par = s->cfg.n_par;
-        a.n_keep = s->pr.n_keep;
-        a.chains = s->pr.d_chains;
-        a.skip = skip + k0 * thin;
-        a.thin = thin;
-        a.n = (unsigned int)(kept - k0 < (u64)kPredictPiece ? kept - k0 : (u64)kPredictPiece);
-        a.n0 = s->pr.n;
-        a.n_x = s->pr.n_x;
-        a.x = s->pr.d_x;
-        a.n_cols = s->pr.n_cols;
-        a.sigma = s->sh.consts.sigma;
-        a.hmin = s->sh.consts.hmin;
-        a.nbins = s->pr.nbins;
-        a.points = s->pr.points;
-        a.n_blocks = (s->pr.n_x + s->pr.points - 1) / s->pr.points;
-        a.lo = s->pr.lo;
-        a.hi = s->pr.hi;
-        a.origin = s->pr.d_origin;
-        a.sum = s->pr.d_sum;
-        a.sq = s->pr.d_sq;
-        a.vmin = s->pr.d_vmin;
-        a.vmax = s->pr.d_vmax;
-        a.hist = s->pr.d_hist;
-        a.best_prob = s->pr.d_best_prob;
-        a.best_params = s->pr.d_best_params;
-        a.best_n = s->pr.d_best_n;
-        HIP_TRY(predict_launch_fold(s, a));
-        s->pr.n += a.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-static int predict_xfer(apemost_hip_sampler *s, const apemost_hip_predict_view *v, bool up) {
-    if (!s->pr.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_%s: no predict_begin", up ? "set" : "get");
-    if (!v)
-        return fail(APEMOST_HIP_ERR_INVALID, "predict view is NULL");
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    const size_t nk = (size_t)s->pr.n_keep, ns = nk * s->pr.n_x, np = (size_t)s->cfg.n_par;
-    // stream order: behind every accumulate queued so far, on the stream they run on
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-#define PREDICT_COPY(dev, host, bytes)                                                                         \
-    do {                                                                                                       \
-        if ((host) && (bytes) > 0)                                                                             \
-            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(host), (bytes), kind, s->copy_stream)    \
-                       : hipMemcpyAsync((void *)(host), (const void *)(dev), (bytes), kind, s->copy_stream));  \
-    } while (0)
-    PREDICT_COPY(s->pr.d_origin, v->origin, ns * sizeof(double));
-    PREDICT_COPY(s->pr.d_sum, v->sum, ns * sizeof(double));
-    PREDICT_COPY(s->pr.d_sq, v->sq, ns * sizeof(double));
-    PREDICT_COPY(s->pr.d_vmin, v->vmin, ns * sizeof(double));
-    PREDICT_COPY(s->pr.d_vmax, v->vmax, ns * sizeof(double));
-    PREDICT_COPY(s->pr.d_hist, v->hist, ns * s->pr.nbins * sizeof(u64));
-    PREDICT_COPY(s->pr.d_best_prob, v->best_prob, nk * sizeof(double));
-    PREDICT_COPY(s->pr.d_best_params, v->best_params, nk * np * sizeof(double));
-    PREDICT_COPY(s->pr.d_best_n, v->best_n, nk * sizeof(u64));
-#undef PREDICT_COPY
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    if (v->n) {
-        if (up)
-            s->pr.n = *v->n;
-        else
-            *v->n = s->pr.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_predict_get(apemost_hip_sampler *s, const apemost_hip_predict_view *v) {
-    CHECK_S(s);
-    PREDICT_HAS_CURVE(s, "predict_get");
-    return predict_xfer(s, v, false);
-}
-
-extern "C" int apemost_hip_predict_set(apemost_hip_sampler *s, const apemost_hip_predict_view *v) {
-    CHECK_S(s);
-    PREDICT_HAS_CURVE(s, "predict_set");
-    return predict_xfer(s, v, true);
-}
-
-extern "C" int apemost_hip_predict_end(apemost_hip_sampler *s) {
-    CHECK_S(s);
-    PREDICT_HAS_CURVE(s, "predict_end");
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    predict_free(s);
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x,
-                                         const double *x, double *out) {
-    CHECK_S(s);
-    PREDICT_HAS_CURVE(s, "predict_curve");
-    if (!x)
-        n_x = s->cfg.n_data;
-    if (n < 1 || !params || !out || n_x < 1 || (u64)n * (u64)n_x > ((u64)1 << 26))
-        return fail(APEMOST_HIP_ERR_INVALID, "predict_curve: %d rows x %d abscissae, or a NULL array", n, n_x);
-    const int np = s->cfg.n_par;
-    const bool user = s->cfg.model == APEMOST_MODEL_USER;
-    int nc = user ? s->cfg.n_cols : 1; // a user model's abscissae are whole rows [n_x][n_cols], finite
-    std::vector<double> by_cols;
-    if (user && x) {
-        for (size_t i = 0; i < (size_t)n_x * nc; i++)
-            if (!std::isfinite(x[i]))
-                return fail(APEMOST_HIP_ERR_INVALID, "predict_curve: x[%zu] is not finite", i);
-        by_cols = rows_by_columns(x, n_x, nc);
-        x = by_cols.data();
-    }
-    double *d_par = nullptr, *d_x = nullptr, *d_out = nullptr;
-    hipError_t err = hipMalloc((void **)&d_par, (size_t)n * np * sizeof(double));
-    if (err == hipSuccess)
-        err = hipMalloc((void **)&d_x, (size_t)nc * n_x * sizeof(double));
-    if (err == hipSuccess)
-        err = hipMalloc((void **)&d_out, (size_t)n * n_x * sizeof(double));
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(d_par, params, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, s->stream);
-    if (err == hipSuccess)
-        err = x ? hipMemcpyAsync(d_x, x, (size_t)nc * n_x * sizeof(double), hipMemcpyHostToDevice, s->stream)
-                : hipMemcpyAsync(d_x, s->d.data, (size_t)nc * n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream);
-    if (err == hipSuccess && user) {
-        int np_ = np;
-        double sigma = s->sh.consts.sigma, hmin = s->sh.consts.hmin;
-        void *params_[] = {&d_par, &np_, &n_x, &nc, &d_x, &sigma, &hmin, &d_out};
-        err = user_launch(s->ua.predict_curve, (unsigned)((n_x + kPredictWave - 1) / kPredictWave) * (unsigned)n,
-                          kPredictWave, 0, s->stream, params_);
-    } else if (err == hipSuccess) {
-        const dim3 grid((unsigned)((n_x + kPredictWave - 1) / kPredictWave) * (unsigned)n), block(kPredictWave);
-        switch (s->cfg.model) {
-        case APEMOST_MODEL_SIMPLESIN:
-            hipLaunchKernelGGL(predict_curve_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->stream, d_par, np, n_x, d_x, d_out);
-            break;
-        case APEMOST_MODEL_SINE3:
-            hipLaunchKernelGGL(predict_curve_kernel<APEMOST_MODEL_SINE3>, grid, block, 0, s->stream, d_par, np, n_x, d_x, d_out);
-            break;
-        case APEMOST_MODEL_PULSE:
-            hipLaunchKernelGGL(predict_curve_kernel<APEMOST_MODEL_PULSE>, grid, block, 0, s->stream, d_par, np, n_x, d_x, d_out);
-            break;
-        default:
-            hipLaunchKernelGGL(predict_curve_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->stream, d_par, np, n_x, d_x, d_out);
-            break;
-        }
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(out, d_out, (size_t)n * n_x * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    const hipError_t sync = hipStreamSynchronize(s->stream);
-    for (double *p : {d_par, d_x, d_out})
-        if (p)
-            hipFree(p);
-    HIP_TRY(err);
-    HIP_TRY(sync);
-    return APEMOST_HIP_OK;
-}
-
-// ---- on-device pointwise log-likelihood (pt_pointwise.h) ----
-// a built-in model, or a user-supplied one with the pointwise hook
-#define POINTWISE_HAS_TERM(s, what)                                                                              \
-    do {                                                                                                        \
-        if ((s)->cfg.model == APEMOST_MODEL_USER) {                                                             \
-            const int rc_hooks = user_analysis(s);                                                              \
-            if (rc_hooks != APEMOST_HIP_OK)                                                                     \
-                return rc_hooks;                                                                                \
-            if (!(s)->ua.has_pointwise)                                                                         \
-                return fail(APEMOST_HIP_ERR_UNSUPPORTED,                                                        \
-                            what ": this user-supplied device model has no datum's term: it does not define "   \
-                                 "the hook apemost_user_pointwise (APEMOST_USER_POINTWISE, "                    \
-                                 "include/apemost_device_model.h)");                                            \
-        }                                                                                                       \
-    } while (0)
-
-constexpr int kPointwiseWords = 8; // origin, sum, sq, m_up, S_up, m_dn, S_dn, S2_dn
-
-static double pointwise_c(const apemost_hip_sampler *s) {
-    const double sigma = s->sh.consts.sigma;
-    const double t = -2.0 * sigma;
-    const double denom = t * sigma;
-    return 1.0 / denom;
-}
-
-extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg) {
-    CHECK_S(s);
-    POINTWISE_HAS_TERM(s, "pointwise_begin");
-    if (!cfg)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: config is NULL");
-    const int np = s->cfg.n_par, nd = s->cfg.n_data;
-    if (cfg->n_keep < 1 || cfg->n_keep > s->cfg.n_chains || !cfg->chains)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: n_keep %d outside [1,%d], or no chains", cfg->n_keep,
-                    s->cfg.n_chains);
-    for (int k = 0; k < cfg->n_keep; k++)
-        if (cfg->chains[k] < 0 || cfg->chains[k] >= s->cfg.n_chains || (k > 0 && cfg->chains[k] <= cfg->chains[k - 1]))
-            return fail(APEMOST_HIP_ERR_INVALID,
-                        "pointwise_begin: chains[%d] = %d: local chain indices in [0,%d), strictly increasing", k,
-                        cfg->chains[k], s->cfg.n_chains);
-    const u64 n_series = (u64)cfg->n_keep * (u64)nd;
-    if (n_series > ((u64)1 << 20))
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d chains x %d data: more than 2^20 series", cfg->n_keep,
-                    nd);
-    if (np > kPointwiseTile)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d parameters, more than %d", np, kPointwiseTile);
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream)); // a fold begun before may still be accumulating
-    pointwise_free(s);
-    s->pw.n_keep = cfg->n_keep;
-    s->pw.c = pointwise_c(s);
-    s->pw.n = 0;
-    const size_t ns = (size_t)n_series, nk = (size_t)cfg->n_keep;
-    const bool user = s->cfg.model == APEMOST_MODEL_USER;
-    const size_t nc = user ? (size_t)s->cfg.n_cols : 1; // a user model's data: all of its columns, in d_x
-    HIP_TRY(hipMalloc((void **)&s->pw.d_chains, nk * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&s->pw.d_x, ns * nc * sizeof(double)));
-    if (!user)
-        HIP_TRY(hipMalloc((void **)&s->pw.d_y, ns * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pw.d_state, kPointwiseWords * ns * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->pw.d_par, 2 * nk * np * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(s->pw.d_state, 0, kPointwiseWords * ns * sizeof(double), s->stream));
-    HIP_TRY(hipMemsetAsync(s->pw.d_par, 0, 2 * nk * np * sizeof(double), s->stream));
-    HIP_TRY(hipMemcpyAsync(s->pw.d_chains, cfg->chains, nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    for (int k = 0; k < cfg->n_keep; k++) {
-        // columns 0 and 1 of the kept chain's own ladder (the data is stored by columns, ladder after ladder)
-        const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
-        const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * nd;
-        HIP_TRY(hipMemcpyAsync(s->pw.d_x + (size_t)k * nc * nd, col0, nc * nd * sizeof(double), hipMemcpyDeviceToDevice,
-                               s->stream));
-        if (!user)
-            HIP_TRY(hipMemcpyAsync(s->pw.d_y + (size_t)k * nd, col0 + nd, (size_t)nd * sizeof(double),
-                               hipMemcpyDeviceToDevice, s->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's array is read until here)
-    s->pw.open = true;
-    return APEMOST_HIP_OK;
-}
-
-// ---- the tail of the pointwise fold (pt_pointwise_tail.h) ----
-static PointwiseTailArgs pointwise_tail_args(const apemost_hip_sampler *s, bool force) {
-    PointwiseTailArgs t;
-    t.buf = s->pw.tail.d_buf;
-    t.slots = s->pw.tail.d_slots;
-    t.thr = s->pw.tail.d_thr;
-    t.capacity = s->pw.tail.capacity;
-    t.B = s->pw.tail.B;
-    t.n_data = s->cfg.n_data;
-    t.n_blocks = (s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
-    t.force = force ? 1 : 0;
-    t.dense = nullptr;
-    t.count = nullptr;
-    return t;
-}
-
-static int pointwise_tail_compact(apemost_hip_sampler *s, bool force) {
-    const PointwiseTailArgs t = pointwise_tail_args(s, force);
-    const dim3 grid((unsigned)s->pw.n_keep * (unsigned)s->cfg.n_data), block(kTailThreads);
-    hipLaunchKernelGGL(pointwise_tail_compact_kernel, grid, block, (size_t)t.B * sizeof(unsigned long long), s->copy_stream, t);
-    HIP_TRY(hipGetLastError());
-    return APEMOST_HIP_OK;
-}
-
-// the kept steps of the fold piece `fold` (already launched), in tail pieces: append, then compact, on copy_stream
-static int pointwise_tail_pieces(apemost_hip_sampler *s, const PointwiseArgs &fold) {
-    const PointwiseTailArgs t = pointwise_tail_args(s, false);
-    const unsigned int piece = (unsigned int)tail_piece(t.capacity);
-    for (unsigned int k0 = 0; k0 < fold.n; k0 += piece) {
-        PointwiseArgs a = fold;
-        a.skip = fold.skip + (u64)k0 * fold.thin;
-        a.n = fold.n - k0 < piece ? fold.n - k0 : piece;
-        a.n0 = fold.n0 + k0;
-        const dim3 grid((unsigned)a.n_blocks * (unsigned)a.n_keep), block(kPointwiseWave);
-        PointwiseTailArgs tt = t;
-        switch (s->cfg.model) {
-        case APEMOST_MODEL_USER: {
-            void *params[] = {&a, &tt};
-            HIP_TRY(user_launch(s->ua.pointwise_tail_append, grid.x, block.x, 0, s->copy_stream, params));
-            break;
-        }
-        case APEMOST_MODEL_SIMPLESIN:
-            hipLaunchKernelGGL(pointwise_tail_append_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->copy_stream, a, tt);
-            break;
-        case APEMOST_MODEL_SINE3:
-            hipLaunchKernelGGL(pointwise_tail_append_kernel<APEMOST_MODEL_SINE3>, grid, block, 0, s->copy_stream, a, tt);
-            break;
-        case APEMOST_MODEL_PULSE:
-            hipLaunchKernelGGL(pointwise_tail_append_kernel<APEMOST_MODEL_PULSE>, grid, block, 0, s->copy_stream, a, tt);
-            break;
-        default:
-            hipLaunchKernelGGL(pointwise_tail_append_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->copy_stream, a, tt);
-            break;
-        }
-        HIP_TRY(hipGetLastError());
-        const int rc = pointwise_tail_compact(s, false);
-        if (rc != APEMOST_HIP_OK)
-            return rc;
-    }
-    return APEMOST_HIP_OK;
-}
-
-// Queued on copy_stream behind everything launched so far on the sampler's stream, like
-// apemost_hip_predict_accumulate; apemost_hip_samples_wait covers it.
-extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
-                                                uint64_t skip, uint64_t thin) {
-    CHECK_S(s);
-    POINTWISE_HAS_TERM(s, "pointwise_accumulate");
-    if (!s->pw.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: no pointwise_begin");
-    if (thin < 1 || (!d_samples && n_steps > 0))
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: bad arguments");
-    if (s->pw.tail.awaits_set)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: the tail was begun on a fold of %llu samples that "
-                    "pointwise_set loaded: pointwise_tail_set must load the tail of those samples first",
-                    (unsigned long long)s->pw.n);
-    const u64 kept = skip < n_steps ? (n_steps - skip + thin - 1) / thin : 0;
-    if (kept == 0)
-        return APEMOST_HIP_OK;
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const size_t ns = (size_t)s->pw.n_keep * s->cfg.n_data;
-    for (u64 k0 = 0; k0 < kept; k0 += kPointwisePiece) {
-        PointwiseArgs a;
-        a.rows = d_samples;
-        a.n_chains = s->cfg.n_chains;
-        a.n_par = s->cfg.n_par;
-        a.n_keep = s->pw.n_keep;
-        a.chains = s->pw.d_chains;
-        a.skip = skip + k0 * thin;
-        a.thin = thin;
-        a.n = (unsigned int)(kept - k0 < (u64)kPointwisePiece ? kept - k0 : (u64)kPointwisePiece);
-        a.n0 = s->pw.n;
-        a.n_data = s->cfg.n_data;
-        a.n_blocks = (s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
-        a.x = s->pw.d_x;
-        a.y = s->pw.d_y;
-        a.c = s->pw.c;
-        a.n_cols = s->cfg.n_cols;
-        a.sigma = s->sh.consts.sigma;
-        a.hmin = s->sh.consts.hmin;
-        a.origin = s->pw.d_state;
-        a.sum = s->pw.d_state + ns;
-        a.sq = s->pw.d_state + 2 * ns;
-        a.m_up = s->pw.d_state + 3 * ns;
-        a.S_up = s->pw.d_state + 4 * ns;
-        a.m_dn = s->pw.d_state + 5 * ns;
-        a.S_dn = s->pw.d_state + 6 * ns;
-        a.S2_dn = s->pw.d_state + 7 * ns;
-        a.par_origin = s->pw.d_par;
-        a.par_sum = s->pw.d_par + (size_t)s->pw.n_keep * s->cfg.n_par;
-        const dim3 grid((unsigned)(a.n_blocks + 1) * (unsigned)a.n_keep), block(kPointwiseWave);
-        switch (s->cfg.model) {
-        case APEMOST_MODEL_USER: {
-            void *params[] = {&a};
-            HIP_TRY(user_launch(s->ua.pointwise_fold, grid.x, block.x, 0, s->copy_stream, params));
-            break;
-        }
-        case APEMOST_MODEL_SIMPLESIN:
-            hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->copy_stream, a);
-            break;
-        case APEMOST_MODEL_SINE3:
-            hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_SINE3>, grid, block, 0, s->copy_stream, a);
-            break;
-        case APEMOST_MODEL_PULSE:
-            hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_PULSE>, grid, block, 0, s->copy_stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL(pointwise_fold_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->copy_stream, a);
-            break;
-        }
-        HIP_TRY(hipGetLastError());
-        if (s->pw.tail.capacity > 0) {
-            rc = pointwise_tail_pieces(s, a);
-            if (rc != APEMOST_HIP_OK)
-                return rc;
-        }
-        s->pw.n += a.n;
-        s->pw.n_set = false;
-    }
-    return APEMOST_HIP_OK;
-}
-
-static int pointwise_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v, bool up) {
-    if (!s->pw.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_%s: no pointwise_begin", up ? "set" : "get");
-    if (!v)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise view is NULL");
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    const size_t nk = (size_t)s->pw.n_keep, ns = nk * s->cfg.n_data, np = (size_t)s->cfg.n_par;
-    // stream order: behind every accumulate queued so far, on the stream they run on
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-    double *const host[kPointwiseWords] = {v->origin, v->sum, v->sq, v->m_up, v->S_up, v->m_dn, v->S_dn, v->S2_dn};
-#define POINTWISE_COPY(dev, hst, bytes)                                                                        \
-    do {                                                                                                       \
-        if ((hst) && (bytes) > 0)                                                                              \
-            HIP_TRY(up ? hipMemcpyAsync((void *)(dev), (const void *)(hst), (bytes), kind, s->copy_stream)     \
-                       : hipMemcpyAsync((void *)(hst), (const void *)(dev), (bytes), kind, s->copy_stream));   \
-    } while (0)
-    for (int q = 0; q < kPointwiseWords; q++)
-        POINTWISE_COPY(s->pw.d_state + (size_t)q * ns, host[q], ns * sizeof(double));
-    POINTWISE_COPY(s->pw.d_par, v->par_origin, nk * np * sizeof(double));
-    POINTWISE_COPY(s->pw.d_par + nk * np, v->par_sum, nk * np * sizeof(double));
-#undef POINTWISE_COPY
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    if (v->n) {
-        if (up) {
-            s->pw.n = *v->n;
-            s->pw.n_set = true;
-        } else
-            *v->n = s->pw.n;
-    }
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_pointwise_get(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
-    CHECK_S(s);
-    POINTWISE_HAS_TERM(s, "pointwise_get");
-    return pointwise_xfer(s, v, false);
-}
-
-extern "C" int apemost_hip_pointwise_set(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
-    CHECK_S(s);
-    POINTWISE_HAS_TERM(s, "pointwise_set");
-    return pointwise_xfer(s, v, true);
-}
-
-extern "C" int apemost_hip_pointwise_end(apemost_hip_sampler *s) {
-    CHECK_S(s);
-    POINTWISE_HAS_TERM(s, "pointwise_end");
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    pointwise_free(s);
-    return APEMOST_HIP_OK;
-}
-
-// padded series (64 per block of data) times the slots of a series' buffer
-static u64 pointwise_tail_slots(const apemost_hip_sampler *s, int B) {
-    const u64 n_blocks = ((u64)s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
-    return (u64)s->pw.n_keep * n_blocks * kPointwiseWave * (u64)B;
-}
-
-extern "C" int apemost_hip_pointwise_tail_begin(apemost_hip_sampler *s, int32_t capacity) {
-    if (!s)
-        return fail(APEMOST_HIP_ERR_INVALID, "sampler is NULL");
-    if (capacity < 2 || capacity > kTailMaxCapacity)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: capacity %d outside [2,%d]", capacity, kTailMaxCapacity);
-    CHECK_S(s);
-    POINTWISE_HAS_TERM(s, "pointwise_tail_begin");
-    if (!s->pw.open)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: no pointwise_begin");
-    if (s->pw.n > 0 && !s->pw.n_set)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: the fold has accumulated %llu samples whose tail is "
-                    "lost: begin the tail before the first accumulate, or right behind pointwise_set",
-                    (unsigned long long)s->pw.n);
-    const u64 limit = (u64)1 << 28;
-    const int B = tail_buffer(capacity);
-    if (pointwise_tail_slots(s, B) > limit) {
-        int fits = 0; // the largest capacity whose buffers fit
-        for (int b = kTailMaxB; b >= 2 * kTailMinP && !fits; b >>= 1)
-            if (pointwise_tail_slots(s, b) <= limit)
-                fits = b / 2;
-        if (fits)
-            return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: %d chains x %d data (in blocks of 64) x %d slots "
-                        "for capacity %d: more than 2^28 slots (2 GiB); the largest capacity that fits is %d",
-                        s->pw.n_keep, s->cfg.n_data, B, capacity, fits);
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: %d chains x %d data (in blocks of 64) x %d slots for "
-                    "capacity %d: more than 2^28 slots (2 GiB); the largest capacity that fits is 0: no capacity fits, "
-                    "keep fewer chains", s->pw.n_keep, s->cfg.n_data, B, capacity);
-    }
-    if (s->copy_stream)
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    pointwise_tail_free(s);
-    const size_t ns = (size_t)s->pw.n_keep * s->cfg.n_data;
-    double *buf = nullptr;
-    unsigned int *slots = nullptr;
-    unsigned long long *thr = nullptr;
-    hipError_t err = hipMalloc((void **)&buf, (size_t)pointwise_tail_slots(s, B) * sizeof(double));
-    if (err == hipSuccess)
-        err = hipMalloc((void **)&slots, ns * sizeof(unsigned int));
-    if (err == hipSuccess)
-        err = hipMalloc((void **)&thr, ns * sizeof(unsigned long long));
-    if (err == hipSuccess)
-        err = hipMemsetAsync(slots, 0, ns * sizeof(unsigned int), s->stream);
-    if (err == hipSuccess)
-        err = hipMemsetAsync(thr, 0, ns * sizeof(unsigned long long), s->stream);
-    if (err == hipSuccess)
-        err = hipStreamSynchronize(s->stream);
-    if (err != hipSuccess) { // the fold stays as it was, without a tail
-        for (void *p : {(void *)buf, (void *)slots, (void *)thr})
-            if (p)
-                hipFree(p);
-        HIP_TRY(err);
-    }
-    s->pw.tail.capacity = capacity;
-    s->pw.tail.B = B;
-    s->pw.tail.d_buf = buf;
-    s->pw.tail.d_slots = slots;
-    s->pw.tail.d_thr = thr;
-    s->pw.tail.awaits_set = s->pw.n > 0;
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_pointwise_tail_capacity(apemost_hip_sampler *s, int32_t *capacity) {
-    if (!s)
-        return fail(APEMOST_HIP_ERR_INVALID, "sampler is NULL");
-    if (!capacity)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_capacity: capacity is NULL");
-    *capacity = s->pw.open ? s->pw.tail.capacity : 0;
-    return APEMOST_HIP_OK;
-}
-
-static int pointwise_tail_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v, bool up) {
-    const char *what = up ? "set" : "get";
-    if (!s->pw.open || s->pw.tail.capacity == 0)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_%s: no pointwise_tail_begin", what);
-    if (!v || !v->count || !v->values)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_%s: the view or one of its arrays is NULL", what);
-    const size_t ns = (size_t)s->pw.n_keep * s->cfg.n_data, cap = (size_t)s->pw.tail.capacity;
-    if (up)
-        for (size_t q = 0; q < ns; q++) {
-            if (v->count[q] > cap)
-                return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_set: count[%zu] = %llu, more than the capacity %zu", q,
-                            (unsigned long long)v->count[q], cap);
-            for (size_t j = 0; j < (size_t)v->count[q]; j++)
-                if (v->values[q * cap + j] != v->values[q * cap + j])
-                    return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_set: values[%zu][%zu] is NaN: a tail holds none", q, j);
-        }
-    int rc = ensure_copy_stream(s);
-    if (rc != APEMOST_HIP_OK)
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_copy, 0));
-    PointwiseTailArgs t = pointwise_tail_args(s, true);
-    hipError_t err = hipMalloc((void **)&t.dense, ns * cap * sizeof(double));
-    if (err == hipSuccess)
-        err = hipMalloc((void **)&t.count, ns * sizeof(unsigned long long));
-    const dim3 grid((unsigned)ns, (unsigned)((cap + kTailThreads - 1) / kTailThreads)), block(kTailThreads);
-    if (err == hipSuccess && up) {
-        err = hipMemcpyAsync(t.dense, v->values, ns * cap * sizeof(double), hipMemcpyHostToDevice, s->copy_stream);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(t.count, v->count, ns * sizeof(unsigned long long), hipMemcpyHostToDevice, s->copy_stream);
-        if (err == hipSuccess) {
-            hipLaunchKernelGGL(pointwise_tail_scatter_kernel, grid, block, 0, s->copy_stream, t);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess) // sorts what was loaded and sets every threshold from it
-            err = pointwise_tail_compact(s, true) == APEMOST_HIP_OK ? hipSuccess : hipErrorLaunchFailure;
-    } else if (err == hipSuccess) {
-        err = pointwise_tail_compact(s, true) == APEMOST_HIP_OK ? hipSuccess : hipErrorLaunchFailure;
-        if (err == hipSuccess) {
-            hipLaunchKernelGGL(pointwise_tail_gather_kernel, grid, block, 0, s->copy_stream, t);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(v->values, t.dense, ns * cap * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(v->count, t.count, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->copy_stream);
-    }
-    const hipError_t sync = hipStreamSynchronize(s->copy_stream);
-    for (void *p : {(void *)t.dense, (void *)t.count})
-        if (p)
-            hipFree(p);
-    HIP_TRY(err);
-    HIP_TRY(sync);
-    if (up)
-        s->pw.tail.awaits_set = false;
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_pointwise_tail_get(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v) {
-    CHECK_S(s);
-    return pointwise_tail_xfer(s, v, false);
-}
-
-extern "C" int apemost_hip_pointwise_tail_set(apemost_hip_sampler *s, const apemost_hip_pointwise_tail_view *v) {
-    CHECK_S(s);
-    return pointwise_tail_xfer(s, v, true);
-}
-
-extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int32_t ladder, int32_t n,
-                                                    const double *params, double *out) {
-    CHECK_S(s);
-    POINTWISE_HAS_TERM(s, "pointwise_loglike");
-    const int np = s->cfg.n_par, nd = s->cfg.n_data;
-    if (ladder < 0 || ladder >= (s->batch ? s->n_ladders : 1))
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: ladder %d outside [0,%d)", ladder,
-                    s->batch ? s->n_ladders : 1);
-    if (n < 1 || !params || !out || (u64)n * (u64)nd > ((u64)1 << 26))
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: %d rows x %d data, or a NULL array", n, nd);
-    double *d_par = nullptr, *d_out = nullptr;
-    hipError_t err = hipMalloc((void **)&d_par, (size_t)n * np * sizeof(double));
-    if (err == hipSuccess)
-        err = hipMalloc((void **)&d_out, (size_t)n * nd * sizeof(double));
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(d_par, params, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, s->stream);
-    if (err == hipSuccess) {
-        const dim3 grid((unsigned)((nd + kPointwiseWave - 1) / kPointwiseWave) * (unsigned)n), block(kPointwiseWave);
-        // the ladder's columns 0 and 1 (the data is stored by columns, ladder after ladder)
-        const double *x = s->d.data + (size_t)ladder * s->cfg.n_cols * nd, *y = x + nd;
-        const double c = pointwise_c(s);
-        switch (s->cfg.model) {
-        case APEMOST_MODEL_USER: { // all n_cols columns of the ladder's rows
-            int np_ = np, nd_ = nd, nc = s->cfg.n_cols;
-            double sigma = s->sh.consts.sigma, hmin = s->sh.consts.hmin;
-            void *params_[] = {&d_par, &np_, &nd_, &nc, &x, &sigma, &hmin, &d_out};
-            err = user_launch(s->ua.pointwise_loglike, grid.x, block.x, 0, s->stream, params_);
-            break;
-        }
-        case APEMOST_MODEL_SIMPLESIN:
-            hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_SIMPLESIN>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
-            break;
-        case APEMOST_MODEL_SINE3:
-            hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_SINE3>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
-            break;
-        case APEMOST_MODEL_PULSE:
-            hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_PULSE>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
-            break;
-        default:
-            hipLaunchKernelGGL(pointwise_loglike_kernel<APEMOST_MODEL_PULSE_VROT>, grid, block, 0, s->stream, d_par, np, nd, x, y, c, d_out);
-            break;
-        }
-        if (err == hipSuccess)
-            err = hipGetLastError();
-    }
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(out, d_out, (size_t)n * nd * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    const hipError_t sync = hipStreamSynchronize(s->stream);
-    for (double *p : {d_par, d_out})
-        if (p)
-            hipFree(p);
-    HIP_TRY(err);
-    HIP_TRY(sync);
-    return APEMOST_HIP_OK;
-}
-
-extern "C" int apemost_hip_pointwise_loglike(apemost_hip_sampler *s, int32_t n, const double *params, double *out) {
-    return apemost_hip_pointwise_loglike_ladder(s, 0, n, params, out);
-}
+// ---- the on-device folds: one protocol (abi/fold_common.h), and what is particular to each ----
+#include "abi/fold_common.h"
+#include "abi/fold_summary.h"
+#include "abi/fold_peaks.h"
+#include "abi/fold_joint.h"
+#include "abi/fold_evidence.h"
+#include "abi/fold_autocorr.h"
+#include "abi/fold_predict.h"
+#include "abi/fold_pointwise.h"
 
 // Host arithmetic only (no device): tools/peaks.c:130, 177-200 and the selection sort of src/gsl_helper.c:102-127.
 extern "C" int apemost_hip_peaks_table(const apemost_hip_peaks_view *v, int32_t n_par, int32_t k, int32_t p,

@@ -7,18 +7,14 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include "run_io.h"
+
+/* run_io.h with this file's word in the messages */
+#define alloc_or_die(count, size) run_alloc_or_die(count, size, "autocorrelation")
+#define read_or_die(p, size, count, f, path) run_read_or_die(p, size, count, f, path, "autocorr file")
 
 #define RUN_AUTOCORR_MAGIC "APEMOSTA"
 #define RUN_AUTOCORR_VERSION 1
-
-static void *alloc_or_die(size_t count, size_t size) {
-    void *p = calloc(count > 0 ? count : 1, size);
-    if (p == NULL) {
-        fprintf(stderr, "autocorrelation: out of memory\n");
-        exit(1);
-    }
-    return p;
-}
 
 void run_autocorr_alloc(run_autocorr *r) {
     const size_t nc = r->n_cols, L = r->max_lag;
@@ -38,13 +34,6 @@ void run_autocorr_free(run_autocorr *r) {
     free(r->head);
     free(r->tail);
     memset(r, 0, sizeof *r);
-}
-
-static void read_or_die(void *p, size_t size, size_t count, FILE *f, const char *path) {
-    if (count > 0 && fread(p, size, count, f) != count) {
-        fprintf(stderr, "%s: truncated autocorr file\n", path);
-        exit(1);
-    }
 }
 
 int run_autocorr_read(const char *path, run_autocorr *r) {
@@ -86,25 +75,8 @@ int run_autocorr_read(const char *path, run_autocorr *r) {
     return 0;
 }
 
-static FILE *open_or_die(const char *path, const char *mode) {
-    FILE *f = fopen(path, mode);
-    if (f == NULL) {
-        fprintf(stderr, "opening file %s failed\n", path);
-        perror("opening file failed");
-        exit(1);
-    }
-    return f;
-}
-
-static void close_or_die(FILE *f, const char *path) {
-    if (fclose(f) != 0) {
-        fprintf(stderr, "writing %s failed\n", path);
-        exit(1);
-    }
-}
-
 void run_autocorr_write(const char *path, const run_autocorr *r) {
-    FILE *f = open_or_die(path, "wb");
+    FILE *f = run_open_or_die(path, "wb");
     const size_t nc = r->n_cols, L = r->max_lag;
     uint32_t u32[6];
     uint64_t u64[2];
@@ -126,7 +98,7 @@ void run_autocorr_write(const char *path, const run_autocorr *r) {
     fwrite(r->lag, sizeof(double), nc * L, f);
     fwrite(r->head, sizeof(double), nc * (L - 1), f);
     fwrite(r->tail, sizeof(double), nc * (L - 1), f);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }
 
 /* lags that have at least one pair */
@@ -207,15 +179,8 @@ double run_autocorr_tau_geyer(const run_autocorr *r, const double *acov, long *w
 }
 
 /* "%.15e", a NaN of either sign as nan */
-static void print_value(FILE *f, double v) {
-    if (v != v)
-        fprintf(f, "nan");
-    else
-        fprintf(f, "%.15e", v);
-}
-
 void run_autocorr_write_text(const char *path, const run_autocorr *r, const char **names) {
-    FILE *f = open_or_die(path, "w");
+    FILE *f = run_open_or_die(path, "w");
     double *acov = (double *)alloc_or_die(r->max_lag, sizeof(double));
     const double n = (double)r->n;
     unsigned int c;
@@ -232,21 +197,21 @@ void run_autocorr_write_text(const char *path, const run_autocorr *r, const char
             fprintf(f, "%s\t", names[col]);
         else
             fprintf(f, "%s\t", col == r->n_par ? "prob" : "prob-prior");
-        print_value(f, mean);
+        run_print_value(f, mean);
         fprintf(f, "\t");
-        print_value(f, acov[0]);
+        run_print_value(f, acov[0]);
         fprintf(f, "\t");
-        print_value(f, ts);
+        run_print_value(f, ts);
         fprintf(f, "\t%ld\t", window);
-        print_value(f, n / ts);
+        run_print_value(f, n / ts);
         fprintf(f, "\t");
         t = acov[0] * ts;
         t = t / n;
-        print_value(f, sqrt(t));
+        run_print_value(f, sqrt(t));
         fprintf(f, "\t");
-        print_value(f, tg);
+        run_print_value(f, tg);
         fprintf(f, "\n");
     }
     free(acov);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }

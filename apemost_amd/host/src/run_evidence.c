@@ -8,18 +8,14 @@
 
 #include "parallel_tempering_beta.h"
 #include "run_summary.h"
+#include "run_io.h"
+
+/* run_io.h with this file's word in the messages */
+#define alloc_or_die(count) ((double *)run_alloc_or_die(count, sizeof(double), "evidence"))
+#define read_or_die(p, size, count, f, path) run_read_or_die(p, size, count, f, path, "evidence file")
 
 #define RUN_EVIDENCE_MAGIC "APEMOSTE"
 #define RUN_EVIDENCE_VERSION 1
-
-static double *alloc_or_die(size_t count) {
-    double *p = (double *)calloc(count > 0 ? count : 1, sizeof(double));
-    if (p == NULL) {
-        fprintf(stderr, "evidence: out of memory\n");
-        exit(1);
-    }
-    return p;
-}
 
 static void evidence_alloc(run_evidence *r) {
     const size_t nc = r->n_chains;
@@ -45,13 +41,6 @@ static void evidence_free(run_evidence *r) {
     free(r->S);
     free(r->batch);
     memset(r, 0, sizeof *r);
-}
-
-static void read_or_die(void *p, size_t size, size_t count, FILE *f, const char *path) {
-    if (count > 0 && fread(p, size, count, f) != count) {
-        fprintf(stderr, "%s: truncated evidence file\n", path);
-        exit(1);
-    }
 }
 
 /* 0: read; -1: no such file.  *n_ladders receives the ladders the file holds */
@@ -96,25 +85,8 @@ static int evidence_read(const char *path, run_evidence *r, uint32_t *n_ladders)
     return 0;
 }
 
-static FILE *open_or_die(const char *path, const char *mode) {
-    FILE *f = fopen(path, mode);
-    if (f == NULL) {
-        fprintf(stderr, "opening file %s failed\n", path);
-        perror("opening file failed");
-        exit(1);
-    }
-    return f;
-}
-
-static void close_or_die(FILE *f, const char *path) {
-    if (fclose(f) != 0) {
-        fprintf(stderr, "writing %s failed\n", path);
-        exit(1);
-    }
-}
-
 static void evidence_write(const char *path, const run_evidence *r) {
-    FILE *f = open_or_die(path, "wb");
+    FILE *f = run_open_or_die(path, "wb");
     const size_t nc = r->n_chains;
     uint32_t u32[4];
     uint64_t u64[4];
@@ -138,7 +110,7 @@ static void evidence_write(const char *path, const run_evidence *r) {
     fwrite(r->m, sizeof(double), 2 * nc, f);
     fwrite(r->S, sizeof(double), 2 * nc, f);
     fwrite(r->batch, sizeof(double), nc * (size_t)(r->max_batches + 1), f);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }
 
 /* the view of shard j over the whole ladder's arrays; m and S of a shard are [2][its chains], staged in `ms` */
@@ -232,16 +204,9 @@ void run_evidence_open(run_evidence *r, apemost_ladder *l, mcmc **chains, const 
 }
 
 /* "%.15e", a NaN of either sign as nan */
-static void print_value(FILE *f, double v) {
-    if (v != v)
-        fprintf(f, "nan");
-    else
-        fprintf(f, "%.15e", v);
-}
-
 static void print_total(FILE *f, const char *name, double v) {
     fprintf(f, "%s\t", name);
-    print_value(f, v);
+    run_print_value(f, v);
     fprintf(f, "\n");
 }
 
@@ -275,7 +240,7 @@ static void evidence_write_text(const char *path, const run_evidence *r) {
     double base_rect, base_down, rect, trap, corr, ss_up, ss_down, e_rect = 0, e_trap = 0;
     unsigned int c;
     uint64_t k;
-    FILE *f = open_or_die(path, "w");
+    FILE *f = run_open_or_die(path, "w");
     for (c = 0; c < nc; c++) {
         const double beta = r->betas[c], mean_v = r->origin[c] + r->sum[c] / n;
         const double *batch = r->batch + (size_t)c * (size_t)(r->max_batches + 1);
@@ -290,17 +255,17 @@ static void evidence_write_text(const char *path, const run_evidence *r) {
         mcse[c] = nb < 2 ? sqrt(-1.0) : sqrt(errorsum / (double)nb) / sqrt((double)nb) / beta;
         up[c] = r->m[c] + log(r->S[c] / n);
         down[c] = r->m[nc + c] + log(r->S[nc + c] / n);
-        print_value(f, beta);
+        run_print_value(f, beta);
         fprintf(f, "\t");
-        print_value(f, mean[c]);
+        run_print_value(f, mean[c]);
         fprintf(f, "\t");
-        print_value(f, var[c]);
+        run_print_value(f, var[c]);
         fprintf(f, "\t");
-        print_value(f, mcse[c]);
+        run_print_value(f, mcse[c]);
         fprintf(f, "\t");
-        print_value(f, up[c]);
+        run_print_value(f, up[c]);
         fprintf(f, "\t");
-        print_value(f, down[c]);
+        run_print_value(f, down[c]);
         fprintf(f, "\n");
     }
     base_rect = mean[nc - 1] * r->betas[nc - 1];
@@ -337,7 +302,7 @@ static void evidence_write_text(const char *path, const run_evidence *r) {
     free(mcse);
     free(up);
     free(down);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }
 
 void run_evidence_close(run_evidence *r, apemost_ladder *l, const unsigned int *lo, unsigned int n_shards) {

@@ -8,18 +8,14 @@
 
 #include "apemost_bridge.h"
 #include "mcmc_gettersetter.h"
+#include "run_io.h"
+
+/* run_io.h with this file's word in the messages */
+#define alloc_or_die(count, size) run_alloc_or_die(count, size, "joint marginals")
+#define read_or_die(p, size, count, f, path) run_read_or_die(p, size, count, f, path, "joint file")
 
 #define RUN_JOINT_MAGIC "APEMOSTJ"
 #define RUN_JOINT_VERSION 1
-
-static void *alloc_or_die(size_t count, size_t size) {
-    void *p = calloc(count > 0 ? count : 1, size);
-    if (p == NULL) {
-        fprintf(stderr, "joint marginals: out of memory\n");
-        exit(1);
-    }
-    return p;
-}
 
 static size_t tri_count(const run_joint *r) {
     return (size_t)r->n_par * (r->n_par + 1) / 2;
@@ -48,13 +44,6 @@ static void joint_free(run_joint *r) {
     free(r->cross);
     free(r->counts);
     memset(r, 0, sizeof *r);
-}
-
-static void read_or_die(void *p, size_t size, size_t count, FILE *f, const char *path) {
-    if (count > 0 && fread(p, size, count, f) != count) {
-        fprintf(stderr, "%s: truncated joint file\n", path);
-        exit(1);
-    }
 }
 
 /* 0: read; -1: no such file.  *n_keep and *chain receive the kept chains and the first of them */
@@ -100,25 +89,8 @@ static int joint_read(const char *path, run_joint *r, uint32_t *n_keep, int32_t 
     return 0;
 }
 
-static FILE *open_or_die(const char *path, const char *mode) {
-    FILE *f = fopen(path, mode);
-    if (f == NULL) {
-        fprintf(stderr, "opening file %s failed\n", path);
-        perror("opening file failed");
-        exit(1);
-    }
-    return f;
-}
-
-static void close_or_die(FILE *f, const char *path) {
-    if (fclose(f) != 0) {
-        fprintf(stderr, "writing %s failed\n", path);
-        exit(1);
-    }
-}
-
 static void joint_write(const char *path, const run_joint *r) {
-    FILE *f = open_or_die(path, "wb");
+    FILE *f = run_open_or_die(path, "wb");
     uint32_t u32[6];
     uint64_t u64[2];
     const int32_t chain = 0;
@@ -141,7 +113,7 @@ static void joint_write(const char *path, const run_joint *r) {
     fwrite(r->sum, sizeof(double), r->n_par, f);
     fwrite(r->cross, sizeof(double), tri_count(r), f);
     fwrite(r->counts, sizeof(uint64_t), (size_t)r->n_pairs * r->nbins * r->nbins, f);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }
 
 static void joint_view(run_joint *r, apemost_hip_joint_view *v) {
@@ -221,13 +193,6 @@ void run_joint_open(run_joint *r, apemost_hip_sampler *s, const mcmc *chain0, un
 }
 
 /* "%.15e", a NaN of either sign as nan */
-static void print_value(FILE *f, double v) {
-    if (v != v)
-        fprintf(f, "nan");
-    else
-        fprintf(f, "%.15e", v);
-}
-
 /* the summary's edge b of n over [lo, hi] (gsl_histogram_set_ranges_uniform, the top one widened as create_hist()).
  * The definition it must follow is summary_edge of apemost_amd/csrc/pt_summary.h, which bins the samples: the same
  * two products and one sum, unfused (summary.edges of apemost_amd/summary.py is the Python statement of it). */
@@ -249,7 +214,7 @@ static void write_pair(const run_joint *r, unsigned int q, const char **names) {
     unsigned int a, b;
     FILE *f;
     sprintf(name, "%.200s-%.200s.joint", names[i], names[j]);
-    f = open_or_die(name, "w");
+    f = run_open_or_die(name, "w");
     ey = (char(*)[32])alloc_or_die((size_t)n + 1, 32);
     for (b = 0; b <= n; b++)
         sprintf(ey[b], "%.15e", joint_edge(r->lo[j], r->hi[j], b, n));
@@ -261,7 +226,7 @@ static void write_pair(const run_joint *r, unsigned int q, const char **names) {
         fprintf(f, "\n");
     }
     free(ey);
-    close_or_die(f, name);
+    run_close_or_die(f, name);
 }
 
 /* cov_ij = (cross_ij - sum_i sum_j / n) / (n - 1); corr_ij = cov_ij / (sqrt(cov_ii) sqrt(cov_jj)), the diagonal 1 where
@@ -272,7 +237,7 @@ static void write_correlation(const run_joint *r) {
     double *cov = (double *)alloc_or_die((size_t)np * np, sizeof(double));
     double *sd = (double *)alloc_or_die(np, sizeof(double));
     unsigned int i, j;
-    FILE *f = open_or_die("correlation.matrix", "w");
+    FILE *f = run_open_or_die("correlation.matrix", "w");
     for (i = 0; i < np; i++)
         for (j = 0; j < np; j++) {
             const double cr = r->cross[i <= j ? tri_index(r, i, j) : tri_index(r, j, i)];
@@ -291,13 +256,13 @@ static void write_correlation(const run_joint *r) {
                 x = (v > 0 && v - v == 0) ? 1.0 : sqrt(-1.0);
             if (j > 0)
                 fprintf(f, "\t");
-            print_value(f, x);
+            run_print_value(f, x);
         }
         fprintf(f, "\n");
     }
     free(cov);
     free(sd);
-    close_or_die(f, "correlation.matrix");
+    run_close_or_die(f, "correlation.matrix");
 }
 
 void run_joint_close(run_joint *r, apemost_hip_sampler *s, const mcmc *chain0) {

@@ -7,20 +7,16 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include "run_io.h"
+
+/* run_io.h with this file's word in the messages */
+#define alloc_or_die(count, size) run_alloc_or_die(count, size, "pointwise")
+#define read_or_die(p, size, count, f, path) run_read_or_die(p, size, count, f, path, "pointwise file")
 
 #define RUN_POINTWISE_MAGIC "APEMOSTW"
 #define RUN_POINTWISE_VERSION 1
 #define RUN_POINTWISE_TAIL_MAGIC "APEMOSTT"
 #define RUN_POINTWISE_TAIL_VERSION 1
-
-static void *alloc_or_die(size_t count, size_t size) {
-    void *p = calloc(count > 0 ? count : 1, size);
-    if (p == NULL) {
-        fprintf(stderr, "pointwise: out of memory\n");
-        exit(1);
-    }
-    return p;
-}
 
 void run_pointwise_alloc(run_pointwise *r) {
     const size_t nd = r->n_data;
@@ -65,13 +61,6 @@ void run_pointwise_tail_free(run_pointwise_tail *t) {
     free(t->count);
     free(t->values);
     memset(t, 0, sizeof *t);
-}
-
-static void read_or_die(void *p, size_t size, size_t count, FILE *f, const char *path) {
-    if (count > 0 && fread(p, size, count, f) != count) {
-        fprintf(stderr, "%s: truncated pointwise file\n", path);
-        exit(1);
-    }
 }
 
 int run_pointwise_read(const char *path, run_pointwise *r) {
@@ -153,25 +142,8 @@ int run_pointwise_tail_read(const char *path, run_pointwise_tail *t) {
     return 0;
 }
 
-static FILE *open_or_die(const char *path, const char *mode) {
-    FILE *f = fopen(path, mode);
-    if (f == NULL) {
-        fprintf(stderr, "opening file %s failed\n", path);
-        perror("opening file failed");
-        exit(1);
-    }
-    return f;
-}
-
-static void close_or_die(FILE *f, const char *path) {
-    if (fclose(f) != 0) {
-        fprintf(stderr, "writing %s failed\n", path);
-        exit(1);
-    }
-}
-
 void run_pointwise_write(const char *path, const run_pointwise *r) {
-    FILE *f = open_or_die(path, "wb");
+    FILE *f = run_open_or_die(path, "wb");
     const size_t nd = r->n_data;
     uint32_t u32[8];
     uint64_t u64[2];
@@ -198,11 +170,11 @@ void run_pointwise_write(const char *path, const run_pointwise *r) {
     fwrite(r->par_origin, sizeof(double), r->n_par, f);
     fwrite(r->par_sum, sizeof(double), r->n_par, f);
     fwrite(r->at_mean, sizeof(double), nd, f);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }
 
 void run_pointwise_tail_write(const char *path, const run_pointwise_tail *t) {
-    FILE *f = open_or_die(path, "wb");
+    FILE *f = run_open_or_die(path, "wb");
     const double zero = 0.0;
     uint32_t u32[8], i, j;
     uint64_t u64[2];
@@ -222,7 +194,7 @@ void run_pointwise_tail_write(const char *path, const run_pointwise_tail *t) {
     for (i = 0; i < t->n_data; i++)
         for (j = 0; j < t->capacity; j++)
             fwrite(j < t->count[i] ? &t->values[(size_t)i * t->capacity + j] : &zero, sizeof(double), 1, f);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }
 
 /* what Pointwise gives per datum (apemost_amd/pointwise.py), operation for operation */
@@ -258,46 +230,39 @@ static pointwise_datum datum(const run_pointwise *r, uint32_t i) {
 }
 
 /* "%.15e", a NaN of either sign as nan */
-static void print_value(FILE *f, double v) {
-    if (v != v)
-        fprintf(f, "nan");
-    else
-        fprintf(f, "%.15e", v);
-}
-
 void run_pointwise_write_text(const char *path, const run_pointwise *r) {
-    FILE *f = open_or_die(path, "w");
+    FILE *f = run_open_or_die(path, "w");
     uint32_t i;
     for (i = 0; i < r->n_data; i++) {
         const pointwise_datum d = datum(r, i);
-        print_value(f, r->x[i]);
+        run_print_value(f, r->x[i]);
         fprintf(f, "\t");
-        print_value(f, r->y[i]);
+        run_print_value(f, r->y[i]);
         fprintf(f, "\t");
-        print_value(f, d.mean);
+        run_print_value(f, d.mean);
         fprintf(f, "\t");
-        print_value(f, sqrt(d.var));
+        run_print_value(f, sqrt(d.var));
         fprintf(f, "\t");
-        print_value(f, d.lppd);
+        run_print_value(f, d.lppd);
         fprintf(f, "\t");
-        print_value(f, d.var);
+        run_print_value(f, d.var);
         fprintf(f, "\t");
-        print_value(f, d.elpd_loo);
+        run_print_value(f, d.elpd_loo);
         fprintf(f, "\t");
-        print_value(f, d.ess);
+        run_print_value(f, d.ess);
         fprintf(f, "\n");
     }
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }
 
 static void print_named(FILE *f, const char *name, double v) {
     fprintf(f, "%s\t", name);
-    print_value(f, v);
+    run_print_value(f, v);
     fprintf(f, "\n");
 }
 
 void run_pointwise_write_criteria(const char *path, const run_pointwise *r) {
-    FILE *f = open_or_die(path, "w");
+    FILE *f = run_open_or_die(path, "w");
     const double nd = (double)r->n_data;
     double lppd = 0.0, p1 = 0.0, p2 = 0.0, waic = 0.0, loo = 0.0, at = 0.0, mean = 0.0, spread = 0.0, centre, p_dic, t, u;
     uint32_t i;
@@ -336,5 +301,5 @@ void run_pointwise_write_criteria(const char *path, const run_pointwise *r) {
     u = 2.0 * p_dic;
     print_named(f, "dic", t + u);
     print_named(f, "p_dic", p_dic);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }

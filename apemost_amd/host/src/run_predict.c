@@ -7,18 +7,14 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include "run_io.h"
+
+/* run_io.h with this file's word in the messages */
+#define alloc_or_die(count, size) run_alloc_or_die(count, size, "predict")
+#define read_or_die(p, size, count, f, path) run_read_or_die(p, size, count, f, path, "predict file")
 
 #define RUN_PREDICT_MAGIC "APEMOSTP"
 #define RUN_PREDICT_VERSION 1
-
-static void *alloc_or_die(size_t count, size_t size) {
-    void *p = calloc(count > 0 ? count : 1, size);
-    if (p == NULL) {
-        fprintf(stderr, "predict: out of memory\n");
-        exit(1);
-    }
-    return p;
-}
 
 void run_predict_alloc(run_predict *r) {
     const size_t nx = r->n_x;
@@ -49,13 +45,6 @@ void run_predict_free(run_predict *r) {
     free(r->hist);
     free(r->best_params);
     memset(r, 0, sizeof *r);
-}
-
-static void read_or_die(void *p, size_t size, size_t count, FILE *f, const char *path) {
-    if (count > 0 && fread(p, size, count, f) != count) {
-        fprintf(stderr, "%s: truncated predict file\n", path);
-        exit(1);
-    }
 }
 
 int run_predict_read(const char *path, run_predict *r) {
@@ -105,25 +94,8 @@ int run_predict_read(const char *path, run_predict *r) {
     return 0;
 }
 
-static FILE *open_or_die(const char *path, const char *mode) {
-    FILE *f = fopen(path, mode);
-    if (f == NULL) {
-        fprintf(stderr, "opening file %s failed\n", path);
-        perror("opening file failed");
-        exit(1);
-    }
-    return f;
-}
-
-static void close_or_die(FILE *f, const char *path) {
-    if (fclose(f) != 0) {
-        fprintf(stderr, "writing %s failed\n", path);
-        exit(1);
-    }
-}
-
 void run_predict_write(const char *path, const run_predict *r) {
-    FILE *f = open_or_die(path, "wb");
+    FILE *f = run_open_or_die(path, "wb");
     const size_t nx = r->n_x;
     uint32_t u32[8];
     uint64_t u64[2];
@@ -155,7 +127,7 @@ void run_predict_write(const char *path, const run_predict *r) {
     fwrite(&r->best_prob, sizeof(double), 1, f);
     fwrite(r->best_params, sizeof(double), r->n_par, f);
     fwrite(&r->best_n, sizeof(uint64_t), 1, f);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }
 
 /* the run summary's edges: GSL's uniform ranges, the top one widened */
@@ -201,15 +173,8 @@ double run_predict_quantile(const run_predict *r, const double *edges, uint32_t 
 }
 
 /* "%.15e", a NaN of either sign as nan */
-static void print_value(FILE *f, double v) {
-    if (v != v)
-        fprintf(f, "nan");
-    else
-        fprintf(f, "%.15e", v);
-}
-
 void run_predict_write_text(const char *path, const run_predict *r, const double *y, const double *best) {
-    FILE *f = open_or_die(path, "w");
+    FILE *f = run_open_or_die(path, "w");
     double *edges = (double *)alloc_or_die((size_t)r->nbins + 1, sizeof(double));
     const double n = (double)r->n;
     const int ratio = r->model == 1 || r->model == 2; /* APEMOST_MODEL_PULSE, APEMOST_MODEL_PULSE_VROT */
@@ -225,31 +190,31 @@ void run_predict_write_text(const char *path, const run_predict *r, const double
         var = t / n;
         if (var < 0)
             var = 0.0;
-        print_value(f, r->x[i]);
+        run_print_value(f, r->x[i]);
         fprintf(f, "\t");
-        print_value(f, y[i]);
+        run_print_value(f, y[i]);
         fprintf(f, "\t");
-        print_value(f, mean);
+        run_print_value(f, mean);
         fprintf(f, "\t");
-        print_value(f, sqrt(var));
+        run_print_value(f, sqrt(var));
         fprintf(f, "\t");
-        print_value(f, ratio ? y[i] / mean : y[i] - mean);
+        run_print_value(f, ratio ? y[i] / mean : y[i] - mean);
         fprintf(f, "\t");
-        print_value(f, r->vmin[i]);
+        run_print_value(f, r->vmin[i]);
         fprintf(f, "\t");
-        print_value(f, r->vmax[i]);
+        run_print_value(f, r->vmax[i]);
         fprintf(f, "\t");
-        print_value(f, best[i]);
+        run_print_value(f, best[i]);
         if (r->nbins > 0) {
             fprintf(f, "\t");
-            print_value(f, run_predict_quantile(r, edges, i, 0.5));
+            run_print_value(f, run_predict_quantile(r, edges, i, 0.5));
             fprintf(f, "\t");
-            print_value(f, run_predict_quantile(r, edges, i, (1 - 0.68) / 2));
+            run_print_value(f, run_predict_quantile(r, edges, i, (1 - 0.68) / 2));
             fprintf(f, "\t");
-            print_value(f, run_predict_quantile(r, edges, i, (1 + 0.68) / 2));
+            run_print_value(f, run_predict_quantile(r, edges, i, (1 + 0.68) / 2));
         }
         fprintf(f, "\n");
     }
     free(edges);
-    close_or_die(f, path);
+    run_close_or_die(f, path);
 }

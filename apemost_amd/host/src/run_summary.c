@@ -3,6 +3,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include "run_summary.h"
+#include "run_io.h"
+
+/* run_io.h with this file's word in the messages */
+#define alloc_or_die(count, size) run_alloc_or_die(count, size, "run summary")
+#define read_or_die(p, size, count, f, path) run_read_or_die(p, size, count, f, path, "run summary")
 
 #define RUN_SUMMARY_MAGIC "APEMOSTS"
 #define RUN_SUMMARY_VERSION 1
@@ -23,15 +28,6 @@ uint64_t run_summary_batches(uint64_t n, uint64_t bs) {
     return bs == 1 ? n : (n + 1) / bs;
 }
 
-static void *alloc_or_die(size_t count, size_t size) {
-    void *p = calloc(count > 0 ? count : 1, size);
-    if (p == NULL) {
-        fprintf(stderr, "run summary: out of memory\n");
-        exit(1);
-    }
-    return p;
-}
-
 void run_summary_alloc(run_summary *r) {
     const size_t n_hp = (size_t)r->n_hist * r->n_par;
     r->lo = (double *)alloc_or_die(r->n_par, sizeof(double));
@@ -49,13 +45,6 @@ void run_summary_free(run_summary *r) {
     free(r->batch_sums);
     r->lo = r->hi = r->prob_sum = r->batch_sums = NULL;
     r->hist = NULL;
-}
-
-static void read_or_die(void *p, size_t size, size_t count, FILE *f, const char *path) {
-    if (count > 0 && fread(p, size, count, f) != count) {
-        fprintf(stderr, "%s: truncated run summary\n", path);
-        exit(1);
-    }
 }
 
 int run_summary_read(const char *path, run_summary *r) {
@@ -129,8 +118,5 @@ void run_summary_write(const char *path, const run_summary *r) {
     fwrite(r->prob_sum, sizeof(double), r->n_beta, f);
     fwrite(r->hist, sizeof(uint64_t), n_hp * r->nbins, f);
     fwrite(r->batch_sums, sizeof(double), n_hp * (r->max_batches + 1), f);
-    if (fclose(f) != 0) {
-        fprintf(stderr, "writing %s failed\n", path);
-        exit(1);
-    }
+    run_close_or_die(f, path);
 }
