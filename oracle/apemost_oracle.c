@@ -219,12 +219,41 @@ double orc_mod_double(double x, double y) {
  * Likelihoods (user plugins of the reference)
  * ========================================================================= */
 
+/* the engine's range guard of the sine models (apemost_oracle.h) */
+static int sine_guard_on = 0;
+static uint64_t sine_guard_hits = 0;
+void orc_set_sine_guard(int on) {
+    sine_guard_on = on;
+    sine_guard_hits = 0;
+}
+uint64_t orc_sine_guard_count(void) { return sine_guard_hits; }
+
+/* 1: every sine of the model (n_sines triples a, f, phi from p) has its argument in range over the data */
+static int sines_in_range(const double *p, int n_sines, const double *data, int n, int nc) {
+    double x_abs_max = 0;
+    int i, k, ok = 1;
+    for (i = 0; i < n; i++) {
+        double ax = fabs(data[(size_t)i * nc]);
+        if (!(ax <= x_abs_max)) /* also NaN */
+            x_abs_max = isfinite(ax) ? ax : INFINITY;
+    }
+    for (k = 0; k < n_sines; k++)
+        ok = ok && 2.0 * M_PI * (fabs(p[3 * k + 1]) * x_abs_max + fabs(p[3 * k + 2])) < 35184372088832.0;
+    if (!ok) {
+#pragma omp atomic
+        sine_guard_hits++;
+    }
+    return ok;
+}
+
 /* apps/simplesin.c:12-38 ; gsl_sf_sin stands for sin() to ~1 ulp */
 static double ll_simplesin(const double *p, const double *data, int n, int nc, double beta,
                            double sigma) {
     double amplitude = p[0], frequency = p[1], phase = p[2], offset = p[3];
     double square_sum = 0;
     int i;
+    if (sine_guard_on && !sines_in_range(p, 1, data, n, nc))
+        return NAN;
     for (i = 0; i < n; i++) {
         double x = data[(size_t)i * nc + 0];
         double y = data[(size_t)i * nc + 1];
@@ -241,6 +270,8 @@ static double ll_sine3(const double *p, const double *data, int n, int nc, doubl
                        double sigma) {
     double square_sum = 0;
     int i, k;
+    if (sine_guard_on && !sines_in_range(p, 3, data, n, nc))
+        return NAN;
     for (i = 0; i < n; i++) {
         double x = data[(size_t)i * nc + 0];
         double y = data[(size_t)i * nc + 1];

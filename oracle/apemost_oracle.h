@@ -167,6 +167,13 @@ double orc_accept_log_uniform(uint64_t seed, uint64_t chain_global, int n_par, u
 double orc_loglike(int model, int n_par, const double *params, const double *data,
                    int n_data, int n_cols, double beta, double sigma, double hmin,
                    double *prior_out);
+/* The engine's range guard of the sine models, opt-in (off by default: the reference has none, and every pinned
+ * trajectory is one without it).  On: ll_simplesin / ll_sine3 return NaN where
+ * !(2 pi (|f| max|x| + |phi|) < 2^45) for a sine of the model, max|x| over column 0 of the data (inf if an entry is
+ * not finite) -- the predicate of Model::load (apemost_amd/csrc/pt_device.h), operation by operation -- and such
+ * evaluations are counted.  Process-wide, like orc_set_progress_path. */
+void orc_set_sine_guard(int on);
+uint64_t orc_sine_guard_count(void);   /* out-of-range evaluations since the guard was last set */
 void orc_calc_model(orc_state *s, int chain);
 
 int orc_check_accept(double prob_old, double prob_new, orc_rng *r, const orc_state *s,

@@ -142,6 +142,10 @@ def lib():
         L.orc_calibrate_rest.argtypes = [C.POINTER(_State), C.POINTER(_Rng), C.POINTER(CalibCfg),
                                          C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp]
         L.orc_calibrate_rest.restype = C.c_int
+        L.orc_set_sine_guard.argtypes = [C.c_int]
+        L.orc_set_sine_guard.restype = None
+        L.orc_sine_guard_count.argtypes = []
+        L.orc_sine_guard_count.restype = C.c_uint64
         L.orc_mod_double.argtypes = [C.c_double, C.c_double]
         L.orc_mod_double.restype = C.c_double
         _lib = L
@@ -296,6 +300,23 @@ def loglike(model, params, data, beta=1.0, sigma=0.5, hmin=1e-6):
     prob = lib().orc_loglike(model, len(params), params.ctypes.data_as(_dp), data.ctypes.data_as(_dp),
                              data.shape[0], data.shape[1], beta, sigma, hmin, C.byref(prior))
     return prob, prior.value
+
+
+class sine_guard:
+    """with sine_guard() as g: the sine likelihoods return NaN where the engine's range guard does
+    (apemost_oracle.h, orc_set_sine_guard) and g.count() is how many evaluations did; off again on leaving.
+    Off by default: the reference has no guard."""
+
+    def __enter__(self):
+        lib().orc_set_sine_guard(1)
+        return self
+
+    def __exit__(self, *exc):
+        self.final = self.count()
+        lib().orc_set_sine_guard(0)
+
+    def count(self):
+        return int(lib().orc_sine_guard_count())
 
 
 def run_sampler(ladder, rng, n_rounds, n_swap, record=False, n_threads=1):

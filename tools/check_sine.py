@@ -5,9 +5,11 @@ rounds them (every FMA rounds once).  Reports the absolute error (what a likelih
 a sin() to numbers of order one) and the relative error in ulp, for the kernel's two-term
 reduction and for a three-term one (which keeps the relative error near the zeros of the sine at
 the price of one more FMA per sine), and compares the two evaluation orders of the polynomial:
-Horner (shortest instruction count) and Estrin (shortest dependent chain).
+Horner (shortest instruction count) and Estrin (shortest dependent chain).  Both forms of the multiple of pi are
+reported: n = rint(x / pi), and the one that ships, n = rint(2 u) from the phase in turns (fm = fma(u, 2, magic)).
 
     python tools/check_sine.py [samples]"""
+import math
 import random
 import sys
 
@@ -26,8 +28,9 @@ def fma(a, b, c):
     return float(mp.mpf(a) * mp.mpf(b) + mp.mpf(c))
 
 
-def reduce_(x, terms=2):
-    fm = fma(x, INV_PI, MAGIC)
+def reduce_(x, terms=2, u=None):
+    """u: the phase in turns, x = fl(2 pi u): the form that ships (APEMOST_SIN_FOLD_N), n = rint(2 u)"""
+    fm = fma(x, INV_PI, MAGIC) if u is None else fma(u, 2.0, MAGIC)
     fn = fm - MAGIC
     r = fma(fn, NPI_HI, x)
     r = fma(fn, NPI_MID, r)
@@ -36,8 +39,8 @@ def reduce_(x, terms=2):
     return r, int(fn) & 1
 
 
-def horner(x, terms=2):
-    r, odd = reduce_(x, terms)
+def horner(x, terms=2, u=None):
+    r, odd = reduce_(x, terms, u)
     z = r * r
     q = fma(z, S[7], S[6])
     for k in (5, 4, 3, 2, 1, 0):
@@ -92,7 +95,28 @@ def main():
         worst["ulp3"] = max(worst["ulp3"], ulp_err(h3, x))
         worst["estrin_abs2"] = max(worst["estrin_abs2"], float(abs(mp.mpf(estrin(x, 2)) - ref)))
         worst["estrin_ulp3"] = max(worst["estrin_ulp3"], ulp_err(estrin(x, 3), x))
+    # the form that ships: n = rint(2 u) from the phase in turns, x = fl(2 pi u).  The two forms differ where 2 u is
+    # within an ulp of a half integer: there r leaves [-pi/2, pi/2] (tests/sine_domain.py holds the list and the bound)
+    two_pi = 2.0 * 3.14159265358979323846264338328
+    shipped = {"abs": 0.0, "abs_half": 0.0, "r_over": 0.0}
+    for i in range(n):
+        if i % 2:
+            u = rnd.choice((-1, 1)) * 10 ** rnd.uniform(0, 12.7)
+            key = "abs"
+        else:
+            k = rnd.randrange(1, 2 ** rnd.randrange(1, 44))
+            u = rnd.choice((-1, 1)) * (k + 0.5) / 2
+            for _ in range(rnd.randrange(3)):
+                u = math.nextafter(u, rnd.choice((-math.inf, math.inf)))
+            key = "abs_half"
+        x = float(mp.mpf(two_pi) * mp.mpf(u))
+        if abs(x) >= 2.0 ** 45:
+            continue
+        shipped[key] = max(shipped[key], float(abs(mp.mpf(horner(x, 2, u)) - mp.sin(mp.mpf(x)))))
+        shipped["r_over"] = max(shipped["r_over"], abs(reduce_(x, 2, u)[0]) - math.pi / 2)
     print("max error over %d samples, |x| < 3e13" % n)
+    print("  as shipped (n = rint(2 u) from the phase, |x| < 2^45): absolute %.3g at random phases, %.3g with 2 u within"
+          " two ulps of a half integer (|r| - pi/2 up to %.3g)" % (shipped["abs"], shipped["abs_half"], shipped["r_over"]))
     print("  kernel (two-term reduction, Horner): absolute %.3g; relative %.3g ulp where |sin| > 1e-6, %.3g ulp anywhere"
           % (worst["abs2"], worst["ulp2_away"], worst["ulp2"]))
     print("  three-term reduction, Horner: %.3g ulp anywhere" % worst["ulp3"])
