@@ -124,7 +124,19 @@ class PointwiseTailView(C.Structure):
     _fields_ = [("count", _up), ("values", _dp)]
 
 
-PEAKS_MAX = 99   # peaks described per column (include/apemost_hip.h)
+class DerivedConfig(C.Structure):
+    _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("n_col", C.c_int32),
+                ("code", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("n_const", C.c_int32), ("consts", _dp),
+                ("nbins", C.c_int32), ("n_pairs", C.c_int32), ("pairs", C.POINTER(C.c_int32)), ("lo", _dp), ("hi", _dp),
+                ("batch_size", C.c_uint64), ("max_batches", C.c_uint64), ("stage_steps", C.c_uint64)]
+
+
+class DerivedView(C.Structure):
+    _fields_ = [("n", _up), ("hist", _up), ("batch", _dp), ("n_batches", _up), ("counts", _up), ("origin", _dp),
+                ("sum", _dp), ("cross", _dp), ("nonfinite", _up), ("vmin", _dp), ("vmax", _dp)]
+
+
+PEAKS_MAX = 99  # peaks described per column (include/apemost_hip.h)
 
 
 class ReplicaFlowView(C.Structure):
@@ -170,6 +182,8 @@ EXPORTS = [
     "apemost_hip_pointwise_loglike_ladder",
     "apemost_hip_pointwise_tail_begin", "apemost_hip_pointwise_tail_get", "apemost_hip_pointwise_tail_set",
     "apemost_hip_pointwise_tail_capacity",
+    "apemost_hip_derived_check", "apemost_hip_derived_begin", "apemost_hip_derived_accumulate",
+    "apemost_hip_derived_get", "apemost_hip_derived_set", "apemost_hip_derived_end", "apemost_hip_derived_eval",
 ]
 
 _lib = None
@@ -314,6 +328,14 @@ def lib():
     L.apemost_hip_pointwise_tail_get.argtypes = [vp, C.POINTER(PointwiseTailView)]
     L.apemost_hip_pointwise_tail_set.argtypes = [vp, C.POINTER(PointwiseTailView)]
     L.apemost_hip_pointwise_tail_capacity.argtypes = [vp, C.POINTER(C.c_int32)]
+    ip = C.POINTER(C.c_int32)
+    L.apemost_hip_derived_check.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int32, ip]
+    L.apemost_hip_derived_begin.argtypes = [vp, C.POINTER(DerivedConfig)]
+    L.apemost_hip_derived_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_derived_get.argtypes = [vp, C.POINTER(DerivedView)]
+    L.apemost_hip_derived_set.argtypes = [vp, C.POINTER(DerivedView)]
+    L.apemost_hip_derived_end.argtypes = [vp]
+    L.apemost_hip_derived_eval.argtypes = [vp, C.c_uint64, _dp, _dp]
     L.apemost_hip_timer_begin.argtypes = [vp]
     L.apemost_hip_timer_end.argtypes = [vp, C.POINTER(C.c_float), _up]
     _lib = L

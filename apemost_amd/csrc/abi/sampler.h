@@ -38,7 +38,7 @@ namespace { // (internal linkage, like the unnamed structs of the sampler: no sy
 
 // the device memory a fold owns: filled by fold_alloc (abi/fold_common.h), released as a whole.  Plain data, so
 // that a fold's struct is reset by `= {}` like everything else in the sampler.
-constexpr int kFoldMaxOwned = 16;
+constexpr int kFoldMaxOwned = 24;
 struct FoldMem {
     void *owned[kFoldMaxOwned];
     int n_owned;
@@ -94,6 +94,21 @@ struct JointFold {
     double *d_lo, *d_hi, *d_vals, *d_origin, *d_sum, *d_cross;
     unsigned short *d_bins;
     u64 *d_counts;
+    FoldMem mem;
+};
+
+// on-device derived quantities (pt_derived.h): the summary's histograms and batch sums and the joint fold's pair
+// counts and moments of computed columns
+struct DerivedFold {
+    bool open;
+    int n_keep, n_col, nbins, n_pairs, n_const;
+    u64 bs, max_batches;
+    u64 chunk; // kept steps staged per launch
+    u64 n;
+    int *d_chains, *d_pairs, *d_code, *d_start;
+    double *d_consts, *d_lo, *d_hi, *d_vals, *d_origin, *d_sum, *d_cross, *d_batch, *d_vmin, *d_vmax;
+    unsigned short *d_bins;
+    u64 *d_counts, *d_hist, *d_nonfinite;
     FoldMem mem;
 };
 
@@ -254,6 +269,7 @@ struct apemost_hip_sampler {
     AutocorrFold ac;
     PredictFold pr;
     PointwiseFold pw;
+    DerivedFold dv;
 };
 
 // everything a sampler owns on the device; safe on a half-built sampler
@@ -291,6 +307,7 @@ static void release(apemost_hip_sampler *s) {
     fold_free(s->ac);
     fold_free(s->pr);
     fold_free(s->pw);
+    fold_free(s->dv);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {

@@ -16,6 +16,7 @@
 #include "run_predict.h"
 #include "run_pointwise.h"
 #include "run_evidence.h"
+#include "run_derived.h"
 #include "run_joint.h"
 #include "run_peaks.h"
 #include "run_summary.h"
@@ -216,6 +217,12 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            box, on the bins of the marginal histograms, and into the moments of the parameter covariance; at the end
  *            write joint.bin, one <a>-<b>.joint per pair and correlation.matrix (run_joint.h).  Combines with every
  *            other token and writes no sample file by itself, like peaks
+ *   derived  fold functions of chain 0's rows on the device -- the columns of the file `derived` (or of the file
+ *            APEMOST_DERIVED_FILE names), one per line as `name lo hi` and a program in reverse Polish notation over the
+ *            names of the params file, prob and like -- into histograms, batch sums, pair histograms and moments; at the
+ *            end write derived.bin, derived.txt and one <name>.histogram per column (run_derived.h): what the
+ *            reference's matrix_man and histogram_tool give from the text dumps.  Needs a bounded run.  Combines with
+ *            every other token and writes no sample file by itself, like joint
  *   evidence fold column prob - prior of EVERY chain on the device into its moments, batch sums and the log-sum-exps of
  *            the stepping-stone estimator; at the end write evidence.bin and evidence.txt: thermodynamic integration by
  *            the rectangle, trapezoid and variance-corrected trapezoid rules, the stepping stone in both directions and
@@ -257,6 +264,7 @@ typedef struct {
     int binary;               /* 0 text, 1 binary, 2 binary with every chain's parameters */
     int summary;              /* summary.bin from the device (APEMOST_DUMP token `summary`) */
     int peaks;                /* <paramname>.peaks from the device (APEMOST_DUMP token `peaks`) */
+    int derived;              /* derived.bin, derived.txt and the columns' histograms from the device (token `derived`) */
     int joint;                /* joint.bin and the pair files from the device (APEMOST_DUMP token `joint`) */
     int evidence;             /* evidence.bin and evidence.txt from the device (APEMOST_DUMP token `evidence`) */
     int autocorr;             /* autocorr.bin and autocorr.txt from the device (APEMOST_DUMP token `autocorr`) */
@@ -283,6 +291,7 @@ static void sink_parse(sample_sink *k) {
     k->summary = 0;
     k->peaks = 0;
     k->joint = 0;
+    k->derived = 0;
     k->evidence = 0;
     k->autocorr = 0;
     k->predict = 0;
@@ -302,6 +311,8 @@ static void sink_parse(sample_sink *k) {
             k->peaks = 1;
         else if (strncmp(spec, "joint", 5) == 0 && (spec[5] == 0 || spec[5] == ','))
             k->joint = 1;
+        else if (strncmp(spec, "derived", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
+            k->derived = 1;
         else if (strncmp(spec, "evidence", 8) == 0 && (spec[8] == 0 || spec[8] == ','))
             k->evidence = 1;
         else if (strncmp(spec, "autocorr", 8) == 0 && (spec[8] == 0 || spec[8] == ','))
@@ -311,14 +322,15 @@ static void sink_parse(sample_sink *k) {
         else if (strncmp(spec, "pointwise", 9) == 0 && (spec[9] == 0 || spec[9] == ','))
             k->pointwise = 1;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived; got '%s'\n", spec);
             exit(1);
         }
         spec = strchr(spec, ',');
         if (spec != NULL)
             spec++;
     }
-    k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr || k->predict || k->pointwise) ||
+    k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr || k->predict || k->pointwise ||
+                 k->derived) ||
                format_given;
     if (k->pointwise) /* a malformed APEMOST_POINTWISE_TAIL ends the program here, before any file is opened */
         (void)run_pointwise_tail_from_env();
@@ -636,6 +648,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     int k = 0, device_pack, rows_on_host, text_sink;
     run_summary summary;
     run_joint joint;
+    run_derived derived;
     run_evidence evidence;
     run_autocorr autocorr;
     run_predict predict;
@@ -707,6 +720,11 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
                        mode[0] == 'a');
     if (sink.joint) /* chain 0 lives on shard 0 */
         run_joint_open(&joint, apemost_ladder_shard(l, 0), chains[0], NBINS, sink.thin, mode[0] == 'a');
+    if (sink.derived) /* chain 0 lives on shard 0; a bad line of the derived file ends the program here */
+        run_derived_open(&derived, apemost_ladder_shard(l, 0), chains[0], NBINS,
+                         planned_samples("derived", "the batch size of the error estimate is fixed before the first sample",
+                                         n_swap, iter, max_iterations, sink.thin),
+                         sink.thin, mode[0] == 'a');
     if (sink.evidence) /* every chain: one fold per shard */
         run_evidence_open(&evidence, l, chains, lo, n_shards,
                           planned_samples("evidence", "the batch size of the error estimate is fixed before the first sample",
@@ -785,6 +803,10 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             apemost_hip_or_die(apemost_hip_joint_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
                                                             (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
                                "joint_accumulate");
+        if (sink.derived) /* functions of chain 0's rows, on the same stream */
+            apemost_hip_or_die(apemost_hip_derived_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
+                                                              (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
+                               "derived_accumulate");
         for (j = 0; j < n_shards && sink.evidence; j++) /* every chain's prob - prior column, on the same stream */
             apemost_hip_or_die(apemost_hip_evidence_accumulate(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
                                                                (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
@@ -864,6 +886,8 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         run_peaks_close(apemost_ladder_shard(l, 0), chains[0]);
     if (sink.joint)
         run_joint_close(&joint, apemost_ladder_shard(l, 0), chains[0]);
+    if (sink.derived)
+        run_derived_close(&derived, apemost_ladder_shard(l, 0));
     if (sink.evidence)
         run_evidence_close(&evidence, l, lo, n_shards);
     if (sink.autocorr)

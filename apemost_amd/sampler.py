@@ -479,6 +479,75 @@ class HipSampler:
     def joint_end(self):
         capi.check(self.L.apemost_hip_joint_end(self._h))
 
+    # -- on-device derived quantities (apemost_amd/derived.py) --------------------------------------
+    def derived_begin(self, columns, lo, hi, chains=(0,), nbins=200, pairs=None, batch_size=1, max_batches=0, names=None,
+                      stage_steps=0, thin=1):
+        """start the fold of computed columns for the local chains `chains`: histograms over [lo[c], hi[c]] on the
+        summary's bins, batch sums, the joint fold's pair counts and moments over the columns, non-finite counts, min
+        and max.  columns: each a derived.Program, an infix expression (derived.compile) or a (name, either) pair;
+        names: the parameters' names in expressions (default p0, p1, ...).  stage_steps: kept steps per staged piece,
+        0 for the joint fold's choice.  `thin` is only recorded with the result."""
+        from . import derived as dv
+        row_names = ["p%d" % i for i in range(self.n_par)] if names is None else list(names)
+        assert len(row_names) == self.n_par
+        col_names, programs = [], []
+        for c, col in enumerate(columns):
+            name, col = col if isinstance(col, tuple) else ("d%d" % c, col)
+            col_names.append(name)
+            programs.append(col if isinstance(col, dv.Program) else dv.compile(col, row_names))
+        code, start, consts = dv.pack(programs)
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        chains = np.ascontiguousarray(chains, dtype=np.int32)
+        assert lo.shape == hi.shape == (len(programs),) and chains.ndim == 1
+        use_pairs = np.ascontiguousarray(dv.all_pairs(len(programs)) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        given = np.zeros((max(len(use_pairs), 1), 2), dtype=np.int32)    # (never a NULL pointer for an empty list)
+        given[:len(use_pairs)] = use_pairs
+        code_arg = code if len(code) else np.zeros(1, dtype=np.int32)
+        consts_arg = consts if len(consts) else np.zeros(1)
+        cfg = capi.DerivedConfig(n_keep=len(chains), chains=chains.ctypes.data_as(ip), n_col=len(programs),
+                                 code=code_arg.ctypes.data_as(ip), start=start.ctypes.data_as(ip), n_const=len(consts),
+                                 consts=consts_arg.ctypes.data_as(dp), nbins=nbins, n_pairs=len(use_pairs),
+                                 pairs=None if pairs is None else given.ctypes.data_as(ip), lo=lo.ctypes.data_as(dp),
+                                 hi=hi.ctypes.data_as(dp), batch_size=batch_size, max_batches=max_batches,
+                                 stage_steps=stage_steps)
+        capi.check(self.L.apemost_hip_derived_begin(self._h, C.byref(cfg)))
+        self._dv_cfg = dict(programs=programs, lo=lo, hi=hi, chains=chains, nbins=int(nbins), pairs=use_pairs,
+                            batch_size=int(batch_size), max_batches=int(max_batches), names=col_names,
+                            row_names=row_names, thin=thin)
+
+    def derived_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]; asynchronous
+        (derived() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_derived_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def derived(self):
+        """the fold so far as a Derived object (synchronises with the accumulates issued so far)"""
+        from .derived import Derived
+        dv = Derived.empty(**self._dv_cfg)
+        capi.check(self.L.apemost_hip_derived_get(self._h, C.byref(dv.view())))
+        return dv
+
+    def derived_set(self, dv):
+        """load a Derived (a resumed run) into the fold begun with the same configuration"""
+        c = self._dv_cfg
+        assert dv.hist.shape == (len(c["chains"]), len(c["programs"]), c["nbins"]) and np.array_equal(dv.pairs, c["pairs"])
+        assert dv.batch.shape[2] == c["max_batches"] + 1 and dv.batch_size == c["batch_size"]
+        dv.n_batches_[0] = dv.n_batches
+        capi.check(self.L.apemost_hip_derived_set(self._h, C.byref(dv.view())))
+
+    def derived_end(self):
+        capi.check(self.L.apemost_hip_derived_end(self._h))
+
+    def derived_eval(self, rows):
+        """[n][n_col]: the open fold's programs on the host rows [n][n_par+2], by the device function the fold uses"""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        assert rows.ndim == 2 and rows.shape[1] == self.n_par + 2
+        out = np.zeros((len(rows), len(self._dv_cfg["programs"])))
+        dp = C.POINTER(C.c_double)
+        capi.check(self.L.apemost_hip_derived_eval(self._h, len(rows), rows.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+        return out
+
     # -- on-device evidence fold (apemost_amd/evidence.py) ------------------------------------------
     def evidence_begin(self, betas=None, batch_size=1, max_batches=0, coef_up=None, coef_down=None, thin=1):
         """start the fold of column n_par+1 of every local chain: moments about the first sample, batch sums and the

@@ -1026,6 +1026,114 @@ int apemost_hip_pointwise_tail_set(apemost_hip_sampler *s, const apemost_hip_poi
 /* *capacity = the capacity of the open fold's tail, 0 where there is none */
 int apemost_hip_pointwise_tail_capacity(apemost_hip_sampler *s, int32_t *capacity);
 
+/* ---- on-device derived quantities: column programs folded without dumps ------------------------
+ * What the reference's tools/matrix_man.c computes over the text dumps (add, mul, addc, mulc, invm, inva, ... piped
+ * into histogram_tool) from rows that stay on the device: the posterior of functions of the parameters -- a splitting
+ * f2 - f1, a ratio h2 / h1, A cos 2 pi phi, (prob - prior) / beta.
+ *
+ * A derived column is a small stack program over one sample row x[0 .. n_par+1], x[n_par] being prob and
+ * x[n_par+1] prob - prior.  One int32 per instruction: the low 8 bits are the opcode, the high 24 bits the operand.
+ * The programs of all columns are concatenated in code[]; column c is code[start[c] .. start[c+1]); constants are in
+ * consts[].  "top" is the last value pushed, "second" the one below it:
+ *   COL c      push x[c], 0 <= c <= n_par+1                  CONST k    push consts[k], 0 <= k < n_const
+ *   DUP        push top                                       SWAP       top and second change places
+ *   exact group -- every result is the correctly rounded IEEE fp64 operation, contraction off, so a program of this
+ *   group alone gives the bits numpy gives:
+ *   ADD SUB MUL DIV   second (op) top replaces both           NEG ABS    -top, |top| (the sign bit alone changes)
+ *   INV        1.0 / top                                      SQRT FLOOR sqrt(top), floor(top)
+ *   MIN        second < top ? second : top                    MAX        second > top ? second : top
+ *              (literally: with a NaN among the two, or two zeros, the comparison is false and top stays)
+ *   library group -- the device library's plain double-precision functions, not promised bit-equal to any host's:
+ *   LOG EXP SIN COS   of top                                  ATAN2      atan2(second, top) replaces both
+ * Limits: 1 .. 64 columns, 1 .. 256 instructions per column, at most 256 constants, stack depth at most 16; a program
+ * leaves exactly one value. */
+enum {
+    APEMOST_DERIVED_COL = 0, APEMOST_DERIVED_CONST = 1, APEMOST_DERIVED_DUP = 2, APEMOST_DERIVED_SWAP = 3,
+    APEMOST_DERIVED_ADD = 4, APEMOST_DERIVED_SUB = 5, APEMOST_DERIVED_MUL = 6, APEMOST_DERIVED_DIV = 7,
+    APEMOST_DERIVED_NEG = 8, APEMOST_DERIVED_ABS = 9, APEMOST_DERIVED_INV = 10, APEMOST_DERIVED_SQRT = 11,
+    APEMOST_DERIVED_FLOOR = 12, APEMOST_DERIVED_MIN = 13, APEMOST_DERIVED_MAX = 14,
+    APEMOST_DERIVED_LOG = 15, APEMOST_DERIVED_EXP = 16, APEMOST_DERIVED_SIN = 17, APEMOST_DERIVED_COS = 18,
+    APEMOST_DERIVED_ATAN2 = 19, APEMOST_DERIVED_N_OPCODES = 20
+};
+#define APEMOST_DERIVED_MAX_COLUMNS 64
+#define APEMOST_DERIVED_MAX_CODE 256     /* instructions per column */
+#define APEMOST_DERIVED_MAX_CONSTS 256
+#define APEMOST_DERIVED_MAX_DEPTH 16
+/* Host arithmetic only, no device and no sampler: verifies the n_col programs code[start[c] .. start[c+1]) over rows of
+ * n_par + 2 values and n_const constants by abstract execution, and writes the stack depth each program reaches to
+ * depth_out[n_col] (NULL: not wanted).  APEMOST_HIP_ERR_INVALID, the message naming column and instruction, for
+ * n_col outside 1 .. 64, an empty program or one of more than 256 instructions, an unknown opcode, a COL operand
+ * above n_par + 1, a CONST operand >= n_const, n_const outside 0 .. 256, a pop from too short a stack, a depth above
+ * 16, or a final depth other than 1. */
+int apemost_hip_derived_check(int32_t n_par, int32_t n_col, const int32_t *code, const int32_t *start, int32_t n_const,
+                              int32_t *depth_out);
+
+/* The fold.  Accumulated from the sample rows while they are still on the device, per kept chain k and column c, with
+ * v the value the column's program gives for a kept row and n the kept samples so far:
+ *   hist[k][c][nbins]      counts of v in the run summary's bins over [lo[c], hi[c]] (the edges and the bisection of
+ *                          the summary and the joint fold: one device function for all three);
+ *   batch[k][c][max_batches + 1]  the batch sums of batch_means_error() with the summary's rule: batch 0 holds
+ *                          batch_size - 1 samples, every later one batch_size; slot n_batches is the open batch;
+ *   counts[k][q][a][b], origin[k][c], sum[k][c], cross[k][c (c + 1) / 2]  exactly what the joint fold defines, with
+ *                          "parameter" read as "column": the joint fold's own kernels run on the staged columns;
+ *   nonfinite[k][c]        the count of values that are not finite;
+ *   vmin[k][c], vmax[k][c] the least and the greatest v that is not a NaN, +inf and -inf before there is one; of the
+ *                          two zeros -0.0 is the lesser (a derived quantity has no prior box: a pilot run reads these
+ *                          to choose lo and hi).
+ * Nothing is filtered from the sums: a non-finite v makes its column's sums non-finite, as in the joint and summary
+ * folds, and nonfinite says why.  Every count is exact and every sum one thread's chain of additions in sample order:
+ * the fold equals a sequential host loop over the values apemost_hip_derived_eval returns for the kept rows, bit for
+ * bit, whatever the calls, the thinning and the staged pieces are.
+ * Sharded ladders and ladder batches: `chains` as for the joint fold. */
+typedef struct {
+    int32_t n_keep;          /* number of kept chains, 1 .. n_chains; n_keep * n_col <= 65535 */
+    const int32_t *chains;   /* host [n_keep]: local chain indices, strictly increasing */
+    int32_t n_col;           /* columns, 1 .. 64 */
+    const int32_t *code;     /* host [start[n_col]] */
+    const int32_t *start;    /* host [n_col + 1], start[0] = 0 */
+    int32_t n_const;         /* 0 .. 256 */
+    const double *consts;    /* host [n_const] (may be NULL with n_const = 0) */
+    int32_t nbins;           /* 1 .. 512 */
+    int32_t n_pairs;         /* pairs of columns, with the joint fold's rules (ignored with pairs == NULL: all i < j) */
+    const int32_t *pairs;    /* host [n_pairs][2] */
+    const double *lo, *hi;   /* host [n_col]: the histogram range of every column, finite, lo < hi, hi - lo finite */
+    uint64_t batch_size;     /* >= 1 */
+    uint64_t max_batches;    /* batches there is room for; an accumulate that would close more is refused */
+    uint64_t stage_steps;    /* kept steps per staged piece, 1 .. 2^18; 0: about 4 Mi values over all columns, as the
+                                joint fold stages */
+} apemost_hip_derived_config;
+typedef struct {
+    uint64_t *n;             /* kept samples */
+    uint64_t *hist;          /* [n_keep][n_col][nbins] */
+    double *batch;           /* [n_keep][n_col][max_batches + 1] */
+    uint64_t *n_batches;     /* batches closed (get writes it; set checks it against n where both are given) */
+    uint64_t *counts;        /* [n_keep][n_pairs][nbins][nbins] */
+    double *origin, *sum;    /* [n_keep][n_col] */
+    double *cross;           /* [n_keep][n_col (n_col + 1) / 2], upper triangle row-major */
+    uint64_t *nonfinite;     /* [n_keep][n_col] */
+    double *vmin, *vmax;     /* [n_keep][n_col] */
+} apemost_hip_derived_view;  /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* checks the programs with apemost_hip_derived_check and everything else before any device work, then allocates and
+ * zeroes the accumulator and the scratch of one staged piece (10 bytes per value).  A fold begun before is dropped once
+ * the new configuration has been accepted; a begin that is refused leaves it open and accumulating as it was. */
+int apemost_hip_derived_begin(apemost_hip_sampler *s, const apemost_hip_derived_config *cfg);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2]); asynchronous and
+ * queued like apemost_hip_joint_accumulate.  APEMOST_HIP_ERR_INVALID without derived_begin, with thin == 0, or where
+ * the call would close more than max_batches batches (nothing is accumulated then). */
+int apemost_hip_derived_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                   uint64_t thin);
+/* copies the accumulator out (synchronises with the accumulates issued so far) */
+int apemost_hip_derived_get(apemost_hip_sampler *s, const apemost_hip_derived_view *v);
+/* loads a view saved by derived_get into a fold begun with the same configuration (a resumed run), origin included */
+int apemost_hip_derived_set(apemost_hip_sampler *s, const apemost_hip_derived_view *v);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_derived_end(apemost_hip_sampler *s);
+/* the open fold's programs on the caller's n rows (HOST rows[n][n_par+2], out[n][n_col]; n * (n_par + 2) and n * n_col
+ * at most 2^26), by the device function the fold's gather kernel uses: how a program is checked, and what fixes the
+ * fold's meaning.  APEMOST_HIP_ERR_INVALID without derived_begin. */
+int apemost_hip_derived_eval(apemost_hip_sampler *s, uint64_t n, const double *rows, double *out);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
