@@ -166,6 +166,8 @@ EXPORTS = [
     "apemost_hip_samples_text_bound", "apemost_hip_samples_text_read_async", "apemost_hip_device_alloc",
     "apemost_hip_device_free",
     "apemost_hip_create_batch", "apemost_hip_n_ladders", "apemost_hip_set_data_ladder",
+    "apemost_hip_create_batch_ragged", "apemost_hip_ragged_layout", "apemost_hip_ladder_n_data",
+    "apemost_hip_predict_lengths", "apemost_hip_pointwise_lengths",
     "apemost_hip_replica_flow_get", "apemost_hip_replica_flow_set", "apemost_hip_replica_flow_reset",
     "apemost_hip_peaks_begin", "apemost_hip_peaks_accumulate", "apemost_hip_peaks_get", "apemost_hip_peaks_end",
     "apemost_hip_peaks_table",
@@ -220,6 +222,11 @@ def lib():
     L.apemost_hip_device_info.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), _up]
     L.apemost_hip_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
     L.apemost_hip_create_batch.argtypes = [C.POINTER(Config), C.c_int32, _up, C.POINTER(vp)]
+    L.apemost_hip_create_batch_ragged.argtypes = [C.POINTER(Config), C.c_int32, _up, C.POINTER(C.c_int32), C.POINTER(vp)]
+    L.apemost_hip_ragged_layout.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), _up, C.POINTER(C.c_int32), _up]
+    L.apemost_hip_ladder_n_data.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+    L.apemost_hip_predict_lengths.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.apemost_hip_pointwise_lengths.argtypes = [vp, C.POINTER(C.c_int32)]
     L.apemost_hip_n_ladders.argtypes = [vp, C.POINTER(C.c_int32)]
     L.apemost_hip_set_data_ladder.argtypes = [vp, C.c_int32, _dp]
     L.apemost_hip_destroy.argtypes = [vp]
@@ -366,6 +373,17 @@ def calib_defaults(**overrides):
     for k, v in overrides.items():
         setattr(c, k, v)
     return c
+
+
+def ragged_layout(n_data, n_cols):
+    """Where the ladders' data matrices of a ragged batch start, in doubles: (offsets [n_ladders + 1], the longest
+    length, the total).  Host arithmetic only (apemost_hip_ragged_layout): no device is touched."""
+    lens = np.ascontiguousarray(n_data, dtype=np.int32)
+    off = np.zeros(len(lens) + 1, dtype=np.uint64)
+    longest, total = C.c_int32(0), C.c_uint64(0)
+    check(lib().apemost_hip_ragged_layout(len(lens), n_cols, lens.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          off.ctypes.data_as(_up), C.byref(longest), C.byref(total)))
+    return off, longest.value, total.value
 
 
 def swap_pair(seed, round_, n_global):

@@ -31,8 +31,13 @@ extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost
     POINTWISE_HAS_TERM(s, "pointwise_begin");
     if (!cfg)
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: config is NULL");
-    const int np = s->cfg.n_par, nd = s->cfg.n_data;
+    const int np = s->cfg.n_par;
     FOLD_TRY(fold_check_chains(s, "pointwise", cfg->n_keep, cfg->chains));
+    // the longest data among the kept chains' ladders (a batch's ladders may differ in length: the arrays stay
+    // rectangular and every kept chain folds its own len[k] <= nd series)
+    std::vector<int> len;
+    bool ragged = false;
+    const int nd = kept_lengths(s, cfg->n_keep, cfg->chains, len, &ragged);
     const u64 n_series = (u64)cfg->n_keep * (u64)nd;
     if (n_series > ((u64)1 << 20))
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d chains x %d data: more than 2^20 series", cfg->n_keep,
@@ -42,6 +47,7 @@ extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost
     FOLD_TRY(fold_reset(s, s->pw));
     PointwiseFold &f = s->pw;
     f.n_keep = cfg->n_keep;
+    f.n_data = nd;
     f.c = pointwise_c(s);
     f.n = 0;
     const size_t ns = (size_t)n_series, nk = (size_t)cfg->n_keep;
@@ -54,14 +60,19 @@ extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost
     FOLD_TRY(fold_alloc(s, f.mem, &f.d_state, kPointwiseWords * ns, true));
     FOLD_TRY(fold_alloc(s, f.mem, &f.d_par, 2 * nk * np, true));
     HIP_TRY(hipMemcpyAsync(f.d_chains, cfg->chains, nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    if (ragged) {
+        FOLD_TRY(fold_alloc(s, f.mem, &f.d_len, nk, false));
+        HIP_TRY(hipMemcpyAsync(f.d_len, len.data(), nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    }
     for (int k = 0; k < cfg->n_keep; k++) {
-        // columns 0 and 1 of the kept chain's own ladder (the data is stored by columns, ladder after ladder)
-        const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
-        const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * nd;
-        HIP_TRY(hipMemcpyAsync(f.d_x + (size_t)k * nc * nd, col0, nc * nd * sizeof(double), hipMemcpyDeviceToDevice,
+        // columns 0 and 1 of the kept chain's own ladder (the data is stored by columns, ladder after ladder), in
+        // that ladder's own length (a user model, which no batch runs: len[k] = nd)
+        const double *col0 = ladder_data(s, s->batch ? cfg->chains[k] / s->per_ladder : 0);
+        const size_t mine = (size_t)len[k];
+        HIP_TRY(hipMemcpyAsync(f.d_x + (size_t)k * nc * nd, col0, nc * mine * sizeof(double), hipMemcpyDeviceToDevice,
                                s->stream));
         if (!user)
-            HIP_TRY(hipMemcpyAsync(f.d_y + (size_t)k * nd, col0 + nd, (size_t)nd * sizeof(double),
+            HIP_TRY(hipMemcpyAsync(f.d_y + (size_t)k * nd, col0 + mine, mine * sizeof(double),
                                    hipMemcpyDeviceToDevice, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's array is read until here)
@@ -77,8 +88,8 @@ static PointwiseTailArgs pointwise_tail_args(const apemost_hip_sampler *s, bool 
     t.thr = s->pw.tail.d_thr;
     t.capacity = s->pw.tail.capacity;
     t.B = s->pw.tail.B;
-    t.n_data = s->cfg.n_data;
-    t.n_blocks = (s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+    t.n_data = s->pw.n_data;
+    t.n_blocks = (s->pw.n_data + kPointwiseWave - 1) / kPointwiseWave;
     t.force = force ? 1 : 0;
     t.dense = nullptr;
     t.count = nullptr;
@@ -87,7 +98,7 @@ static PointwiseTailArgs pointwise_tail_args(const apemost_hip_sampler *s, bool 
 
 static int pointwise_tail_compact(apemost_hip_sampler *s, bool force) {
     const PointwiseTailArgs t = pointwise_tail_args(s, force);
-    const dim3 grid((unsigned)s->pw.n_keep * (unsigned)s->cfg.n_data), block(kTailThreads);
+    const dim3 grid((unsigned)s->pw.n_keep * (unsigned)s->pw.n_data), block(kTailThreads);
     hipLaunchKernelGGL(pointwise_tail_compact_kernel, grid, block, (size_t)t.B * sizeof(unsigned long long), s->copy_stream, t);
     HIP_TRY(hipGetLastError());
     return APEMOST_HIP_OK;
@@ -132,7 +143,7 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
     if (kept == 0)
         return APEMOST_HIP_OK;
     FOLD_TRY(fold_order_behind_stream(s));
-    const size_t ns = (size_t)f.n_keep * s->cfg.n_data;
+    const size_t ns = (size_t)f.n_keep * f.n_data;
     for (u64 k0 = 0; k0 < kept; k0 += kPointwisePiece) {
         PointwiseArgs a;
         a.rows = d_samples;
@@ -144,8 +155,9 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
         a.thin = thin;
         a.n = (unsigned int)(kept - k0 < (u64)kPointwisePiece ? kept - k0 : (u64)kPointwisePiece);
         a.n0 = f.n;
-        a.n_data = s->cfg.n_data;
-        a.n_blocks = (s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+        a.n_data = f.n_data;
+        a.n_blocks = (f.n_data + kPointwiseWave - 1) / kPointwiseWave;
+        a.len = f.d_len;
         a.x = f.d_x;
         a.y = f.d_y;
         a.c = f.c;
@@ -183,7 +195,7 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
 static int pointwise_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v, bool up) {
     PointwiseFold &f = s->pw;
     FOLD_TRY(fold_xfer_check("pointwise", f.open, v, up));
-    const size_t nk = (size_t)f.n_keep, ns = nk * s->cfg.n_data, np = (size_t)s->cfg.n_par;
+    const size_t nk = (size_t)f.n_keep, ns = nk * f.n_data, np = (size_t)s->cfg.n_par;
     FOLD_TRY(fold_order_behind_stream(s));
     const FoldCopy copy{s, up};
     double *const host[kPointwiseWords] = {v->origin, v->sum, v->sq, v->m_up, v->S_up, v->m_dn, v->S_dn, v->S2_dn};
@@ -210,6 +222,20 @@ extern "C" int apemost_hip_pointwise_set(apemost_hip_sampler *s, const apemost_h
     return pointwise_xfer(s, v, true);
 }
 
+extern "C" int apemost_hip_pointwise_lengths(apemost_hip_sampler *s, int32_t *len) {
+    CHECK_S(s);
+    const PointwiseFold &f = s->pw;
+    if (!f.open || !len)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_lengths: %s", f.open ? "len is NULL" : "no pointwise_begin");
+    for (int k = 0; k < f.n_keep; k++)
+        len[k] = f.n_data;
+    if (f.d_len) {
+        HIP_TRY(hipMemcpyAsync(len, f.d_len, (size_t)f.n_keep * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    return APEMOST_HIP_OK;
+}
+
 extern "C" int apemost_hip_pointwise_end(apemost_hip_sampler *s) {
     CHECK_S(s);
     POINTWISE_HAS_TERM(s, "pointwise_end");
@@ -218,7 +244,7 @@ extern "C" int apemost_hip_pointwise_end(apemost_hip_sampler *s) {
 
 // padded series (64 per block of data) times the slots of a series' buffer
 static u64 pointwise_tail_slots(const apemost_hip_sampler *s, int B) {
-    const u64 n_blocks = ((u64)s->cfg.n_data + kPointwiseWave - 1) / kPointwiseWave;
+    const u64 n_blocks = ((u64)s->pw.n_data + kPointwiseWave - 1) / kPointwiseWave;
     return (u64)s->pw.n_keep * n_blocks * kPointwiseWave * (u64)B;
 }
 
@@ -232,6 +258,9 @@ extern "C" int apemost_hip_pointwise_tail_begin(apemost_hip_sampler *s, int32_t 
     PointwiseFold &f = s->pw;
     if (!f.open)
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: no pointwise_begin");
+    if (f.d_len)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "pointwise_tail_begin: the kept chains' ladders differ in n_data: the tail "
+                    "of a ragged batch is a follow-up; keep chains of ladders of one length, or one fold per length");
     if (f.n > 0 && !f.n_set)
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: the fold has accumulated %llu samples whose tail is "
                     "lost: begin the tail before the first accumulate, or right behind pointwise_set",
@@ -246,14 +275,14 @@ extern "C" int apemost_hip_pointwise_tail_begin(apemost_hip_sampler *s, int32_t 
         if (fits)
             return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: %d chains x %d data (in blocks of 64) x %d slots "
                         "for capacity %d: more than 2^28 slots (2 GiB); the largest capacity that fits is %d",
-                        f.n_keep, s->cfg.n_data, B, capacity, fits);
+                        f.n_keep, f.n_data, B, capacity, fits);
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_begin: %d chains x %d data (in blocks of 64) x %d slots for "
                     "capacity %d: more than 2^28 slots (2 GiB); the largest capacity that fits is 0: no capacity fits, "
-                    "keep fewer chains", f.n_keep, s->cfg.n_data, B, capacity);
+                    "keep fewer chains", f.n_keep, f.n_data, B, capacity);
     }
     FOLD_TRY(fold_reset(s, f.tail));
     PointwiseTailFold &t = f.tail;
-    const size_t ns = (size_t)f.n_keep * s->cfg.n_data;
+    const size_t ns = (size_t)f.n_keep * f.n_data;
     const int rc = [&]() -> int {
         FOLD_TRY(fold_alloc(s, t.mem, &t.d_buf, (size_t)pointwise_tail_slots(s, B), false));
         FOLD_TRY(fold_alloc(s, t.mem, &t.d_slots, ns, true));
@@ -289,7 +318,7 @@ static int pointwise_tail_xfer(apemost_hip_sampler *s, const apemost_hip_pointwi
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_%s: no pointwise_tail_begin", what);
     if (!v || !v->count || !v->values)
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_tail_%s: the view or one of its arrays is NULL", what);
-    const size_t ns = (size_t)s->pw.n_keep * s->cfg.n_data, cap = (size_t)s->pw.tail.capacity;
+    const size_t ns = (size_t)s->pw.n_keep * s->pw.n_data, cap = (size_t)s->pw.tail.capacity;
     if (up)
         for (size_t q = 0; q < ns; q++) {
             if (v->count[q] > cap)
@@ -342,10 +371,11 @@ extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int3
                                                     const double *params, double *out) {
     CHECK_S(s);
     POINTWISE_HAS_TERM(s, "pointwise_loglike");
-    const int np = s->cfg.n_par, nd = s->cfg.n_data;
+    const int np = s->cfg.n_par;
     if (ladder < 0 || ladder >= (s->batch ? s->n_ladders : 1))
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: ladder %d outside [0,%d)", ladder,
                     s->batch ? s->n_ladders : 1);
+    const int nd = ladder_len(s, ladder);
     if (n < 1 || !params || !out || (u64)n * (u64)nd > ((u64)1 << 26))
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike: %d rows x %d data, or a NULL array", n, nd);
     FoldScratch scratch;
@@ -356,7 +386,7 @@ extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int3
         HIP_TRY(hipMemcpyAsync(d_par, params, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, s->stream));
         const dim3 grid((unsigned)((nd + kPointwiseWave - 1) / kPointwiseWave) * (unsigned)n), block(kPointwiseWave);
         // the ladder's columns 0 and 1 (the data is stored by columns, ladder after ladder)
-        const double *x = s->d.data + (size_t)ladder * s->cfg.n_cols * nd, *y = x + nd;
+        const double *x = ladder_data(s, ladder), *y = x + nd;
         const double c = pointwise_c(s);
         if (s->cfg.model == APEMOST_MODEL_USER) { // all n_cols columns of the ladder's rows
             int np_ = np, nd_ = nd, nc = s->cfg.n_cols;

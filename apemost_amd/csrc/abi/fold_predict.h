@@ -48,7 +48,11 @@ extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_h
         return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: config is NULL");
     const int np = s->cfg.n_par;
     FOLD_TRY(fold_check_chains(s, "predict", cfg->n_keep, cfg->chains));
-    const int n_x = cfg->x ? cfg->n_x : s->cfg.n_data;
+    // at the data's abscissae: the longest data among the kept chains' ladders (a batch's ladders may differ in
+    // length: the arrays stay rectangular and every kept chain folds its own len[k] <= n_x series)
+    std::vector<int> len;
+    bool ragged = false;
+    const int n_x = cfg->x ? cfg->n_x : kept_lengths(s, cfg->n_keep, cfg->chains, len, &ragged);
     if (n_x < 1)
         return fail(APEMOST_HIP_ERR_INVALID, "predict_begin: n_x %d < 1", n_x);
     // a user model's abscissae are whole rows: [n_x][n_cols] from the caller, or the sampler's data
@@ -92,6 +96,10 @@ extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_h
     FOLD_TRY(fold_alloc(s, f.mem, &f.d_best_prob, nk, false));
     FOLD_TRY(fold_alloc(s, f.mem, &f.d_best_params, nk * np, true));
     FOLD_TRY(fold_alloc(s, f.mem, &f.d_best_n, nk, true));
+    if (ragged) {
+        FOLD_TRY(fold_alloc(s, f.mem, &f.d_len, nk, false));
+        HIP_TRY(hipMemcpyAsync(f.d_len, len.data(), nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    }
     std::vector<double> pinf(ns, INFINITY), ninf(ns, -INFINITY);
     HIP_TRY(hipMemcpyAsync(f.d_vmin, pinf.data(), ns * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(f.d_vmax, ninf.data(), ns * sizeof(double), hipMemcpyHostToDevice, s->stream));
@@ -105,9 +113,9 @@ extern "C" int apemost_hip_predict_begin(apemost_hip_sampler *s, const apemost_h
             HIP_TRY(hipMemcpyAsync(dst, host_x, (size_t)nc * n_x * sizeof(double), hipMemcpyHostToDevice, s->stream));
         } else { // column 0 of the kept chain's own ladder (the data is stored by columns, ladder after ladder);
                  // a user model: all of its columns
-            const int ladder = s->batch ? cfg->chains[k] / s->per_ladder : 0;
-            const double *col0 = s->d.data + (size_t)ladder * s->cfg.n_cols * s->cfg.n_data;
-            HIP_TRY(hipMemcpyAsync(dst, col0, (size_t)nc * n_x * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+            // (a batch runs the built-in models only: nc = 1, and len[k] <= n_x values of the ladder's own column)
+            const double *col0 = ladder_data(s, s->batch ? cfg->chains[k] / s->per_ladder : 0);
+            HIP_TRY(hipMemcpyAsync(dst, col0, (size_t)nc * len[k] * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
         }
     }
     HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's arrays are read until here)
@@ -155,6 +163,7 @@ extern "C" int apemost_hip_predict_accumulate(apemost_hip_sampler *s, const doub
         a.best_prob = f.d_best_prob;
         a.best_params = f.d_best_params;
         a.best_n = f.d_best_n;
+        a.len = f.d_len;
         HIP_TRY(predict_launch_fold(s, a));
         f.n += a.n;
     }
@@ -193,6 +202,20 @@ extern "C" int apemost_hip_predict_set(apemost_hip_sampler *s, const apemost_hip
     return predict_xfer(s, v, true);
 }
 
+extern "C" int apemost_hip_predict_lengths(apemost_hip_sampler *s, int32_t *len) {
+    CHECK_S(s);
+    const PredictFold &f = s->pr;
+    if (!f.open || !len)
+        return fail(APEMOST_HIP_ERR_INVALID, "predict_lengths: %s", f.open ? "len is NULL" : "no predict_begin");
+    for (int k = 0; k < f.n_keep; k++)
+        len[k] = f.n_x;
+    if (f.d_len) {
+        HIP_TRY(hipMemcpyAsync(len, f.d_len, (size_t)f.n_keep * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    return APEMOST_HIP_OK;
+}
+
 extern "C" int apemost_hip_predict_end(apemost_hip_sampler *s) {
     CHECK_S(s);
     PREDICT_HAS_CURVE(s, "predict_end");
@@ -205,7 +228,7 @@ extern "C" int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, cons
     CHECK_S(s);
     PREDICT_HAS_CURVE(s, "predict_curve");
     if (!x)
-        n_x = s->cfg.n_data;
+        n_x = ladder_len(s, 0); // (a batch: ladder 0's data, which d.data starts with)
     if (n < 1 || !params || !out || n_x < 1 || (u64)n * (u64)n_x > ((u64)1 << 26))
         return fail(APEMOST_HIP_ERR_INVALID, "predict_curve: %d rows x %d abscissae, or a NULL array", n, n_x);
     const int np = s->cfg.n_par;

@@ -143,6 +143,7 @@ struct PredictFold {
     int *d_chains;
     double *d_x, *d_origin, *d_sum, *d_sq, *d_vmin, *d_vmax, *d_best_prob, *d_best_params;
     u64 *d_hist, *d_best_n;
+    int *d_len; // [n_keep] abscissae per kept chain where they differ (the data of a ragged batch), else nullptr
     FoldMem mem;
 };
 
@@ -160,9 +161,11 @@ struct PointwiseTailFold {
 struct PointwiseFold {
     bool open;
     int n_keep;
-    double c; // 1 / (-2 sigma^2)
+    int n_data; // the width of every [n_keep][n_data] array: the longest data among the kept chains' ladders
+    double c;   // 1 / (-2 sigma^2)
     u64 n;
     int *d_chains;
+    int *d_len; // [n_keep] data per kept chain where they differ (a ragged batch), else nullptr
     double *d_x, *d_y; // [n_keep][n_data] (a user model: d_x [n_keep][n_cols][n_data], no d_y)
     double *d_state;   // the eight [n_keep][n_data] words, one after the other (kPointwiseWords)
     double *d_par;     // par_origin, par_sum: [n_keep][n_par] each
@@ -261,6 +264,12 @@ struct apemost_hip_sampler {
     int n_ladders, per_ladder;
     std::vector<u64> seeds;        // [n_ladders] (empty for an ordinary sampler)
     std::vector<double> x_abs_max; // [n_ladders] of each ladder's data
+    // each ladder's data rows and where its matrix starts in d.data, in doubles (apemost_hip_create_batch_ragged;
+    // an equal batch: cfg.n_data and b * n_cols * cfg.n_data); cfg.n_data is the largest length.  data_off has
+    // n_ladders + 1 entries, the last being the whole allocation.  Empty for an ordinary sampler.
+    std::vector<int> data_len;
+    std::vector<u64> data_off;
+    bool ragged; // the lengths differ
     // the folds (apemost_hip_<fold>_begin .. _end), each in abi/fold_<fold>.h
     SummaryFold sum;
     PeaksFold pk;
@@ -271,6 +280,23 @@ struct apemost_hip_sampler {
     PointwiseFold pw;
     DerivedFold dv;
 };
+
+// the data rows of ladder b and its column-major matrix on the device (an ordinary sampler: b = 0)
+static int ladder_len(const apemost_hip_sampler *s, int b) { return s->batch ? s->data_len[b] : s->cfg.n_data; }
+static const double *ladder_data(const apemost_hip_sampler *s, int b) { return s->d.data + (s->batch ? s->data_off[b] : 0); }
+
+// the data rows of each kept chain's ladder; returns the largest, *differ: they are not all equal
+static int kept_lengths(const apemost_hip_sampler *s, int n_keep, const int *chains, std::vector<int> &len, bool *differ) {
+    len.resize(n_keep);
+    int longest = 0;
+    *differ = false;
+    for (int k = 0; k < n_keep; k++) {
+        len[k] = ladder_len(s, s->batch ? chains[k] / s->per_ladder : 0);
+        longest = len[k] > longest ? len[k] : longest;
+        *differ = *differ || len[k] != len[0];
+    }
+    return longest;
+}
 
 // everything a sampler owns on the device; safe on a half-built sampler
 static void release(apemost_hip_sampler *s) {

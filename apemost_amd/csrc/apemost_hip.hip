@@ -707,12 +707,15 @@ static int user_analysis(apemost_hip_sampler *s) {
     return rc;
 }
 
-// the two words per ladder a batch keeps behind its counters (DevArrays::ladder_words)
+// the four words per ladder a batch keeps behind its counters (DevArrays::ladder_words)
 static int ladder_words_upload(apemost_hip_sampler *s) {
-    std::vector<u64> w(2 * (size_t)s->n_ladders);
+    constexpr int kW = DevArrays::kLadderWords;
+    std::vector<u64> w(kW * (size_t)s->n_ladders);
     for (int b = 0; b < s->n_ladders; b++) {
-        w[2 * b] = s->seeds[b];
-        memcpy(&w[2 * b + 1], &s->x_abs_max[b], sizeof(double));
+        w[kW * b] = s->seeds[b];
+        memcpy(&w[kW * b + 1], &s->x_abs_max[b], sizeof(double));
+        w[kW * b + 2] = (u64)s->data_len[b];
+        w[kW * b + 3] = s->data_off[b];
     }
     HIP_TRY(hipMemcpyAsync(s->d.ladder_words(), w.data(), w.size() * sizeof(u64), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -761,8 +764,8 @@ static int create_body(apemost_hip_sampler *s) {
     d.n = cfg->n_chains;
     d.np = cfg->n_par;
     double *data = nullptr;
-    if ((rc = dev_alloc(s, &d.f, d.f_count())) || (rc = dev_alloc(s, &d.u, d.u_count() + (s->track ? d.flow_count() : s->batch ? 2 * (size_t)s->n_ladders : 0))) ||
-        (rc = dev_alloc(s, &data, (size_t)cfg->n_cols * cfg->n_data * s->n_ladders)))
+    if ((rc = dev_alloc(s, &d.f, d.f_count())) || (rc = dev_alloc(s, &d.u, d.u_count() + (s->track ? d.flow_count() : s->batch ? DevArrays::kLadderWords * (size_t)s->n_ladders : 0))) ||
+        (rc = dev_alloc(s, &data, s->batch ? (size_t)s->data_off[s->n_ladders] : (size_t)cfg->n_cols * cfg->n_data)))
         return rc;
     d.data = data;
     if (s->batch && (rc = ladder_words_upload(s)))
@@ -872,9 +875,10 @@ static int create_body(apemost_hip_sampler *s) {
 }
 
 // seeds == nullptr: an ordinary sampler; else a batch of n_ladders ladders of per_ladder chains, *cfg already
-// describing the whole grid (apemost_hip_create_batch)
+// describing the whole grid (apemost_hip_create_batch).  n_data: the ladders' data rows, cfg->n_data being the
+// largest (apemost_hip_create_batch_ragged), or nullptr: cfg->n_data for every ladder.
 static int create_impl(const apemost_hip_config *cfg, int n_ladders, int per_ladder, const uint64_t *seeds,
-                       apemost_hip_sampler **out) {
+                       apemost_hip_sampler **out, const int32_t *n_data = nullptr) {
     if (cfg->abi_version != APEMOST_HIP_ABI_VERSION)
         return fail(APEMOST_HIP_ERR_INVALID, "ABI version %d, library has %d", cfg->abi_version,
                     APEMOST_HIP_ABI_VERSION);
@@ -973,6 +977,7 @@ static int create_impl(const apemost_hip_config *cfg, int n_ladders, int per_lad
     s->rwm_keep = nullptr;
     s->in_rwm = false;
     s->sum = {};
+    s->ragged = false;
     s->batch = seeds != nullptr;
     s->track = (cfg->flags & APEMOST_HIP_FLAG_TRACK_REPLICAS) != 0;
     s->n_ladders = n_ladders;
@@ -980,6 +985,18 @@ static int create_impl(const apemost_hip_config *cfg, int n_ladders, int per_lad
     if (seeds) {
         s->seeds.assign(seeds, seeds + n_ladders);
         s->x_abs_max.assign(n_ladders, INFINITY); // until set_data
+        s->data_len.assign(n_ladders, cfg->n_data);
+        if (n_data)
+            s->data_len.assign(n_data, n_data + n_ladders);
+        s->data_off.assign((size_t)n_ladders + 1, 0);
+        // (the one statement of the layout rule; its argument checks have passed above, or in create_batch_ragged)
+        const int rc_layout = apemost_hip_ragged_layout(n_ladders, cfg->n_cols, s->data_len.data(), reinterpret_cast<uint64_t *>(s->data_off.data()), nullptr, nullptr);
+        if (rc_layout != APEMOST_HIP_OK) {
+            delete s;
+            return rc_layout;
+        }
+        for (int b = 0; b < n_ladders; b++)
+            s->ragged = s->ragged || s->data_len[b] != s->data_len[0];
     }
     if (s->waves == 6 && (s->batch || (cfg->flags & (APEMOST_HIP_FLAG_PROPOSAL_LOGISTIC | APEMOST_HIP_FLAG_PROPOSAL_UNIFORM |
                                                      APEMOST_HIP_FLAG_RANDOMSWAP | APEMOST_HIP_FLAG_SWAP_EVEN_ODD |
@@ -1005,11 +1022,9 @@ extern "C" int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sam
 
 // A ladder batch: what it cannot do is refused here, before any device is touched, so that nothing runs
 // silently as a single ladder (the list: include/apemost_hip.h).
-extern "C" int apemost_hip_create_batch(const apemost_hip_config *cfg, int32_t n_ladders, const uint64_t *seeds,
-                                        apemost_hip_sampler **out) {
-    if (!cfg || !out)
-        return fail(APEMOST_HIP_ERR_INVALID, "cfg/out is NULL");
-    *out = nullptr;
+// n_data: apemost_hip_create_batch_ragged's lengths, or nullptr
+static int create_batch_impl(const apemost_hip_config *cfg, int32_t n_ladders, const uint64_t *seeds, const int32_t *n_data,
+                             apemost_hip_sampler **out) {
     if (!seeds || n_ladders < 1)
         return fail(APEMOST_HIP_ERR_INVALID, "create_batch: n_ladders %d needs that many seeds", n_ladders);
     if (cfg->abi_version != APEMOST_HIP_ABI_VERSION)
@@ -1040,7 +1055,76 @@ extern "C" int apemost_hip_create_batch(const apemost_hip_config *cfg, int32_t n
     grid.n_chains = cfg->n_chains * n_ladders;
     grid.n_chains_global = grid.n_chains;
     grid.seed = seeds[0];
-    return create_impl(&grid, n_ladders, cfg->n_chains, seeds, out);
+    if (n_data) {
+        // the sampler's own n_data is the largest: one launch has one LDS size and one wave count, and both follow
+        // the longest ladder (choose_waves' by_data, choose_lds, the launches' LDS, the calibration's t_eval)
+        if (cfg->n_cols < 2 || cfg->n_cols > 65535)
+            return fail(APEMOST_HIP_ERR_INVALID, "create_batch_ragged: n_cols %d outside [2,65535]", cfg->n_cols);
+        uint64_t total = 0;
+        const int rc = apemost_hip_ragged_layout(n_ladders, cfg->n_cols, n_data, nullptr, &grid.n_data, &total);
+        if (rc != APEMOST_HIP_OK)
+            return rc;
+    }
+    return create_impl(&grid, n_ladders, cfg->n_chains, seeds, out, n_data);
+}
+
+extern "C" int apemost_hip_create_batch(const apemost_hip_config *cfg, int32_t n_ladders, const uint64_t *seeds,
+                                        apemost_hip_sampler **out) {
+    if (!cfg || !out)
+        return fail(APEMOST_HIP_ERR_INVALID, "cfg/out is NULL");
+    *out = nullptr;
+    return create_batch_impl(cfg, n_ladders, seeds, nullptr, out);
+}
+
+extern "C" int apemost_hip_ragged_layout(int32_t n_ladders, int32_t n_cols, const int32_t *n_data, uint64_t *offsets,
+                                         int32_t *n_data_max, uint64_t *total) {
+    if (n_ladders < 1 || n_cols < 1 || !n_data)
+        return fail(APEMOST_HIP_ERR_INVALID, "ragged_layout: n_ladders %d, n_cols %d, n_data %s", n_ladders, n_cols,
+                    n_data ? "given" : "NULL");
+    // the whole allocation in bytes has to fit a size_t with room to spare: 2^60 doubles is beyond any device
+    const uint64_t limit = (uint64_t)1 << 60;
+    uint64_t sum = 0;
+    int32_t longest = 0;
+    for (int b = 0; b < n_ladders; b++) {
+        if (n_data[b] < 1)
+            return fail(APEMOST_HIP_ERR_INVALID, "ragged_layout: ladder %d has n_data %d: at least 1 row", b, n_data[b]);
+        if (offsets)
+            offsets[b] = sum;
+        sum += (uint64_t)n_cols * (uint64_t)n_data[b]; // (< 2^47 each: no wrap before the test)
+        if (sum > limit)
+            return fail(APEMOST_HIP_ERR_INVALID, "ragged_layout: the data of ladders 0 .. %d, %d columns each, overflow the allocation", b, n_cols);
+        longest = n_data[b] > longest ? n_data[b] : longest;
+    }
+    if (offsets)
+        offsets[n_ladders] = sum;
+    if (n_data_max)
+        *n_data_max = longest;
+    if (total)
+        *total = sum;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_create_batch_ragged(const apemost_hip_config *cfg, int32_t n_ladders, const uint64_t *seeds,
+                                               const int32_t *n_data, apemost_hip_sampler **out) {
+    if (!cfg || !out)
+        return fail(APEMOST_HIP_ERR_INVALID, "cfg/out is NULL");
+    *out = nullptr;
+    if (!n_data)
+        return fail(APEMOST_HIP_ERR_INVALID, "create_batch_ragged: n_data is NULL (one length per ladder)");
+    if (seeds && n_ladders >= 1) // (else create_batch's own refusal; the lengths first, as nothing else reads them)
+        for (int b = 0; b < n_ladders; b++)
+            if (n_data[b] < 1)
+                return fail(APEMOST_HIP_ERR_INVALID, "create_batch_ragged: ladder %d has n_data %d: at least 1 row", b, n_data[b]);
+    return create_batch_impl(cfg, n_ladders, seeds, n_data, out);
+}
+
+extern "C" int apemost_hip_ladder_n_data(apemost_hip_sampler *s, int32_t ladder, int32_t *n_data) {
+    if (!s || !n_data)
+        return fail(APEMOST_HIP_ERR_INVALID, "sampler / n_data is NULL");
+    if (ladder < 0 || ladder >= s->n_ladders)
+        return fail(APEMOST_HIP_ERR_INVALID, "ladder_n_data: ladder %d outside [0,%d)", ladder, s->n_ladders);
+    *n_data = ladder_len(s, ladder);
+    return APEMOST_HIP_OK;
 }
 
 extern "C" int apemost_hip_n_ladders(apemost_hip_sampler *s, int32_t *n_ladders) {
@@ -1156,7 +1240,10 @@ extern "C" int apemost_hip_set_chain_offset(apemost_hip_sampler *s, int64_t chai
 static int set_data_impl(apemost_hip_sampler *s, int ladder, const double *data_rowmajor) {
     if (!data_rowmajor)
         return fail(APEMOST_HIP_ERR_INVALID, "data is NULL");
-    const int n = s->cfg.n_data, nc = s->cfg.n_cols;
+    if (ladder < 0 && s->ragged)
+        return fail(APEMOST_HIP_ERR_INVALID, "set_data: the ladders of this batch differ in n_data: one matrix per ladder through "
+                                             "apemost_hip_set_data_ladder");
+    const int n = ladder_len(s, ladder < 0 ? 0 : ladder), nc = s->cfg.n_cols;
     std::vector<double> col((size_t)n * nc);
     double x_abs_max = 0;
     for (int i = 0; i < n; i++) {
@@ -1167,7 +1254,7 @@ static int set_data_impl(apemost_hip_sampler *s, int ladder, const double *data_
             x_abs_max = std::isfinite(ax) ? ax : INFINITY;
     }
     for (int b = ladder < 0 ? 0 : ladder; b < (ladder < 0 ? s->n_ladders : ladder + 1); b++) {
-        HIP_TRY(hipMemcpyAsync((void *)(s->d.data + (size_t)b * col.size()), col.data(), col.size() * sizeof(double),
+        HIP_TRY(hipMemcpyAsync((void *)ladder_data(s, b), col.data(), col.size() * sizeof(double),
                                hipMemcpyHostToDevice, s->stream));
         if (s->batch)
             s->x_abs_max[b] = x_abs_max;
@@ -1426,6 +1513,10 @@ static size_t classic_lds_bytes(const apemost_hip_sampler *s, int waves, bool ld
 // calibration picks one per segment, by the number of chains that are still calibrating)
 static int launch_shape(apemost_hip_sampler *s, KernelKind kind, int grid, const void *args, int waves, bool lds_data,
                         bool coop, bool helper = false) {
+    // the one instantiation that does not know a ladder's own length (ob_takes_ladder_length, pt_kernels.h) is not
+    // for a batch whose lengths differ: the same step without the helper wavefront, bit for bit the same chain
+    if (kind == K_ROUND_OB && helper && s->ragged && !ob_takes_ladder_length(s->kmodel, waves, lds_data, true))
+        helper = false;
     LaunchOp op;
     op.kind = kind;
     op.lds_data = lds_data;
@@ -1495,7 +1586,8 @@ extern "C" int apemost_hip_calc_model(apemost_hip_sampler *s, int32_t first, int
     for (int b = first / s->per_ladder; b * s->per_ladder < first + count; b++) {
         const int lo = b * s->per_ladder > first ? b * s->per_ladder : first;
         const int hi = (b + 1) * s->per_ladder < first + count ? (b + 1) * s->per_ladder : first + count;
-        a.d.data = s->d.data + (size_t)b * s->cfg.n_cols * s->cfg.n_data;
+        a.d.data = ladder_data(s, b);
+        a.sh.n_data = ladder_len(s, b);
         a.sh.x_abs_max = s->x_abs_max[b];
         a.first = lo;
         const int rc = launch(s, K_CALC, hi - lo, &a, false);

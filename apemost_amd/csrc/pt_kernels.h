@@ -49,6 +49,17 @@ __host__ __device__ constexpr bool has_producer(int waves) { return waves >= 4; 
 #endif
 __host__ __device__ constexpr bool has_one_barrier(int waves) { return (APEMOST_OB_WAVES_MASK >> waves) & 1; }
 __host__ __device__ constexpr int block_threads(int waves, bool) { return waves * kWave; }
+// Which instantiations of pt_round_ob_kernel take a ladder's own data length from its ladder words (ladder_view).
+// All but one: the pulse_vrot variant with eight likelihood waves, the data read through L2 and a helper wavefront.  With
+// the length a loaded value instead of a kernel argument -- one more scalar register that lives through the
+// kernel and cannot be refetched from the argument block -- the register allocator leaves that one kernel a 16-byte
+// stack slot behind which nothing reads or writes (an sgpr_128 whose reloads were all rematerialised from the
+// argument block), and the dispatch would reserve scratch for it.  That instantiation therefore keeps the grid's
+// length, as before ragged batches existed, and the host never launches it on a batch whose lengths differ: such a
+// launch goes without the helper wavefront, which changes no result (launch_shape, apemost_hip.hip).
+__host__ __device__ constexpr bool ob_takes_ladder_length(int model, int lw, bool lds_data, bool helper) {
+    return !(model % kVariantModel == APEMOST_MODEL_PULSE_VROT && lw == 8 && !lds_data && helper);
+}
 
 template <int MODEL, int WAVES, bool LDS_DATA, bool PRODUCER>
 __device__ __forceinline__ void engine_setup(Engine<MODEL, WAVES, LDS_DATA, PRODUCER> &e, const DevArrays &d,
@@ -98,26 +109,39 @@ __device__ __forceinline__ void engine_setup(Engine<MODEL, WAVES, LDS_DATA, PROD
 
 // A ladder batch (kVariantBatch; the variant instantiations only, so the default kernels carry no test for
 // it): local chain c of the grid is chain c % n_global of ladder b = c / n_global.  The workgroup sees the
-// arguments of a stand-alone sampler of that ladder: the ladder's Philox key, its data matrix, and a chain
+// arguments of a stand-alone sampler of that ladder: the ladder's Philox key, its data matrix and that matrix's
+// number of rows (the ladders of a batch may differ in it: apemost_hip_create_batch_ragged), and a chain
 // offset that turns the local index into the index inside the ladder (chain_offset + c = c % n_global), which
 // is what every RNG address and the swap schedule are made of.  Rows, counters, hand-off words and sample
 // rows stay indexed by the local chain; a pair (a, a + 1) has a + 1 < n_global, so partner rows never leave
-// the ladder.  Args: RoundArgs or CalibArgs.
+// the ladder.  Args: RoundArgs or CalibArgs.  The ladder's own length is ladder_length's, below.
 template <int MODEL, class Args>
 __device__ __forceinline__ std::conditional_t<(MODEL >= kVariantModel), Args, const Args &> ladder_view(const Args &grid, int c) {
     if constexpr (MODEL >= kVariantModel) {
         Args a = grid;
         if (a.sh.variant & kVariantBatch) {
-            const int per = (int)a.sh.n_global, b = c / per;
-            const u64 *w = a.d.ladder_words() + 2 * (size_t)b;
+            const int per = (int)a.sh.n_global, b = (int)((unsigned)c / (unsigned)per); // (both positive)
+            const u64 *w = a.d.ladder_words() + DevArrays::kLadderWords * (size_t)b;
+            a.d.data += (size_t)w[3];
             a.sh.seed = w[0];
             a.sh.x_abs_max = __longlong_as_double((long long)w[1]);
             a.sh.chain_offset = -(long long)b * per;
-            a.d.data += (size_t)b * ((unsigned)a.sh.variant >> 16) * (size_t)a.sh.n_data;
         }
         return a;
     } else {
         return grid; // (the default kernels: the launch's own argument block, untouched)
+    }
+}
+
+// ... and the rows of the ladder's data matrix, which the ladders of a batch may differ in
+// (apemost_hip_create_batch_ragged): called on the view, by every kernel but the one ob_takes_ladder_length names.
+template <int MODEL, class Args>
+__device__ __forceinline__ void ladder_length(Args &a, int c) {
+    if constexpr (MODEL >= kVariantModel) {
+        if (a.sh.variant & kVariantBatch) {
+            const unsigned b = (unsigned)c / (unsigned)a.sh.n_global; // (both positive)
+            a.sh.n_data = (int)a.d.ladder_words()[DevArrays::kLadderWords * (size_t)b + 2]; // (uniform over the workgroup)
+        }
     }
 }
 
@@ -455,6 +479,7 @@ void pt_round_kernel(const RoundArgs grid) {
     Engine<MODEL, WAVES, LDS_DATA, PROD> e;
     const int c = blockIdx.x;
     decltype(auto) a = ladder_view<MODEL>(grid, c);
+    ladder_length<MODEL>(a, c);
     engine_setup(e, a.d, a.sh, c, lds);
     chain_load(e, a.d, a.sh, c, a.cur);
     e.pin_uniforms();
@@ -574,6 +599,8 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
     ObEngine<MODEL, LW, LDS_DATA, HELPER> e;
     const int c = blockIdx.x;
     decltype(auto) a = ladder_view<MODEL>(grid, c);
+    if constexpr (ob_takes_ladder_length(MODEL, LW, LDS_DATA, HELPER))
+        ladder_length<MODEL>(a, c);
     e.setup_common(a.d, a.sh, c, lds);
 #if APEMOST_OB_HELPER_SIMD
     if (HELPER && e.hw > LW + 3 && !e.is_helper())
@@ -1004,6 +1031,7 @@ void pt_calibrate_kernel(const CalibArgs grid) {
     const int slot = grid.list[blockIdx.x];
     const int c = grid.first + slot;
     decltype(auto) a = ladder_view<MODEL>(grid, c);
+    ladder_length<MODEL>(a, c);
     const int n = a.sh.n_par;
     engine_setup(e, a.d, a.sh, c, lds);
     chain_load(e, a.d, a.sh, c, a.cur);

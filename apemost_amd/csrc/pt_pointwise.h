@@ -110,6 +110,8 @@ struct PointwiseArgs {
     double sigma, hmin;
     double *origin, *sum, *sq, *m_up, *S_up, *m_dn, *S_dn, *S2_dn; // [n_keep][n_data]
     double *par_origin, *par_sum;     // [n_keep][n_par]
+    const int *len;                   // [n_keep]: the data kept chain k really has, <= n_data (a batch whose ladders
+                                      // differ in length); series past them are never touched.  nullptr: n_data
 };
 
 // Where a lane's term comes from: its datum in registers and the built-in curve and term.  (pt_user_fold.h: the row
@@ -157,7 +159,7 @@ __device__ __forceinline__ void pointwise_fold_body(const PointwiseArgs &a) {
         return;
     }
     const int i = blk * kPointwiseWave + lane;
-    const bool active = i < a.n_data;
+    const bool active = i < (a.len ? a.len[k] : a.n_data);
     const size_t s = (size_t)k * a.n_data + (active ? i : 0);
     EVAL ev;
     ev.init(a, k, i, s, active);

@@ -192,6 +192,9 @@ struct PredictArgs {
     unsigned long long *hist;         // [n_keep][n_x][nbins]
     double *best_prob, *best_params;  // [n_keep], [n_keep][n_par]
     unsigned long long *best_n;       // [n_keep]
+    const int *len;                   // [n_keep]: the abscissae kept chain k really has, <= n_x (the data of a batch
+                                      // whose ladders differ in length); series past them are never touched.
+                                      // nullptr: n_x for every kept chain
 };
 
 // Where a lane's value comes from: its abscissa in a register and the built-in curve.  (pt_user_fold.h: the row index
@@ -259,13 +262,14 @@ __device__ __forceinline__ void predict_fold_body(const PredictArgs &a) {
         return;
     }
     const int i0 = blk * a.points, i = i0 + lane;
-    const bool active = lane < a.points && i < a.n_x;
+    const int n_mine = a.len ? a.len[k] : a.n_x; // (uniform over the workgroup)
+    const bool active = lane < a.points && i < n_mine;
     const size_t s = (size_t)k * a.n_x + (active ? i : 0);
     EVAL ev;
     ev.init(a, k, i, s, active);
     double *edges = predict_lds;
     unsigned int *bins = (unsigned int *)(predict_lds + a.nbins + 1);
-    const int here = a.n_x - i0 < a.points ? a.n_x - i0 : a.points; // abscissae of this workgroup
+    const int here = n_mine - i0 < a.points ? n_mine - i0 : a.points; // abscissae of this workgroup (<= 0: none)
     const int rw = predict_row_words(a.nbins);
     bool sorted = true;
     double e0 = 0, etop = 0, scale = 0;

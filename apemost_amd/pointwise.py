@@ -37,6 +37,13 @@ Keep in mind:
     between models fitted with the same sigma are not.  For the pulse models the term is -(ln v + y / v); the
     parameter-1 offset that the reference adds to the sum is not a datum's term and is left out.
 
+A fold over a batch whose ladders differ in data length (HipSampler.batch with a list of matrices) stays rectangular,
+n_data being the longest kept ladder's length, and carries `lengths` [n_keep]: kept chain k has lengths[k] data, and
+the entries behind them hold their initial values, 0 (at_mean: NaN).  per_ladder() trims every ladder's object to its
+length; what it returns are ordinary Pointwise objects.  A reduction over the data of the untrimmed object (lppd,
+elpd_*, waic*, looic, p_*, dic, compare, criteria, text, write) would take padding for data and raises ValueError
+instead.
+
 `loglike_numpy` states the term in plain numpy (the operation order of apemost_amd/csrc/pt_pointwise.h on
 predict.curve_numpy's curve, with numpy's sine and logarithm in place of the device's).
 
@@ -144,6 +151,8 @@ class Pointwise:
     * at_mean is filled by HipSampler.pointwise() on the device (pointwise_loglike, in a batch over the kept chain's
       own ladder's data); it is NaN where nobody filled it, and dic and p_dic with it."""
 
+    lengths = None   # [n_keep] data per kept chain of a ragged batch's fold (see the module's docstring)
+
     def __init__(self, n, origin, sum, sq, m_up, S_up, m_dn, S_dn, S2_dn, par_origin, par_sum, chains, x, y, n_par, model,
                  sigma=0.5, thin=1, n_ladders=1, at_mean=None):
         self.n = np.ascontiguousarray(n, dtype=np.uint64).reshape(1)
@@ -179,8 +188,19 @@ class Pointwise:
                                   par_sum=self.par_sum.ctypes.data_as(dp),
                                   **{f: getattr(self, f).ctypes.data_as(dp) for f in STATE})
 
+    def is_ragged(self):
+        """the kept chains differ in length: entries behind lengths[k] are padding"""
+        return self.lengths is not None and bool(np.any(np.asarray(self.lengths) != self.n_data))
+
+    def _no_padding(self, what):
+        if self.is_ragged():
+            raise ValueError("%s over a ragged batch's fold would take padding for data (lengths %s of n_data %d): "
+                             "use per_ladder(), which trims every ladder to its length"
+                             % (what, np.asarray(self.lengths).tolist(), self.n_data))
+
     def per_ladder(self, n_ladders=None):
-        """one Pointwise per ladder of a batch: the kept chains, ladder-major, in equal shares"""
+        """one Pointwise per ladder of a batch: the kept chains, ladder-major, in equal shares; of a ragged batch's
+        fold each trimmed to its ladder's length (the kept chains of one ladder share it)"""
         n_ladders = self.n_ladders if n_ladders is None else n_ladders
         if n_ladders < 1 or self.n_keep % n_ladders:
             raise ValueError("%d kept chains are not %d equal ladders" % (self.n_keep, n_ladders))
@@ -188,9 +208,15 @@ class Pointwise:
         out = []
         for b in range(n_ladders):
             k = slice(b * per, (b + 1) * per)
-            out.append(Pointwise(self.n.copy(), *[getattr(self, f)[k] for f in STATE], self.par_origin[k],
-                                 self.par_sum[k], self.chains[k], self.x[k], self.y[k], self.n_par, self.model,
-                                 self.sigma, self.thin, 1, self.at_mean[k]))
+            m = self.n_data
+            if self.lengths is not None:
+                mine = np.asarray(self.lengths)[k]
+                if np.any(mine != mine[0]):
+                    raise ValueError("ladder %d: its kept chains have lengths %s" % (b, mine.tolist()))
+                m = int(mine[0])
+            out.append(Pointwise(self.n.copy(), *[getattr(self, f)[k, :m] for f in STATE], self.par_origin[k],
+                                 self.par_sum[k], self.chains[k], self.x[k, :m], self.y[k, :m], self.n_par, self.model,
+                                 self.sigma, self.thin, 1, self.at_mean[k, :m]))
         return out
 
     # -- per datum ----------------------------------------------------------------------------
@@ -211,12 +237,14 @@ class Pointwise:
 
     def lppd(self, k=0):
         """[n_data]: m_up + ln(S_up / n), the log pointwise predictive density"""
+        self._no_padding("lppd")
         with np.errstate(all="ignore"):
             return self.m_up[k] + _ln(self.S_up[k] / self._n())
 
     def p_waic(self, kind=2, k=0):
         """[n_data]: the effective number of parameters per datum: kind 1 is 2 (lppd - mean_loglike), kind 2 the
         variance of l"""
+        self._no_padding("p_waic")
         if kind == 2:
             return self.var_loglike(k)
         if kind == 1:
@@ -225,25 +253,31 @@ class Pointwise:
         raise ValueError("kind %r: 1 or 2" % (kind,))
 
     def elpd_waic(self, kind=2, k=0):
+        self._no_padding("elpd_waic")
         with np.errstate(all="ignore"):
             return self.lppd(k) - self.p_waic(kind, k)
 
     def waic(self, kind=2, k=0):
+        self._no_padding("waic")
         return -2.0 * _total(self.elpd_waic(kind, k))
 
     def waic_se(self, kind=2, k=0):
         """the standard error of sum elpd_waic: sqrt(n_data * variance of the pointwise elpd_waic)"""
+        self._no_padding("waic_se")
         return _spread(self.elpd_waic(kind, k))
 
     def elpd_loo(self, k=0):
         """[n_data]: -(m_dn + ln(S_dn / n)): the log of the harmonic mean of the datum's likelihood"""
+        self._no_padding("elpd_loo")
         with np.errstate(all="ignore"):
             return -(self.m_dn[k] + _ln(self.S_dn[k] / self._n()))
 
     def looic(self, k=0):
+        self._no_padding("looic")
         return -2.0 * _total(self.elpd_loo(k))
 
     def p_loo(self, k=0):
+        self._no_padding("p_loo")
         return _total(self.lppd(k)) - _total(self.elpd_loo(k))
 
     def loo_ess(self, k=0):
@@ -268,9 +302,11 @@ class Pointwise:
 
     def p_dic(self, k=0):
         """2 (sum l_i(mean parameters) - sum mean_loglike); needs at_mean"""
+        self._no_padding("p_dic")
         return 2.0 * (_total(self.at_mean[k]) - _total(self.mean_loglike(k)))
 
     def dic(self, k=0):
+        self._no_padding("dic")
         return -2.0 * _total(self.at_mean[k]) + 2.0 * self.p_dic(k)
 
     # -- comparing two models on the same data ------------------------------------------------
@@ -278,6 +314,8 @@ class Pointwise:
         """(difference, standard error): sum over the data of this model's pointwise elpd minus the other's, and
         sqrt(n_data * variance of the pointwise differences).  kind: "loo" or "waic".  Positive favours this model.
         ValueError unless both were folded over the same data."""
+        self._no_padding("compare")
+        other._no_padding("compare")
         if self.x[k].tobytes() != other.x[k_other].tobytes() or self.y[k].tobytes() != other.y[k_other].tobytes():
             raise ValueError("the two folds do not hold the same data")
         if kind == "loo":
@@ -304,6 +342,7 @@ class Pointwise:
 
     def text(self, k=0):
         """pointwise.txt: one line per datum, `x y mean sd lppd p_waic2 elpd_loo ess`, tab separated, %.15e"""
+        self._no_padding("text")
         with np.errstate(all="ignore"):
             cols = [self.x[k], self.y[k], self.mean_loglike(k), np.sqrt(self.var_loglike(k)), self.lppd(k),
                     self.p_waic(2, k), self.elpd_loo(k), self.loo_ess(k)]
@@ -315,6 +354,7 @@ class Pointwise:
                 [(self.par_origin, "<f8"), (self.par_sum, "<f8"), (self.at_mean, "<f8")])
 
     def write(self, path):
+        self._no_padding("write")
         with open(path, "wb") as f:
             f.write(_HEAD.pack(MAGIC, VERSION, self.n_keep, self.n_data, self.n_par, self.n_ladders, self.model, 0, 0,
                                int(self.n[0]), self.thin, self.sigma))

@@ -9,6 +9,13 @@ and its 1-based kept index best_n.
 
     mean = origin + sum / n          var = (sq - sum * sum / n) / n
 
+A fold at the data's abscissae of a batch whose ladders differ in data length (HipSampler.batch with a list of
+matrices) stays rectangular, n_x being the longest kept ladder's length, and carries `lengths` [n_keep]: kept chain k
+has lengths[k] abscissae, and the entries behind them hold their initial values (sums 0, vmin +inf, vmax -inf, counts
+0, x 0).  per_ladder() trims every ladder's object to its length; what it returns are ordinary Predict objects.  A
+reduction over the abscissae (chi2, text, write) of the untrimmed object would take padding for data and raises
+ValueError instead.
+
 Medians and credible bands come from the counts: mean +- sd is not a credible band when the frequency posterior is
 multimodal.  `curve_numpy` states the four curves in plain numpy (the operation order of apemost_amd/csrc/pt_predict.h
 with numpy's sine in place of the device's).
@@ -84,6 +91,8 @@ def _lorentz(h, d, lifetime):
 
 
 class Predict:
+    lengths = None   # [n_keep] abscissae per kept chain of a ragged batch's fold (see the module's docstring)
+
     def __init__(self, n, origin, sum, sq, vmin, vmax, hist, best_prob, best_params, best_n, chains, x, n_par, model,
                  lo=0.0, hi=0.0, thin=1, n_ladders=1):
         self.n = np.ascontiguousarray(n, dtype=np.uint64).reshape(1)
@@ -122,8 +131,19 @@ class Predict:
                                 best_prob=self.best_prob.ctypes.data_as(dp),
                                 best_params=self.best_params.ctypes.data_as(dp), best_n=self.best_n.ctypes.data_as(up))
 
+    def is_ragged(self):
+        """the kept chains differ in length: entries behind lengths[k] are padding"""
+        return self.lengths is not None and bool(np.any(np.asarray(self.lengths) != self.n_x))
+
+    def _no_padding(self, what):
+        if self.is_ragged():
+            raise ValueError("%s over a ragged batch's fold would take padding for data (lengths %s of n_x %d): "
+                             "use per_ladder(), which trims every ladder to its length"
+                             % (what, np.asarray(self.lengths).tolist(), self.n_x))
+
     def per_ladder(self, n_ladders=None):
-        """one Predict per ladder of a batch: the kept chains, ladder-major, in equal shares"""
+        """one Predict per ladder of a batch: the kept chains, ladder-major, in equal shares; of a ragged batch's fold
+        each trimmed to its ladder's length (the kept chains of one ladder share it)"""
         n_ladders = self.n_ladders if n_ladders is None else n_ladders
         if n_ladders < 1 or self.n_keep % n_ladders:
             raise ValueError("%d kept chains are not %d equal ladders" % (self.n_keep, n_ladders))
@@ -131,9 +151,15 @@ class Predict:
         out = []
         for b in range(n_ladders):
             k = slice(b * per, (b + 1) * per)
-            out.append(Predict(self.n.copy(), self.origin[k], self.sum[k], self.sq[k], self.vmin[k], self.vmax[k],
-                               self.hist[k], self.best_prob[k], self.best_params[k], self.best_n[k], self.chains[k],
-                               self.x[k], self.n_par, self.model, self.lo, self.hi, self.thin, 1))
+            m = self.n_x
+            if self.lengths is not None:
+                mine = np.asarray(self.lengths)[k]
+                if np.any(mine != mine[0]):
+                    raise ValueError("ladder %d: its kept chains have lengths %s" % (b, mine.tolist()))
+                m = int(mine[0])
+            out.append(Predict(self.n.copy(), self.origin[k, :m], self.sum[k, :m], self.sq[k, :m], self.vmin[k, :m],
+                               self.vmax[k, :m], self.hist[k, :m], self.best_prob[k], self.best_params[k], self.best_n[k],
+                               self.chains[k], self.x[k, :m], self.n_par, self.model, self.lo, self.hi, self.thin, 1))
         return out
 
     # -- what it gives ------------------------------------------------------------------------
@@ -217,12 +243,14 @@ class Predict:
 
     def chi2(self, y, sigma, k=0):
         """sum ((y - mean) / sigma)^2 over the abscissae"""
+        self._no_padding("chi2")
         r = (np.asarray(y, dtype=np.float64) - self.mean(k)) / sigma
         return float(np.sum(r * r))
 
     def text(self, y, best=None, k=0):
         """predict.txt: one line per abscissa, `x y mean sd residual min max best` (and `median lower68 upper68` with
         histograms), tab separated, "%.15e".  y: data column 1; best: the best-fit curve (default: curve_numpy)."""
+        self._no_padding("text")
         best = self.best_curve(None, k) if best is None else best
         cols = [self.x[k], np.asarray(y, dtype=np.float64), self.mean(k), self.sd(k), self.residuals(y, None, k),
                 self.vmin[k], self.vmax[k], np.asarray(best, dtype=np.float64)]
@@ -237,6 +265,7 @@ class Predict:
                 (self.best_params, "<f8"), (self.best_n, "<u8"))
 
     def write(self, path):
+        self._no_padding("write")
         with open(path, "wb") as f:
             f.write(_HEAD.pack(MAGIC, VERSION, self.n_keep, self.n_x, self.nbins, self.n_par, self.n_ladders, self.model,
                                0, int(self.n[0]), self.thin, self.lo, self.hi))

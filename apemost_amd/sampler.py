@@ -68,15 +68,38 @@ def ladder_view(arr, b, n_ladders):
     return arr[:, b * per:(b + 1) * per] if axis == 1 else arr[b * per:(b + 1) * per]
 
 
+def _rectangle(rows):
+    """1-D arrays of possibly different lengths as the rows of one [len(rows)][longest] array, zeros behind each"""
+    out = np.zeros((len(rows), max([len(r) for r in rows] + [0])), dtype=np.float64)
+    for k, r in enumerate(rows):
+        out[k, :len(r)] = r
+    return out
+
+
 class HipSampler:
     def __init__(self, model, n_par, n_chains, data, seed=0, device=0, chain_offset=0,
                  n_chains_global=None, waves_per_chain=0, sigma=0.5, hmin=1e-6, lds_policy=0, circular_params=0,
-                 flags=0, adapt_target=0.0, device_model_source=None, seeds=None):
+                 flags=0, adapt_target=0.0, device_model_source=None, seeds=None, ragged=False):
         """seeds=None: one ladder (a shard of it) of n_chains chains under `seed`.  seeds=[...]: a ladder batch
         (include/apemost_hip.h, apemost_hip_create_batch; HipSampler.batch reads better): len(seeds) independent
         ladders of n_chains chains EACH in one sampler, ladder b under seeds[b]; `data` is one matrix for every
-        ladder or [n_ladders][n_data][n_cols]; self.n_chains is then the total, self.chains_per_ladder the rest."""
-        data = np.ascontiguousarray(data, dtype=np.float64)
+        ladder, [n_ladders][n_data][n_cols], or a list of one [n_data_b][n_cols] matrix per ladder, whose lengths may
+        differ (apemost_hip_create_batch_ragged); self.n_chains is then the total, self.chains_per_ladder the rest,
+        self.n_data_per_ladder the ladders' data lengths.  ragged=True: through apemost_hip_create_batch_ragged even
+        where the lengths are equal (the two give the same sampler)."""
+        if seeds is not None and ragged and not isinstance(data, (list, tuple)):
+            data = np.asarray(data, dtype=np.float64)
+            data = [data] * len(seeds) if data.ndim == 2 else list(data)
+        # (a list whose elements are matrices: one per ladder; a nested list that spells one matrix, or a 3-D array,
+        # goes the way it always went)
+        if seeds is not None and isinstance(data, (list, tuple)) and len(data) > 0 and np.ndim(data[0]) == 2:
+            mats = [np.ascontiguousarray(m, dtype=np.float64) for m in data]
+            if len(mats) != len(seeds) or any(m.ndim != 2 or m.shape[1:] != mats[0].shape[1:] for m in mats):
+                raise ValueError("data: a list of one [n_data_b][n_cols] matrix per ladder, n_cols the same for all")
+            # (equal lengths: the rectangular batch, as ever)
+            data = np.stack(mats) if all(len(m) == len(mats[0]) for m in mats) and not ragged else mats
+        else:
+            data = np.ascontiguousarray(data, dtype=np.float64)
         if seeds is not None:
             self._init_batch(model, n_par, n_chains, data, [int(x) for x in seeds], device, chain_offset, n_chains_global,
                              waves_per_chain, sigma, hmin, lds_policy, circular_params, flags, adapt_target,
@@ -99,16 +122,20 @@ class HipSampler:
         self.chain_offset = chain_offset
         self.seed = seed
         self.n_ladders, self.chains_per_ladder, self.seeds = 1, n_chains, [seed]
+        self.n_data_per_ladder = [data.shape[0]]
         self._x0 = [data[:, 0].copy()]
         self._y0 = [data[:, 1].copy()]
 
     def _init_batch(self, model, n_par, n_chains, data, seeds, device, chain_offset, n_chains_global, waves_per_chain,
                     sigma, hmin, lds_policy, circular_params, flags, adapt_target, device_model_source):
         n_ladders = len(seeds)
-        if data.ndim not in (2, 3) or (data.ndim == 3 and data.shape[0] != n_ladders):
+        ragged = isinstance(data, list)   # one matrix per ladder, of different lengths
+        if not ragged and (data.ndim not in (2, 3) or (data.ndim == 3 and data.shape[0] != n_ladders)):
             raise ValueError("data: [n_data][n_cols], or [n_ladders][n_data][n_cols] with one matrix per ladder")
+        lengths = [len(m) for m in data] if ragged else [data.shape[-2]] * n_ladders
         self.cfg = capi.Config(abi_version=capi.ABI_VERSION, device=device, model=model, n_par=n_par,
-                               n_chains=n_chains, n_data=data.shape[-2], n_cols=data.shape[-1],
+                               n_chains=n_chains, n_data=max(lengths) if lengths else 0,
+                               n_cols=data[0].shape[-1] if ragged else data.shape[-1],
                                waves_per_chain=waves_per_chain, lds_policy=lds_policy, chain_offset=chain_offset,
                                n_chains_global=n_chains if n_chains_global is None else n_chains_global,
                                seed=0, sigma=sigma, hmin=hmin, circular_params=circular_params, flags=flags,
@@ -117,7 +144,12 @@ class HipSampler:
         self._h = C.c_void_p()
         self.L = capi.lib()
         arr = (C.c_uint64 * max(n_ladders, 1))(*seeds)
-        capi.check(self.L.apemost_hip_create_batch(C.byref(self.cfg), n_ladders, arr, C.byref(self._h)))
+        if ragged:
+            lens = (C.c_int32 * n_ladders)(*lengths)
+            capi.check(self.L.apemost_hip_create_batch_ragged(C.byref(self.cfg), n_ladders, arr, lens, C.byref(self._h)))
+        else:
+            capi.check(self.L.apemost_hip_create_batch(C.byref(self.cfg), n_ladders, arr, C.byref(self._h)))
+        self.n_data_per_ladder = lengths
         self.n_par, self.n_chains = n_par, n_chains * n_ladders
         self.n_chains_global = n_chains            # of the swap schedule: per ladder
         self.chain_offset = 0
@@ -125,7 +157,7 @@ class HipSampler:
         self.n_ladders, self.chains_per_ladder, self.seeds = n_ladders, n_chains, seeds
         self._x0 = [None] * n_ladders
         self._y0 = [None] * n_ladders
-        if data.ndim == 2:
+        if not ragged and data.ndim == 2:
             self.set_data(data)
         else:
             for b in range(n_ladders):
@@ -137,10 +169,17 @@ class HipSampler:
         return cls(model, n_par, n_chains, data, seeds=seeds, **kw)
 
     def set_data(self, data, ladder=None):
-        """the data matrix [n_data][n_cols] of every ladder (ladder=None) or of one ladder of a batch"""
+        """the data matrix [n_data][n_cols] of every ladder (ladder=None) or of one ladder of a batch, in that
+        ladder's own length (n_data_per_ladder)"""
         data = np.ascontiguousarray(data, dtype=np.float64)
-        if data.shape != (self.cfg.n_data, self.cfg.n_cols):
-            raise ValueError("data must be [%d][%d]" % (self.cfg.n_data, self.cfg.n_cols))
+        if ladder is None and len(set(self.n_data_per_ladder)) > 1:
+            raise ValueError("the ladders of this batch differ in data length %s: set_data(data, ladder=b)"
+                             % (self.n_data_per_ladder,))
+        if ladder is not None and not 0 <= int(ladder) < self.n_ladders:
+            raise ValueError("ladder %r outside [0,%d)" % (ladder, self.n_ladders))
+        n_data = self.n_data_per_ladder[0 if ladder is None else int(ladder)]
+        if data.shape != (n_data, self.cfg.n_cols):
+            raise ValueError("data must be [%d][%d]" % (n_data, self.cfg.n_cols))
         p = data.ctypes.data_as(C.POINTER(C.c_double))
         if ladder is None:
             capi.check(self.L.apemost_hip_set_data(self._h, p))
@@ -642,7 +681,7 @@ class HipSampler:
             xs = [self._x0[int(c) // self.chains_per_ladder if self.n_ladders > 1 else 0]
                   for c in self._pr_chains.tolist() if 0 <= c < self.n_chains]
             xs = xs if len(xs) == len(self._pr_chains) else [self._x0[0]] * len(self._pr_chains)
-            self._pr_x = np.array(xs, dtype=np.float64).reshape(len(self._pr_chains), -1)
+            self._pr_x = _rectangle(xs)   # (a ragged batch: every row in its own length, zeros behind it)
             xp, n_x = None, 0
         elif self.cfg.model == MODEL_USER:   # whole rows [n_x][n_cols]; the result's x is their column 0
             x = self._user_rows(x)
@@ -667,7 +706,14 @@ class HipSampler:
         pr = Predict.empty(self._pr_chains, self._pr_x, self.n_par, self.cfg.model, self._pr_nbins, self._pr_lo,
                            self._pr_hi, self._pr_thin, self.n_ladders)
         capi.check(self.L.apemost_hip_predict_get(self._h, C.byref(pr.view())))
+        pr.lengths = self._fold_lengths(self.L.apemost_hip_predict_lengths, pr.n_keep, pr.n_x)
         return pr
+
+    def _fold_lengths(self, call, n_keep, width):
+        """a fold's lengths [n_keep] where they are not all the width of its arrays (a ragged batch), else None"""
+        lens = np.zeros(n_keep, dtype=np.int32)
+        capi.check(call(self._h, lens.ctypes.data_as(C.POINTER(C.c_int32))))
+        return lens if np.any(lens != width) else None
 
     def predict_set(self, pr):
         """load a Predict (a resumed run) into the fold begun with the same configuration"""
@@ -685,7 +731,7 @@ class HipSampler:
         one = params.ndim == 1
         params = params.reshape(-1, self.n_par)
         if x is None:
-            xp, n_x = None, self.cfg.n_data
+            xp, n_x = None, self.n_data_per_ladder[0]
         elif self.cfg.model == MODEL_USER:
             x = self._user_rows(x)
             xp, n_x = x.ctypes.data_as(capi._dp), len(x)
@@ -711,8 +757,8 @@ class HipSampler:
         lads = [int(c) // self.chains_per_ladder if self.n_ladders > 1 else 0
                 for c in self._pw_chains.tolist() if 0 <= c < self.n_chains]
         lads = lads if len(lads) == len(self._pw_chains) else [0] * len(self._pw_chains)
-        self._pw_data = np.array([[self._x0[b], self._y0[b]] for b in lads], dtype=np.float64).reshape(
-            len(self._pw_chains), 2, -1)
+        # ([n_keep][2][n_data]; a ragged batch: every row in its own length, zeros behind it)
+        self._pw_data = np.stack([_rectangle([self._x0[b] for b in lads]), _rectangle([self._y0[b] for b in lads])], axis=1)
         cfg = capi.PointwiseConfig(n_keep=len(self._pw_chains),
                                    chains=self._pw_chains.ctypes.data_as(C.POINTER(C.c_int32)))
         capi.check(self.L.apemost_hip_pointwise_begin(self._h, C.byref(cfg)))
@@ -741,7 +787,7 @@ class HipSampler:
         from .psis import PointwiseTail
         n = C.c_uint64(0)
         capi.check(self.L.apemost_hip_pointwise_get(self._h, C.byref(capi.PointwiseView(n=C.pointer(n)))))
-        t = PointwiseTail.empty(self._pw_chains, self.cfg.n_data, self.pointwise_tail_capacity(), n.value, self._pw_thin,
+        t = PointwiseTail.empty(self._pw_chains, self._pw_data.shape[2], self.pointwise_tail_capacity(), n.value, self._pw_thin,
                                 self.n_ladders)
         capi.check(self.L.apemost_hip_pointwise_tail_get(self._h, C.byref(t.view())))
         t.clear_unused()
@@ -767,12 +813,14 @@ class HipSampler:
         pw = Pointwise.empty(self._pw_chains, self._pw_data[:, 0], self._pw_data[:, 1], self.n_par, self.cfg.model,
                              self.cfg.sigma, self._pw_thin, self.n_ladders)
         capi.check(self.L.apemost_hip_pointwise_get(self._h, C.byref(pw.view())))
+        pw.lengths = self._fold_lengths(self.L.apemost_hip_pointwise_lengths, pw.n_keep, pw.n_data)
         if at_mean and int(pw.n[0]) > 0:
             if self.n_ladders == 1:
                 pw.at_mean = self.pointwise_loglike(pw.par_mean_all()).reshape(pw.n_keep, pw.n_data)
             else:
                 for k in range(pw.n_keep):
-                    pw.at_mean[k] = self.pointwise_loglike(pw.par_mean(k), int(pw.chains[k]) // self.chains_per_ladder)
+                    b = int(pw.chains[k]) // self.chains_per_ladder
+                    pw.at_mean[k, :self.n_data_per_ladder[b]] = self.pointwise_loglike(pw.par_mean(k), b)
         return pw
 
     def pointwise_set(self, pw):
@@ -790,7 +838,7 @@ class HipSampler:
         params = np.ascontiguousarray(params, dtype=np.float64)
         one = params.ndim == 1
         params = np.ascontiguousarray(params.reshape(-1, self.n_par))
-        out = np.zeros((len(params), self.cfg.n_data))
+        out = np.zeros((len(params), self.n_data_per_ladder[ladder if 0 <= ladder < self.n_ladders else 0]))
         capi.check(self.L.apemost_hip_pointwise_loglike_ladder(self._h, int(ladder), len(params),
                                                                params.ctypes.data_as(capi._dp),
                                                                out.ctypes.data_as(capi._dp)))

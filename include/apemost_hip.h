@@ -320,9 +320,48 @@ int apemost_hip_create(const apemost_hip_config *cfg, apemost_hip_sampler **out)
  * n_ladders > 1 (no single data matrix).  waves_per_chain = 6 is APEMOST_HIP_ERR_INVALID, as for every variant. */
 int apemost_hip_create_batch(const apemost_hip_config *cfg, int32_t n_ladders, const uint64_t *seeds,
                              apemost_hip_sampler **out);
+/* ---- ragged ladder batches: one data set per ladder, each of its own length --------------------
+ * apemost_hip_create_batch_ragged is apemost_hip_create_batch with one number of data rows per ladder: n_data[b] >= 1
+ * rows for ladder b (cfg->n_data is ignored on input, as cfg->seed is; the sampler's own n_data is the largest of
+ * them).  Everything said of apemost_hip_create_batch holds, its list of refusals included, with these changes:
+ *   Identity: ladder b is, bit for bit, the stand-alone sampler with n_data = n_data[b], seed seeds[b], ladder b's
+ *   data and the same waves_per_chain.  Every loop of the likelihood takes its trip counts from the ladder's own
+ *   length, which is uniform over the chain's workgroup.
+ *   Data: apemost_hip_set_data_ladder(s, b, data) reads n_data[b] rows of [n_cols].  apemost_hip_set_data, which gives
+ *   every ladder one matrix, returns APEMOST_HIP_ERR_INVALID on a batch whose lengths differ (use set_data_ladder).
+ *   On the device the matrices lie one behind the other, column-major, ladder b's at the offset
+ *   sum over b' < b of n_cols * n_data[b'] doubles (apemost_hip_ragged_layout).
+ *   Geometry: one launch has one LDS size and one wave count.  What follows the data length -- LDS staging and its
+ *   size, the by-data bound of waves_per_chain = 0, the residency check, the calibration's segment shapes -- follows
+ *   the LONGEST ladder; what follows the chip follows the total number of chains, as in every batch.  A batch's
+ *   launch therefore lasts about as long as its longest ladder's.
+ *   Folds: those over sample rows alone (summary, joint, evidence, autocorr, peaks, derived) know nothing of data and
+ *   work as on every batch.  apemost_hip_predict_* at the data's abscissae (x == NULL) and apemost_hip_pointwise_* keep
+ *   their rectangular arrays [n_keep][n_x], n_x being the longest data among the KEPT chains' ladders; kept chain k
+ *   folds its own len[k] <= n_x series, which apemost_hip_predict_lengths / apemost_hip_pointwise_lengths report.
+ *   Entries with i >= len[k] are never written: after *_get they hold their initial values (origin, sums and
+ *   log-sum-exp words 0, vmin +inf, vmax -inf, counts 0), and *_set takes the same rectangular arrays back.  Predict
+ *   over a caller's grid (x != NULL) does not depend on the data and is unchanged.  The pointwise tail
+ *   (apemost_hip_pointwise_tail_begin) on kept chains whose ladders differ in length is refused with
+ *   APEMOST_HIP_ERR_UNSUPPORTED: a follow-up.
+ * If all n_data[b] are equal the sampler is in every respect the one apemost_hip_create_batch makes with that n_data.
+ * APEMOST_HIP_ERR_INVALID, before any device is touched: n_data == NULL, a length < 1, or a total
+ * sum of n_cols * n_data[b] beyond 2^60 doubles (the allocation's arithmetic). */
+int apemost_hip_create_batch_ragged(const apemost_hip_config *cfg, int32_t n_ladders, const uint64_t *seeds,
+                                    const int32_t *n_data, apemost_hip_sampler **out);
+/* The data layout of a ragged batch, on the host alone (no device, no sampler): offsets[b] = sum over b' < b of
+ * n_cols * n_data[b'] for b = 0 .. n_ladders (the last one is the whole allocation, also in *total), *n_data_max the
+ * longest length.  offsets, n_data_max and total may each be NULL.  The argument errors are those of
+ * apemost_hip_create_batch_ragged. */
+int apemost_hip_ragged_layout(int32_t n_ladders, int32_t n_cols, const int32_t *n_data, uint64_t *offsets,
+                              int32_t *n_data_max, uint64_t *total);
+/* the data rows of ladder `ladder`: n_data[ladder] of a ragged batch, cfg.n_data of an equal batch and (ladder 0) of
+ * an ordinary sampler */
+int apemost_hip_ladder_n_data(apemost_hip_sampler *s, int32_t ladder, int32_t *n_data);
 /* 1 for an ordinary sampler */
 int apemost_hip_n_ladders(apemost_hip_sampler *s, int32_t *n_ladders);
-/* row-major [n_data][n_cols] host matrix for ladder `ladder` alone (ladder 0 of an ordinary sampler: its data) */
+/* row-major [n_data][n_cols] host matrix for ladder `ladder` alone (ladder 0 of an ordinary sampler: its data); on a
+ * ragged batch n_data is that ladder's own */
 int apemost_hip_set_data_ladder(apemost_hip_sampler *s, int32_t ladder, const double *data_rowmajor);
 int apemost_hip_destroy(apemost_hip_sampler *s);
 int apemost_hip_synchronize(apemost_hip_sampler *s);
@@ -908,10 +947,15 @@ int apemost_hip_predict_get(apemost_hip_sampler *s, const apemost_hip_predict_vi
 /* loads a view saved by predict_get into a fold begun with the same configuration (a resumed run); with n > 0 the
  * next sample replaces neither the origins nor the best sample (unless its prob is larger) */
 int apemost_hip_predict_set(apemost_hip_sampler *s, const apemost_hip_predict_view *v);
+/* len[n_keep]: the abscissae kept chain k of the open fold really has -- n_x, except at the data's abscissae
+ * (x == NULL) of a ragged batch (apemost_hip_create_batch_ragged), where it is the n_data of the chain's ladder and
+ * n_x the largest of them.  Entries i >= len[k] of every [n_keep][n_x] array are never written by the fold: after
+ * predict_get they hold their initial values (origin, sum, sq 0, vmin +inf, vmax -inf, hist 0). */
+int apemost_hip_predict_lengths(apemost_hip_sampler *s, int32_t *len);
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_predict_end(apemost_hip_sampler *s);
 /* out[r][i] = the same curve for the caller's parameter rows: params host [n][n_par], x host [n_x] (NULL: column 0 of
- * the sampler's data -- of ladder 0 in a batch --, n_x = n_data), out host [n][n_x].  APEMOST_MODEL_USER: x host
+ * the sampler's data -- of ladder 0 in a batch --, n_x = n_data, on a ragged batch n_data[0]), out host [n][n_x].  APEMOST_MODEL_USER: x host
  * [n_x][n_cols], finite (NULL: the data's rows).  Synchronous; needs no predict_begin.  APEMOST_HIP_ERR_INVALID for
  * n < 1, NULL params or out, n_x < 1 or n * n_x above 2^26. */
 int apemost_hip_predict_curve(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x, const double *x,
@@ -976,6 +1020,11 @@ int apemost_hip_pointwise_get(apemost_hip_sampler *s, const apemost_hip_pointwis
 /* loads a view saved by pointwise_get into a fold begun with the same configuration (a resumed run); with n > 0 the
  * next sample replaces no origin */
 int apemost_hip_pointwise_set(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v);
+/* len[n_keep]: the data kept chain k of the open fold really has.  The fold's arrays are [n_keep][n_data] with n_data
+ * the longest data among the kept chains' ladders: the sampler's n_data, except on a ragged batch
+ * (apemost_hip_create_batch_ragged).  Entries i >= len[k] are never written by the fold: after pointwise_get they hold
+ * their initial values, 0 in all eight words. */
+int apemost_hip_pointwise_lengths(apemost_hip_sampler *s, int32_t *len);
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_pointwise_end(apemost_hip_sampler *s);
 /* out[r][i] = l_i(params[r]), the same term for the caller's parameter rows: params host [n][n_par], out host
