@@ -124,6 +124,14 @@ class PointwiseTailView(C.Structure):
     _fields_ = [("count", _up), ("values", _dp)]
 
 
+class PointwiseAt(C.Structure):
+    _fields_ = [("n_at", C.POINTER(C.c_int32)), ("x", _dp), ("y", _dp), ("joint", C.c_int32)]
+
+
+class PointwiseJointView(C.Structure):
+    _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("m", _dp), ("S", _dp)]
+
+
 class DerivedConfig(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("n_col", C.c_int32),
                 ("code", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("n_const", C.c_int32), ("consts", _dp),
@@ -184,6 +192,8 @@ EXPORTS = [
     "apemost_hip_pointwise_loglike_ladder",
     "apemost_hip_pointwise_tail_begin", "apemost_hip_pointwise_tail_get", "apemost_hip_pointwise_tail_set",
     "apemost_hip_pointwise_tail_capacity",
+    "apemost_hip_pointwise_begin_at", "apemost_hip_pointwise_joint_get", "apemost_hip_pointwise_joint_set",
+    "apemost_hip_pointwise_loglike_at",
     "apemost_hip_derived_check", "apemost_hip_derived_begin", "apemost_hip_derived_accumulate",
     "apemost_hip_derived_get", "apemost_hip_derived_set", "apemost_hip_derived_end", "apemost_hip_derived_eval",
 ]
@@ -335,6 +345,10 @@ def lib():
     L.apemost_hip_pointwise_tail_get.argtypes = [vp, C.POINTER(PointwiseTailView)]
     L.apemost_hip_pointwise_tail_set.argtypes = [vp, C.POINTER(PointwiseTailView)]
     L.apemost_hip_pointwise_tail_capacity.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.apemost_hip_pointwise_begin_at.argtypes = [vp, C.POINTER(PointwiseConfig), C.POINTER(PointwiseAt)]
+    L.apemost_hip_pointwise_joint_get.argtypes = [vp, C.POINTER(PointwiseJointView)]
+    L.apemost_hip_pointwise_joint_set.argtypes = [vp, C.POINTER(PointwiseJointView)]
+    L.apemost_hip_pointwise_loglike_at.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]
     ip = C.POINTER(C.c_int32)
     L.apemost_hip_derived_check.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int32, ip]
     L.apemost_hip_derived_begin.argtypes = [vp, C.POINTER(DerivedConfig)]

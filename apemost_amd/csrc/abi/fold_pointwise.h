@@ -1,5 +1,6 @@
 // abi/fold_pointwise.h -- on-device pointwise log-likelihood (pt_pointwise.h) and its tail (pt_pointwise_tail.h), which
-// shares the fold's state (PointwiseFold and its PointwiseTailFold; protocol: abi/fold_common.h)
+// shares the fold's state (PointwiseFold and its PointwiseTailFold; protocol: abi/fold_common.h); the fold begun at the
+// caller's data and the joint predictive of every kept chain's block (pt_pointwise_joint.h)
 #pragma once
 
 // a built-in model, or a user-supplied one with the pointwise hook
@@ -18,6 +19,7 @@
     } while (0)
 
 constexpr int kPointwiseWords = 8; // origin, sum, sq, m_up, S_up, m_dn, S_dn, S2_dn
+constexpr int kPointwiseJointWords = 5; // origin, sum, sq, m, S of a kept chain's block (pt_pointwise_joint.h)
 
 static double pointwise_c(const apemost_hip_sampler *s) {
     const double sigma = s->sh.consts.sigma;
@@ -26,24 +28,30 @@ static double pointwise_c(const apemost_hip_sampler *s) {
     return 1.0 / denom;
 }
 
-extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg) {
-    CHECK_S(s);
-    POINTWISE_HAS_TERM(s, "pointwise_begin");
-    if (!cfg)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: config is NULL");
+// What pointwise_begin and pointwise_begin_at share.  at == nullptr: every kept chain is scored on columns 0 and 1 of its
+// own ladder's data; else on the caller's, at->n_at[k] data per kept chain.  The checks of the caller's arguments have
+// been made.
+static int pointwise_open(apemost_hip_sampler *s, const char *what, const apemost_hip_pointwise_config *cfg,
+                          const apemost_hip_pointwise_at *at) {
     const int np = s->cfg.n_par;
-    FOLD_TRY(fold_check_chains(s, "pointwise", cfg->n_keep, cfg->chains));
-    // the longest data among the kept chains' ladders (a batch's ladders may differ in length: the arrays stay
-    // rectangular and every kept chain folds its own len[k] <= nd series)
+    // the longest data among the kept chains (a batch's ladders, or the caller's blocks, may differ in length: the
+    // arrays stay rectangular and every kept chain folds its own len[k] <= nd series)
     std::vector<int> len;
     bool ragged = false;
-    const int nd = kept_lengths(s, cfg->n_keep, cfg->chains, len, &ragged);
+    int nd = 0;
+    if (at) {
+        len.assign(at->n_at, at->n_at + cfg->n_keep);
+        for (int k = 0; k < cfg->n_keep; k++) {
+            nd = len[k] > nd ? len[k] : nd;
+            ragged = ragged || len[k] != len[0];
+        }
+    } else
+        nd = kept_lengths(s, cfg->n_keep, cfg->chains, len, &ragged);
     const u64 n_series = (u64)cfg->n_keep * (u64)nd;
     if (n_series > ((u64)1 << 20))
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d chains x %d data: more than 2^20 series", cfg->n_keep,
-                    nd);
+        return fail(APEMOST_HIP_ERR_INVALID, "%s: %d chains x %d data: more than 2^20 series", what, cfg->n_keep, nd);
     if (np > kPointwiseTile)
-        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: %d parameters, more than %d", np, kPointwiseTile);
+        return fail(APEMOST_HIP_ERR_INVALID, "%s: %d parameters, more than %d", what, np, kPointwiseTile);
     FOLD_TRY(fold_reset(s, s->pw));
     PointwiseFold &f = s->pw;
     f.n_keep = cfg->n_keep;
@@ -64,20 +72,65 @@ extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost
         FOLD_TRY(fold_alloc(s, f.mem, &f.d_len, nk, false));
         HIP_TRY(hipMemcpyAsync(f.d_len, len.data(), nk * sizeof(int), hipMemcpyHostToDevice, s->stream));
     }
+    if (at && at->joint) {
+        FOLD_TRY(fold_alloc(s, f.mem, &f.d_joint, kPointwiseJointWords * nk, true));
+        FOLD_TRY(fold_alloc(s, f.mem, &f.d_J, nk * kPointwisePiece, false));
+    }
+    size_t packed = 0; // where kept chain k's block starts in the caller's arrays
     for (int k = 0; k < cfg->n_keep; k++) {
+        const size_t mine = (size_t)len[k];
+        if (at) { // (a built-in model: begin_at refuses a user-supplied one)
+            HIP_TRY(hipMemcpyAsync(f.d_x + (size_t)k * nd, at->x + packed, mine * sizeof(double), hipMemcpyHostToDevice,
+                                   s->stream));
+            HIP_TRY(hipMemcpyAsync(f.d_y + (size_t)k * nd, at->y + packed, mine * sizeof(double), hipMemcpyHostToDevice,
+                                   s->stream));
+            packed += mine;
+            continue;
+        }
         // columns 0 and 1 of the kept chain's own ladder (the data is stored by columns, ladder after ladder), in
         // that ladder's own length (a user model, which no batch runs: len[k] = nd)
         const double *col0 = ladder_data(s, s->batch ? cfg->chains[k] / s->per_ladder : 0);
-        const size_t mine = (size_t)len[k];
         HIP_TRY(hipMemcpyAsync(f.d_x + (size_t)k * nc * nd, col0, nc * mine * sizeof(double), hipMemcpyDeviceToDevice,
                                s->stream));
         if (!user)
             HIP_TRY(hipMemcpyAsync(f.d_y + (size_t)k * nd, col0 + mine, mine * sizeof(double),
                                    hipMemcpyDeviceToDevice, s->stream));
     }
-    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's array is read until here)
+    HIP_TRY(hipStreamSynchronize(s->stream)); // (the caller's arrays are read until here)
     f.open = true;
     return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_begin(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg) {
+    CHECK_S(s);
+    POINTWISE_HAS_TERM(s, "pointwise_begin");
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin: config is NULL");
+    FOLD_TRY(fold_check_chains(s, "pointwise", cfg->n_keep, cfg->chains));
+    return pointwise_open(s, "pointwise_begin", cfg, nullptr);
+}
+
+// the fold begun at the caller's data: held-out data that the sampler was not fitted to
+extern "C" int apemost_hip_pointwise_begin_at(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg,
+                                              const apemost_hip_pointwise_at *at) {
+    CHECK_S(s);
+    if (s->cfg.model == APEMOST_MODEL_USER)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "pointwise_begin_at: a user-supplied device model: its datum is a whole "
+                    "row of the sampler's data and it runs in no batch; the hook on held-out rows is a follow-up");
+    if (!cfg)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin_at: config is NULL");
+    if (!at)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin_at: at is NULL");
+    FOLD_TRY(fold_check_chains(s, "pointwise", cfg->n_keep, cfg->chains));
+    if (!at->n_at || !at->x || !at->y)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin_at: at->%s is NULL", !at->n_at ? "n_at" : !at->x ? "x" : "y");
+    if (at->joint != 0 && at->joint != 1)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin_at: at->joint = %d: 0 or 1", at->joint);
+    for (int k = 0; k < cfg->n_keep; k++)
+        if (at->n_at[k] < 1)
+            return fail(APEMOST_HIP_ERR_INVALID, "pointwise_begin_at: at->n_at[%d] = %d: every kept chain is scored on at "
+                        "least one datum", k, at->n_at[k]);
+    return pointwise_open(s, "pointwise_begin_at", cfg, at);
 }
 
 // ---- the tail of the pointwise fold (pt_pointwise_tail.h) ----
@@ -129,6 +182,36 @@ static int pointwise_tail_pieces(apemost_hip_sampler *s, const PointwiseArgs &fo
     return APEMOST_HIP_OK;
 }
 
+// ---- the joint predictive of the kept chains' blocks (pt_pointwise_joint.h) ----
+static PointwiseJointArgs pointwise_joint_args(const apemost_hip_sampler *s) {
+    const PointwiseFold &f = s->pw;
+    const size_t nk = (size_t)f.n_keep;
+    PointwiseJointArgs q;
+    q.J = f.d_J;
+    q.origin = f.d_joint;
+    q.sum = f.d_joint + nk;
+    q.sq = f.d_joint + 2 * nk;
+    q.m = f.d_joint + 3 * nk;
+    q.S = f.d_joint + 4 * nk;
+    return q;
+}
+
+// the kept steps of the fold piece `fold` (already launched): J of every kept sample, then the fold of them in sample
+// order, on copy_stream (a built-in model: begin_at refuses a user-supplied one)
+static int pointwise_joint_piece(apemost_hip_sampler *s, const PointwiseArgs &fold) {
+    const PointwiseJointArgs q = pointwise_joint_args(s);
+    const unsigned int rows = (unsigned int)joint_rows(fold.n_par);
+    const dim3 grid((unsigned)fold.n_keep, (fold.n + rows - 1) / rows), block(kPointwiseWave);
+    with_builtin_model(s->cfg.model, [&](auto m) {
+        hipLaunchKernelGGL(pointwise_joint_sum_kernel<decltype(m)::value>, grid, block, 0, s->copy_stream, fold, q);
+    });
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(pointwise_joint_fold_kernel, dim3((unsigned)fold.n_keep), block, 0, s->copy_stream, q, fold.n,
+                       fold.n0 == 0 ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return APEMOST_HIP_OK;
+}
+
 extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps,
                                                 uint64_t skip, uint64_t thin) {
     CHECK_S(s);
@@ -140,6 +223,10 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
         return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: the tail was begun on a fold of %llu samples that "
                     "pointwise_set loaded: pointwise_tail_set must load the tail of those samples first",
                     (unsigned long long)f.n);
+    if (f.joint_awaits_set)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_accumulate: the fold keeps the joint predictive of its blocks and "
+                    "pointwise_set loaded %llu samples: pointwise_joint_set must load the joint state of those samples "
+                    "first", (unsigned long long)f.n);
     if (kept == 0)
         return APEMOST_HIP_OK;
     FOLD_TRY(fold_order_behind_stream(s));
@@ -186,6 +273,8 @@ extern "C" int apemost_hip_pointwise_accumulate(apemost_hip_sampler *s, const do
         HIP_TRY(hipGetLastError());
         if (f.tail.capacity > 0)
             FOLD_TRY(pointwise_tail_pieces(s, a));
+        if (f.d_joint)
+            FOLD_TRY(pointwise_joint_piece(s, a));
         f.n += a.n;
         f.n_set = false;
     }
@@ -207,7 +296,42 @@ static int pointwise_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_vi
     fold_xfer_count(f.n, v->n, up);
     if (up && v->n)
         f.n_set = true;
+    if (up && v->n && f.d_joint) // (the tail's awaits_set rule: the joint state of the loaded samples comes next)
+        f.joint_awaits_set = f.n > 0;
     return APEMOST_HIP_OK;
+}
+
+static int pointwise_joint_xfer(apemost_hip_sampler *s, const apemost_hip_pointwise_joint_view *v, bool up) {
+    CHECK_S(s);
+    PointwiseFold &f = s->pw;
+    const char *what = up ? "set" : "get";
+    if (!f.open || !f.d_joint)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_joint_%s: no pointwise_begin_at with joint = 1", what);
+    if (!v)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_joint view is NULL");
+    if (up && v->n && *v->n != f.n)
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_joint_set: the view holds %llu samples, the fold %llu: "
+                    "pointwise_set loads the fold's samples first", (unsigned long long)*v->n, (unsigned long long)f.n);
+    const size_t nk = (size_t)f.n_keep;
+    FOLD_TRY(fold_order_behind_stream(s));
+    const FoldCopy copy{s, up};
+    double *const host[kPointwiseJointWords] = {v->origin, v->sum, v->sq, v->m, v->S};
+    for (int q = 0; q < kPointwiseJointWords; q++)
+        FOLD_TRY(copy(f.d_joint + (size_t)q * nk, host[q], nk * sizeof(double)));
+    FOLD_TRY(fold_xfer_wait(s));
+    if (!up && v->n)
+        *v->n = f.n;
+    if (up)
+        f.joint_awaits_set = false;
+    return APEMOST_HIP_OK;
+}
+
+extern "C" int apemost_hip_pointwise_joint_get(apemost_hip_sampler *s, const apemost_hip_pointwise_joint_view *v) {
+    return pointwise_joint_xfer(s, v, false);
+}
+
+extern "C" int apemost_hip_pointwise_joint_set(apemost_hip_sampler *s, const apemost_hip_pointwise_joint_view *v) {
+    return pointwise_joint_xfer(s, v, true);
 }
 
 extern "C" int apemost_hip_pointwise_get(apemost_hip_sampler *s, const apemost_hip_pointwise_view *v) {
@@ -411,4 +535,42 @@ extern "C" int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int3
 
 extern "C" int apemost_hip_pointwise_loglike(apemost_hip_sampler *s, int32_t n, const double *params, double *out) {
     return apemost_hip_pointwise_loglike_ladder(s, 0, n, params, out);
+}
+
+// the term of the caller's n_x data under n parameter rows, by the fold's own function: what a fold begun with
+// pointwise_begin_at folds; no fold need be open, and nothing of the sampler's data is read
+extern "C" int apemost_hip_pointwise_loglike_at(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x,
+                                                const double *x, const double *y, double *out) {
+    CHECK_S(s);
+    if (s->cfg.model == APEMOST_MODEL_USER)
+        return fail(APEMOST_HIP_ERR_UNSUPPORTED, "pointwise_loglike_at: a user-supplied device model: its datum is a "
+                    "whole row of the sampler's data; the hook on held-out rows is a follow-up");
+    const int np = s->cfg.n_par;
+    if (n < 1 || n_x < 1 || !params || !x || !y || !out || (u64)n * (u64)n_x > ((u64)1 << 26))
+        return fail(APEMOST_HIP_ERR_INVALID, "pointwise_loglike_at: %d rows x %d data (n_x), or a NULL array among "
+                    "params, x, y and out", n, n_x);
+    FoldScratch scratch;
+    double *d_par = nullptr, *d_x = nullptr, *d_y = nullptr, *d_out = nullptr;
+    const int rc = [&]() -> int { // (whatever fails, the stream is waited for before the scratch goes)
+        FOLD_TRY(fold_alloc(s, scratch, &d_par, (size_t)n * np, false));
+        FOLD_TRY(fold_alloc(s, scratch, &d_x, (size_t)n_x, false));
+        FOLD_TRY(fold_alloc(s, scratch, &d_y, (size_t)n_x, false));
+        FOLD_TRY(fold_alloc(s, scratch, &d_out, (size_t)n * n_x, false));
+        HIP_TRY(hipMemcpyAsync(d_par, params, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)n_x * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(d_y, y, (size_t)n_x * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        const dim3 grid((unsigned)((n_x + kPointwiseWave - 1) / kPointwiseWave) * (unsigned)n), block(kPointwiseWave);
+        const double c = pointwise_c(s);
+        with_builtin_model(s->cfg.model, [&](auto m) {
+            hipLaunchKernelGGL(pointwise_loglike_kernel<decltype(m)::value>, grid, block, 0, s->stream, d_par, np,
+                               (int)n_x, (const double *)d_x, (const double *)d_y, c, d_out);
+        });
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * n_x * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        return APEMOST_HIP_OK;
+    }();
+    const hipError_t sync = hipStreamSynchronize(s->stream);
+    FOLD_TRY(rc);
+    HIP_TRY(sync);
+    return APEMOST_HIP_OK;
 }

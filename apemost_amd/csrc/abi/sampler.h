@@ -170,6 +170,10 @@ struct PointwiseFold {
     double *d_state;   // the eight [n_keep][n_data] words, one after the other (kPointwiseWords)
     double *d_par;     // par_origin, par_sum: [n_keep][n_par] each
     bool n_set;        // n is what pointwise_set put there: nothing has been accumulated since
+    // the joint predictive of every kept chain's block (pt_pointwise_joint.h; pointwise_begin_at with joint = 1)
+    double *d_joint;   // origin, sum, sq, m, S: [n_keep] each, one after the other (kPointwiseJointWords); else nullptr
+    double *d_J;       // [n_keep][kPointwisePiece]: J of a piece's kept samples
+    bool joint_awaits_set; // pointwise_set loaded samples: no accumulate before pointwise_joint_set has loaded theirs
     PointwiseTailFold tail;
     FoldMem mem;
 };

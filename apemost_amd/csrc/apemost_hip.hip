@@ -7,6 +7,7 @@
 #include "pt_kernels.h"
 #include "pt_peaks.h"
 #include "pt_pointwise.h"
+#include "pt_pointwise_joint.h"
 #include "pt_pointwise_tail.h"
 #include "pt_predict.h"
 #include "pt_user_fold.h"

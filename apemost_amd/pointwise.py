@@ -44,6 +44,12 @@ length; what it returns are ordinary Pointwise objects.  A reduction over the da
 elpd_*, waic*, looic, p_*, dic, compare, criteria, text, write) would take padding for data and raises ValueError
 instead.
 
+A fold begun at the caller's data (HipSampler.pointwise_begin(at=...), apemost_hip_pointwise_begin_at) scores the kept
+chains on data the sampler was not fitted to: the object is the same, with `heldout` set, x and y the caller's, and
+`lengths` where the kept chains' blocks differ in length.  lppd is then the held-out log predictive density of every
+datum (apemost_amd/kfold.py turns it into K-fold cross-validation); the _dn words (elpd_loo, loo_ess) are still folded
+and mean nothing there, at_mean stays NaN, and dic and p_dic raise ValueError.
+
 `loglike_numpy` states the term in plain numpy (the operation order of apemost_amd/csrc/pt_pointwise.h on
 predict.curve_numpy's curve, with numpy's sine and logarithm in place of the device's).
 
@@ -152,6 +158,9 @@ class Pointwise:
       own ladder's data); it is NaN where nobody filled it, and dic and p_dic with it."""
 
     lengths = None   # [n_keep] data per kept chain of a ragged batch's fold (see the module's docstring)
+    heldout = False  # the fold was begun at the caller's data (HipSampler.pointwise_begin(at=...)): x and y are those,
+    #                  lppd is the held-out log predictive density (apemost_amd/kfold.py), the _dn words (elpd_loo,
+    #                  loo_ess) mean nothing, and DIC has no held-out meaning: at_mean stays NaN, dic and p_dic raise
 
     def __init__(self, n, origin, sum, sq, m_up, S_up, m_dn, S_dn, S2_dn, par_origin, par_sum, chains, x, y, n_par, model,
                  sigma=0.5, thin=1, n_ladders=1, at_mean=None):
@@ -198,6 +207,11 @@ class Pointwise:
                              "use per_ladder(), which trims every ladder to its length"
                              % (what, np.asarray(self.lengths).tolist(), self.n_data))
 
+    def _not_heldout(self, what):
+        if self.heldout:
+            raise ValueError("%s of a fold begun at held-out data: DIC evaluates the data the posterior was fitted to "
+                             "and has no held-out meaning" % what)
+
     def per_ladder(self, n_ladders=None):
         """one Pointwise per ladder of a batch: the kept chains, ladder-major, in equal shares; of a ragged batch's
         fold each trimmed to its ladder's length (the kept chains of one ladder share it)"""
@@ -217,6 +231,7 @@ class Pointwise:
             out.append(Pointwise(self.n.copy(), *[getattr(self, f)[k, :m] for f in STATE], self.par_origin[k],
                                  self.par_sum[k], self.chains[k], self.x[k, :m], self.y[k, :m], self.n_par, self.model,
                                  self.sigma, self.thin, 1, self.at_mean[k, :m]))
+            out[-1].heldout = self.heldout
         return out
 
     # -- per datum ----------------------------------------------------------------------------
@@ -303,10 +318,12 @@ class Pointwise:
     def p_dic(self, k=0):
         """2 (sum l_i(mean parameters) - sum mean_loglike); needs at_mean"""
         self._no_padding("p_dic")
+        self._not_heldout("p_dic")
         return 2.0 * (_total(self.at_mean[k]) - _total(self.mean_loglike(k)))
 
     def dic(self, k=0):
         self._no_padding("dic")
+        self._not_heldout("dic")
         return -2.0 * _total(self.at_mean[k]) + 2.0 * self.p_dic(k)
 
     # -- comparing two models on the same data ------------------------------------------------

@@ -744,24 +744,48 @@ class HipSampler:
         return out[0] if one else out
 
     # -- on-device pointwise log-likelihood (apemost_amd/pointwise.py) -------------------------------
-    def pointwise_begin(self, chains=(0,), thin=1, tail=None):
+    def pointwise_begin(self, chains=(0,), thin=1, tail=None, at=None, joint=False):
         """start the fold of the pointwise log-likelihood of every datum (columns 0 and 1 of the data as they are now,
         for every kept chain those of its own ladder) over the kept samples of the local chains `chains` (strictly
         increasing).  The criteria mean what they say for a chain at beta = 1: chain 0, the default.  thin is recorded
         in the result.  tail: also keep, per kept chain and datum, the largest leave-one-out log weights
         (pointwise_tail(), apemost_amd/psis.py): a capacity (2 .. 4096), or "auto:<expected kept samples>" for
-        psis.capacity_for of that many; None keeps none."""
+        psis.capacity_for of that many; None keeps none.
+        at: score the kept chains on the caller's data instead, held-out data the sampler was not fitted to
+        (apemost_hip_pointwise_begin_at, apemost_amd/kfold.py): a list of one [n_at][2] matrix (x, y) per kept chain, or
+        one matrix for all of them.  m_up + ln(S_up / n) is then the held-out log predictive density of every datum;
+        the _dn words and DIC have no meaning there.  joint (with at): also the joint predictive density of every
+        kept chain's block (pointwise_joint())."""
         self._pw_chains = np.ascontiguousarray(chains, dtype=np.int32)
         assert self._pw_chains.ndim == 1
         self._pw_thin = int(thin)
-        lads = [int(c) // self.chains_per_ladder if self.n_ladders > 1 else 0
-                for c in self._pw_chains.tolist() if 0 <= c < self.n_chains]
-        lads = lads if len(lads) == len(self._pw_chains) else [0] * len(self._pw_chains)
-        # ([n_keep][2][n_data]; a ragged batch: every row in its own length, zeros behind it)
-        self._pw_data = np.stack([_rectangle([self._x0[b] for b in lads]), _rectangle([self._y0[b] for b in lads])], axis=1)
         cfg = capi.PointwiseConfig(n_keep=len(self._pw_chains),
                                    chains=self._pw_chains.ctypes.data_as(C.POINTER(C.c_int32)))
-        capi.check(self.L.apemost_hip_pointwise_begin(self._h, C.byref(cfg)))
+        self._pw_at = at is not None
+        self._pw_joint = bool(joint)
+        if at is None:
+            if joint:
+                raise ValueError("joint: the joint predictive of a block needs the block: pass at")
+            lads = [int(c) // self.chains_per_ladder if self.n_ladders > 1 else 0
+                    for c in self._pw_chains.tolist() if 0 <= c < self.n_chains]
+            lads = lads if len(lads) == len(self._pw_chains) else [0] * len(self._pw_chains)
+            # ([n_keep][2][n_data]; a ragged batch: every row in its own length, zeros behind it)
+            self._pw_data = np.stack([_rectangle([self._x0[b] for b in lads]), _rectangle([self._y0[b] for b in lads])],
+                                     axis=1)
+            capi.check(self.L.apemost_hip_pointwise_begin(self._h, C.byref(cfg)))
+        else:
+            mats = [at] * len(self._pw_chains) if not isinstance(at, (list, tuple)) else list(at)
+            mats = [np.ascontiguousarray(m, dtype=np.float64) for m in mats]
+            if len(mats) != len(self._pw_chains) or any(m.ndim != 2 or m.shape[1] < 2 for m in mats):
+                raise ValueError("at: one [n_at][2] matrix per kept chain (%d), or one matrix for all"
+                                 % len(self._pw_chains))
+            n_at = np.array([len(m) for m in mats], dtype=np.int32)
+            x = np.ascontiguousarray(np.concatenate([m[:, 0] for m in mats])) if mats else np.zeros(0)
+            y = np.ascontiguousarray(np.concatenate([m[:, 1] for m in mats])) if mats else np.zeros(0)
+            self._pw_data = np.stack([_rectangle([m[:, 0] for m in mats]), _rectangle([m[:, 1] for m in mats])], axis=1)
+            where = capi.PointwiseAt(n_at=n_at.ctypes.data_as(C.POINTER(C.c_int32)), x=x.ctypes.data_as(capi._dp),
+                                     y=y.ctypes.data_as(capi._dp), joint=1 if joint else 0)
+            capi.check(self.L.apemost_hip_pointwise_begin_at(self._h, C.byref(cfg), C.byref(where)))
         if tail is not None:
             self.pointwise_tail_begin(tail)
 
@@ -814,7 +838,8 @@ class HipSampler:
                              self.cfg.sigma, self._pw_thin, self.n_ladders)
         capi.check(self.L.apemost_hip_pointwise_get(self._h, C.byref(pw.view())))
         pw.lengths = self._fold_lengths(self.L.apemost_hip_pointwise_lengths, pw.n_keep, pw.n_data)
-        if at_mean and int(pw.n[0]) > 0:
+        pw.heldout = getattr(self, "_pw_at", False)   # (DIC has no held-out meaning: at_mean stays NaN, dic raises)
+        if at_mean and int(pw.n[0]) > 0 and not pw.heldout:
             if self.n_ladders == 1:
                 pw.at_mean = self.pointwise_loglike(pw.par_mean_all()).reshape(pw.n_keep, pw.n_data)
             else:
@@ -831,6 +856,40 @@ class HipSampler:
 
     def pointwise_end(self):
         capi.check(self.L.apemost_hip_pointwise_end(self._h))
+
+    def pointwise_joint(self):
+        """the joint predictive state of every kept chain's block so far, a kfold.Joint (a fold begun with at and
+        joint=True; synchronises with the accumulates issued so far)"""
+        from .kfold import Joint
+        jt = Joint.empty(self._pw_chains, self._pw_lengths(), self._pw_thin)
+        capi.check(self.L.apemost_hip_pointwise_joint_get(self._h, C.byref(jt.view())))
+        return jt
+
+    def _pw_lengths(self):
+        lens = np.zeros(len(self._pw_chains), dtype=np.int32)
+        capi.check(self.L.apemost_hip_pointwise_lengths(self._h, lens.ctypes.data_as(C.POINTER(C.c_int32))))
+        return lens
+
+    def pointwise_joint_set(self, jt):
+        """load a kfold.Joint (a resumed run) behind pointwise_set, into a fold begun with the same configuration"""
+        assert np.array_equal(jt.chains, self._pw_chains)
+        capi.check(self.L.apemost_hip_pointwise_joint_set(self._h, C.byref(jt.view())))
+
+    def pointwise_loglike_at(self, params, x, y):
+        """the pointwise log-likelihood [n][n_x] of the parameter rows params [n][n_par] (or one row) over the caller's
+        data x, y [n_x], evaluated on the device by the fold's own term: what a fold begun with `at` folds"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        one = params.ndim == 1
+        params = np.ascontiguousarray(params.reshape(-1, self.n_par))
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if len(x) != len(y):
+            raise ValueError("x holds %d values, y %d" % (len(x), len(y)))
+        out = np.zeros((len(params), len(x)))
+        capi.check(self.L.apemost_hip_pointwise_loglike_at(self._h, len(params), params.ctypes.data_as(capi._dp), len(x),
+                                                           x.ctypes.data_as(capi._dp), y.ctypes.data_as(capi._dp),
+                                                           out.ctypes.data_as(capi._dp)))
+        return out[0] if one else out
 
     def pointwise_loglike(self, params, ladder=0):
         """the pointwise log-likelihood [n][n_data] of the parameter rows params [n][n_par] (or one row) over the

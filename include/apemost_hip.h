@@ -1036,6 +1036,66 @@ int apemost_hip_pointwise_loglike(apemost_hip_sampler *s, int32_t n, const doubl
 int apemost_hip_pointwise_loglike_ladder(apemost_hip_sampler *s, int32_t ladder, int32_t n, const double *params,
                                          double *out);
 
+/* ---- the pointwise fold at the caller's data: held-out log predictive density, K-fold cross-validation ----
+ * apemost_hip_pointwise_begin_at opens the same fold over data the sampler was not fitted to: kept chain k is scored on
+ * the n_at[k] data (x, y) the caller hands in, packed kept chain after kept chain, instead of on columns 0 and 1 of its
+ * own ladder.  After the call the fold is an ordinary pointwise fold whose series are (kept chain k, caller's datum i):
+ * accumulate, get, set, lengths and end, the eight words, the limits (n_keep * max n_at <= 2^20 series, at most 512
+ * parameters) and every rule are those above, and n_data of the fold is max n_at.  Where the lengths differ, the fold is
+ * that of a ragged batch: series past n_at[k] keep their initial zeros and apemost_hip_pointwise_lengths reports n_at.
+ * x and y are copied at begin; nothing of the sampler's data is read afterwards, and a later set_data moves nothing.
+ *   m_up + ln(S_up / n)   is the log predictive density of held-out datum i under kept chain k's posterior, the elpd_i
+ *                         of K-fold cross-validation where kept chain k was fitted without datum i;
+ *   the _dn words         are still folded (the kernel is the same) and have no cross-validation meaning: leaving out a
+ *                         datum that was never in is no estimate of anything.  apemost_amd/kfold.py ignores them.
+ * The typical use is a ragged ladder batch (apemost_hip_create_batch_ragged) whose ladder b was fitted to the training
+ * set of fold b, with chain 0 of every ladder (beta = 1) kept and scored on the block that ladder b left out
+ * (apemost_amd/kfold.py).
+ * The tail (apemost_hip_pointwise_tail_begin) keeps its own rule: allowed where all n_at are equal, refused where they
+ * differ.  APEMOST_MODEL_USER: APEMOST_HIP_ERR_UNSUPPORTED -- a user model's datum is a whole row and it runs in no
+ * batch; the hook on held-out rows is a follow-up.
+ *
+ * joint = 1: also the joint predictive density of every kept chain's block (apemost_amd/csrc/pt_pointwise_joint.h, new
+ * kernels behind each piece of the fold on the same stream; the fold's own words are bitwise what they are without).
+ * Per kept sample t of kept chain k, J_t = the sum of the block's L = n_at[k] terms in a fixed order: lane partial
+ * p[j], j = 0 .. 63, starts at +0.0 and adds l_i for i = j, j + 64, ... < L ascending; the 64 partials are combined by
+ * the adjacent-pairs tree p = p[0::2] + p[1::2] taken six times.  J_t depends on L and the terms and on nothing else.
+ * Five words per kept chain, each a sequential loop in sample order whatever the calls' boundaries:
+ *   origin[k]             J of the first sample ever;
+ *   sum[k], sq[k]         with d = J - origin the sums of d and of d * d (the product rounded, then added);
+ *   m[k], S[k]            the running log-sum-exp of J, the recurrence of the evidence fold:
+ *                         ln mean_t exp(J_t) = m + ln(S / n) is the log predictive density of the block as a whole.
+ * It is not the sum of the block's pointwise densities.  No filter: a non-finite term does what IEEE arithmetic does,
+ * to its own kept chain's words only.  Device memory: 8192 doubles (64 KiB) of scratch per kept chain. */
+typedef struct {
+    const int32_t *n_at;  /* host [n_keep]: data that kept chain k is scored on, each >= 1 */
+    const double *x, *y;  /* host, packed kept chain after kept chain: n_at[0] values, then n_at[1], ... */
+    int32_t joint;        /* 1: also fold the joint predictive of each kept chain's block */
+} apemost_hip_pointwise_at;
+typedef struct {
+    uint64_t *n;          /* kept samples: the fold's */
+    double *origin, *sum, *sq, *m, *S; /* [n_keep] */
+} apemost_hip_pointwise_joint_view; /* host arrays; any pointer may be NULL (that part is skipped) */
+/* apemost_hip_pointwise_begin with the caller's data.  A fold begun before (and its tail and joint state) is dropped
+ * once the new configuration has been accepted; a begin that is refused leaves it as it was.  APEMOST_HIP_ERR_INVALID,
+ * before any device work and with a message that names the argument: what pointwise_begin refuses, a NULL at, a NULL
+ * n_at, x or y, n_at[k] < 1, joint other than 0 or 1. */
+int apemost_hip_pointwise_begin_at(apemost_hip_sampler *s, const apemost_hip_pointwise_config *cfg,
+                                   const apemost_hip_pointwise_at *at);
+/* copies the joint state out (synchronises with the accumulates issued so far) / loads it into a fold begun with the
+ * same configuration (a resumed run).  After a pointwise_set that loaded samples, apemost_hip_pointwise_accumulate returns
+ * APEMOST_HIP_ERR_INVALID until pointwise_joint_set has loaded the joint state of those samples; a view whose n differs
+ * from the fold's is refused.  APEMOST_HIP_ERR_INVALID for a fold without joint = 1.  pointwise_begin, pointwise_begin_at
+ * and pointwise_end drop the joint state. */
+int apemost_hip_pointwise_joint_get(apemost_hip_sampler *s, const apemost_hip_pointwise_joint_view *v);
+int apemost_hip_pointwise_joint_set(apemost_hip_sampler *s, const apemost_hip_pointwise_joint_view *v);
+/* out[r][i] = l_i(params[r]) over the caller's data: params host [n][n_par], x and y host [n_x], out host [n][n_x]: the
+ * term a fold begun with pointwise_begin_at folds, by the same device function.  Synchronous; needs no fold and reads
+ * nothing of the sampler's data.  APEMOST_HIP_ERR_INVALID for n < 1, n_x < 1, a NULL array, or n * n_x above 2^26;
+ * APEMOST_HIP_ERR_UNSUPPORTED for APEMOST_MODEL_USER. */
+int apemost_hip_pointwise_loglike_at(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x,
+                                     const double *x, const double *y, double *out);
+
 /* ---- the tail of a pointwise fold (pt_pointwise_tail.h): what Pareto-smoothed leave-one-out needs ----
  * Per series s = (kept chain k, datum i) the `capacity` largest values of x = -l over the kept samples, exactly, where l
  * is the fold's own term of the same row (the same device function, so the same bits).  The order is the total order of
