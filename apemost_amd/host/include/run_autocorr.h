@@ -54,15 +54,4 @@ double run_autocorr_tau_geyer(const run_autocorr *r, const double *acov, long *w
 /* names: of the n_par parameters */
 void run_autocorr_write_text(const char *path, const run_autocorr *r, const char **names);
 
-#ifndef RUN_AUTOCORR_STANDALONE
-#include "apemost_hip.h"
-#include "mcmc.h"
-/* begins the fold of local chain 0 of shard `s`: all parameters and prob - prior, max_lag from APEMOST_AUTOCORR_LAGS.
- * With `append` autocorr.bin is loaded and the fold goes on from it; a file of another shape, max_lag or thin ends the
- * program. */
-void run_autocorr_open(run_autocorr *r, apemost_hip_sampler *s, const mcmc *chain0, uint64_t thin, int append);
-/* collects the accumulator, writes autocorr.bin and autocorr.txt, and frees everything */
-void run_autocorr_close(run_autocorr *r, apemost_hip_sampler *s, const mcmc *chain0);
-#endif
-
 #endif

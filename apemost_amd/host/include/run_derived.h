@@ -19,7 +19,6 @@
 #include <stdint.h>
 
 #include "apemost_hip.h"
-#include "mcmc.h"
 
 #define RUN_DERIVED_FILE "derived.bin"
 #define RUN_DERIVED_SPEC "derived"
@@ -57,14 +56,5 @@ int run_derived_read(const char *path, run_derived *r);
 void run_derived_write(const char *path, const run_derived *r);
 /* derived.txt and one <name>.histogram per column, in the working directory */
 void run_derived_write_text(const run_derived *r);
-
-/* reads and checks the derived file (a bad line ends the program with its number), then begins the fold of local chain 0
- * of shard `s` for `planned` more kept samples: `nbins` bins, batches of floor(sqrt(planned)).  With `append`
- * derived.bin is loaded and the accumulation goes on from it with its own batch size; a file of other columns, ranges,
- * nbins or thin ends the program with the messages a summary.bin of another shape gets. */
-void run_derived_open(run_derived *r, apemost_hip_sampler *s, const mcmc *chain0, unsigned int nbins, uint64_t planned,
-                      uint64_t thin, int append);
-/* collects the accumulator, writes derived.bin, derived.txt and the .histogram files, and frees everything */
-void run_derived_close(run_derived *r, apemost_hip_sampler *s);
 
 #endif

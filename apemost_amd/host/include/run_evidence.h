@@ -21,10 +21,6 @@
 #define RUN_EVIDENCE_H
 #include <stdint.h>
 
-#include "apemost_bridge.h"
-#include "apemost_hip.h"
-#include "mcmc.h"
-
 #define RUN_EVIDENCE_FILE "evidence.bin"
 #define RUN_EVIDENCE_TEXT "evidence.txt"
 
@@ -37,14 +33,13 @@ typedef struct {
     double *batch;                       /* [n_chains][max_batches + 1] */
 } run_evidence;
 
-/* begins one fold per shard of the ladder (shard j holds chains [lo[j], lo[j+1])), the coefficients sliced from the
- * whole ladder's betas, which must be positive and strictly decreasing.  `planned` kept samples are still to come; the
- * batch size is floor(sqrt(planned)).  With `append` evidence.bin is loaded and the fold goes on from it with its own
- * batch size; a file of another shape, thin or ladder ends the program with the messages a summary.bin of another
- * shape gets. */
-void run_evidence_open(run_evidence *r, apemost_ladder *l, mcmc **chains, const unsigned int *lo, unsigned int n_shards,
-                       uint64_t planned, uint64_t thin, int append);
-/* collects the shards' accumulators, writes evidence.bin and evidence.txt, and frees everything */
-void run_evidence_close(run_evidence *r, apemost_ladder *l, const unsigned int *lo, unsigned int n_shards);
+/* allocates the arrays of a state whose n_chains and max_batches are set; everything zero */
+void run_evidence_alloc(run_evidence *r);
+void run_evidence_free(run_evidence *r);
+/* 0: read; -1: no such file.  *n_ladders receives the ladders the file holds.  Another magic or version, a batch
+ * size that does not fit or a truncated file ends the program. */
+int run_evidence_read(const char *path, run_evidence *r, uint32_t *n_ladders);
+void run_evidence_write(const char *path, const run_evidence *r);
+void run_evidence_write_text(const char *path, const run_evidence *r);
 
 #endif

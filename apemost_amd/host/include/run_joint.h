@@ -20,9 +20,6 @@
 #define RUN_JOINT_H
 #include <stdint.h>
 
-#include "apemost_hip.h"
-#include "mcmc.h"
-
 #define RUN_JOINT_FILE "joint.bin"
 
 typedef struct {
@@ -35,12 +32,16 @@ typedef struct {
     uint64_t *counts;         /* [n_pairs][nbins][nbins] */
 } run_joint;
 
-/* begins the joint marginals of local chain 0 of shard `s`: all pairs, `nbins` bins, the prior box of `chain0`.  With
- * `append` joint.bin is loaded and the accumulation goes on from it; a file of another shape, nbins, thin or range
- * ends the program with the messages a summary.bin of another shape gets. */
-void run_joint_open(run_joint *r, apemost_hip_sampler *s, const mcmc *chain0, unsigned int nbins, uint64_t thin,
-                    int append);
-/* collects the accumulator, writes joint.bin, the .joint files and correlation.matrix, and frees everything */
-void run_joint_close(run_joint *r, apemost_hip_sampler *s, const mcmc *chain0);
+/* allocates the arrays of a state whose n_par, nbins and n_pairs are set; everything zero */
+void run_joint_alloc(run_joint *r);
+void run_joint_free(run_joint *r);
+/* 0: read; -1: no such file.  *n_keep and *chain receive the kept chains and the first of them; a file of another
+ * n_keep or of sizes out of range is left unallocated for the caller to refuse by its shape.  Another magic, version
+ * or a truncated file ends the program. */
+int run_joint_read(const char *path, run_joint *r, uint32_t *n_keep, int32_t *chain);
+void run_joint_write(const char *path, const run_joint *r);
+/* <names[a]>-<names[b]>.joint of pair q, and correlation.matrix, in the working directory */
+void run_joint_write_pair(const run_joint *r, unsigned int q, const char **names);
+void run_joint_write_correlation(const run_joint *r);
 
 #endif

@@ -88,20 +88,4 @@ int run_pointwise_tail_read(const char *path, run_pointwise_tail *t);
 /* the slots at and behind count are written as 0 */
 void run_pointwise_tail_write(const char *path, const run_pointwise_tail *t);
 
-#ifndef RUN_POINTWISE_STANDALONE
-#include "apemost_hip.h"
-#include "mcmc.h"
-/* begins the fold of local chain 0 of shard `s` over its data.  With `append` pointwise.bin is loaded and the fold
- * goes on from it; a file of another shape, data, sigma or thin ends the program.  APEMOST_POINTWISE_TAIL begins the
- * tail as well (`planned` kept samples size it under auto); with `append` pointwise_tail.bin is loaded, and one of
- * another shape, capacity or sample count than pointwise.bin's ends the program. */
-void run_pointwise_open(run_pointwise *r, apemost_hip_sampler *s, const mcmc *chain0, int model, double sigma,
-                        uint64_t thin, int append, uint64_t planned);
-/* APEMOST_POINTWISE_TAIL: 0 unset, -1 auto, else the capacity; a malformed value ends the program */
-int run_pointwise_tail_from_env(void);
-/* collects the accumulator, evaluates the term at the mean parameters on the device, writes the three files, and
- * frees everything */
-void run_pointwise_close(run_pointwise *r, apemost_hip_sampler *s);
-#endif
-
 #endif

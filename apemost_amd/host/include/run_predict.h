@@ -56,16 +56,4 @@ double run_predict_quantile(const run_predict *r, const double *edges, uint32_t 
 /* y: data column 1, best: the best-fit curve, [n_x] each */
 void run_predict_write_text(const char *path, const run_predict *r, const double *y, const double *best);
 
-#ifndef RUN_PREDICT_STANDALONE
-#include "apemost_hip.h"
-#include "mcmc.h"
-/* begins the fold of local chain 0 of shard `s` over column 0 of its data; histograms when APEMOST_PREDICT_BINS and
- * APEMOST_PREDICT_RANGE are both set.  With `append` predict.bin is loaded and the fold goes on from it; a file of
- * another shape, range or thin ends the program. */
-void run_predict_open(run_predict *r, apemost_hip_sampler *s, const mcmc *chain0, int model, uint64_t thin, int append);
-/* collects the accumulator, evaluates the best-fit curve on the device, writes predict.bin and predict.txt, and frees
- * everything */
-void run_predict_close(run_predict *r, apemost_hip_sampler *s, const mcmc *chain0);
-#endif
-
 #endif

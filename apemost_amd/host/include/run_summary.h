@@ -21,16 +21,11 @@ typedef struct {
     double *batch_sums;    /* [n_hist][n_par][max_batches + 1] */
 } run_summary;
 
-/* 1 when the comma separated list in APEMOST_DUMP holds the token `summary` */
-int run_summary_requested(void);
 /* allocates the arrays of a summary whose sizes are set */
 void run_summary_alloc(run_summary *r);
 void run_summary_free(run_summary *r);
 /* 0 and *r filled, or -1 when the file does not exist; a malformed file ends the program */
 int run_summary_read(const char *path, run_summary *r);
 void run_summary_write(const char *path, const run_summary *r);
-/* batches batch_means_error() has closed after n samples (sample n, counted from 1, closes one when
- * n % bs == bs - 1) */
-uint64_t run_summary_batches(uint64_t n, uint64_t bs);
 
 #endif

@@ -12,6 +12,7 @@
 #include "parallel_tempering_config.h"
 #include "utils.h"
 #include "debug.h"
+#include "run_fold.h"
 #include "run_summary.h"
 #include "histogram.h"
 
@@ -44,7 +45,7 @@ void analyse_data_probability() {
     double logprob = 0, previous_beta = 0;
     unsigned int i, j;
     run_summary summary;
-    const int from_summary = run_summary_requested();
+    const int from_summary = run_dump_requested("summary");
     read_calibration_file(chains, n_beta);
     if (from_summary)
         read_summary_or_die(&summary, n_beta, get_n_par(chains[0]));
@@ -209,7 +210,7 @@ void analyse_marginal_distributions() {
     unsigned int i;
     FILE *plot;
     run_summary summary;
-    const int from_summary = run_summary_requested();
+    const int from_summary = run_dump_requested("summary");
     read_calibration_file(chains, n_beta);
 #ifdef HISTOGRAMS_MINMAX
     find_minmax = 1;

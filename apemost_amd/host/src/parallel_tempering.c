@@ -12,14 +12,8 @@
 #include "parallel_tempering_config.h"
 #include "parallel_tempering_run.h"
 #include "apemost_bridge.h"
-#include "run_autocorr.h"
-#include "run_predict.h"
-#include "run_pointwise.h"
-#include "run_evidence.h"
-#include "run_derived.h"
-#include "run_joint.h"
-#include "run_peaks.h"
-#include "run_summary.h"
+#include "run_fold.h"
+#include "run_io.h"
 #include "debug.h"
 #include "define_defaults.h"
 #include "gsl_helper.h"
@@ -212,7 +206,7 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            with text or binary[:all] those are written as well
  *   peaks    keep chain 0's parameter columns on the device and write one <paramname>.peaks per parameter at the
  *            end: the output of the reference's `peaks.exe min max <name>-chain-0.prob.dump` over the prior box
- *            (run_peaks.h).  Combines with every other token and writes no sample file by itself, like summary
+ *            (run_peaks.c).  Combines with every other token and writes no sample file by itself, like summary
  *   joint    fold chain 0's rows on the device into one NBINS x NBINS histogram per pair of parameters over the prior
  *            box, on the bins of the marginal histograms, and into the moments of the parameter covariance; at the end
  *            write joint.bin, one <a>-<b>.joint per pair and correlation.matrix (run_joint.h).  Combines with every
@@ -262,16 +256,8 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
 
 typedef struct {
     int binary;               /* 0 text, 1 binary, 2 binary with every chain's parameters */
-    int summary;              /* summary.bin from the device (APEMOST_DUMP token `summary`) */
-    int peaks;                /* <paramname>.peaks from the device (APEMOST_DUMP token `peaks`) */
-    int derived;              /* derived.bin, derived.txt and the columns' histograms from the device (token `derived`) */
-    int joint;                /* joint.bin and the pair files from the device (APEMOST_DUMP token `joint`) */
-    int evidence;             /* evidence.bin and evidence.txt from the device (APEMOST_DUMP token `evidence`) */
-    int autocorr;             /* autocorr.bin and autocorr.txt from the device (APEMOST_DUMP token `autocorr`) */
-    int predict;              /* predict.bin and predict.txt from the device (APEMOST_DUMP token `predict`) */
-    int pointwise;            /* pointwise.bin, pointwise.txt and criteria.txt from the device (token `pointwise`) */
-    int files;                /* sample files are written (not so for `summary`, `peaks`, `joint`, `evidence`, `autocorr`,
-                                 `predict` and `pointwise` alone) */
+    unsigned int folds;       /* the requested folds, bit k: run_folds[k] (run_fold.h) */
+    int files;                /* sample files are written (not so for fold tokens alone) */
     unsigned int n_param_chains; /* chains 0..n-1 have parameter files (text) / carry their parameter vectors (binary) */
     double *pack;             /* binary: one batch, packed */
     size_t pack_capacity;
@@ -285,18 +271,11 @@ typedef struct {
 
 static void sink_parse(sample_sink *k) {
     const char *spec = getenv("APEMOST_DUMP");
-    int format_given = 0;
+    int format_given = 0, fold;
     k->binary = 0;
     k->thin = 1;
-    k->summary = 0;
-    k->peaks = 0;
-    k->joint = 0;
-    k->derived = 0;
-    k->evidence = 0;
-    k->autocorr = 0;
-    k->predict = 0;
-    k->pointwise = 0;
-    while (spec != NULL && *spec != 0) {
+    k->folds = 0;
+    for (; spec != NULL && *spec != 0; spec = run_dump_next(spec)) {
         if (strncmp(spec, "binary:all", 10) == 0)
             k->binary = 2, format_given = 1;
         else if (strncmp(spec, "binary", 6) == 0)
@@ -305,52 +284,15 @@ static void sink_parse(sample_sink *k) {
             k->binary = 0, format_given = 1;
         else if (strncmp(spec, "thin:", 5) == 0 && atol(spec + 5) > 0)
             k->thin = (unsigned long)atol(spec + 5);
-        else if (strncmp(spec, "summary", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
-            k->summary = 1;
-        else if (strncmp(spec, "peaks", 5) == 0 && (spec[5] == 0 || spec[5] == ','))
-            k->peaks = 1;
-        else if (strncmp(spec, "joint", 5) == 0 && (spec[5] == 0 || spec[5] == ','))
-            k->joint = 1;
-        else if (strncmp(spec, "derived", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
-            k->derived = 1;
-        else if (strncmp(spec, "evidence", 8) == 0 && (spec[8] == 0 || spec[8] == ','))
-            k->evidence = 1;
-        else if (strncmp(spec, "autocorr", 8) == 0 && (spec[8] == 0 || spec[8] == ','))
-            k->autocorr = 1;
-        else if (strncmp(spec, "predict", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
-            k->predict = 1;
-        else if (strncmp(spec, "pointwise", 9) == 0 && (spec[9] == 0 || spec[9] == ','))
-            k->pointwise = 1;
+        else if ((fold = run_fold_find(spec)) >= 0)
+            k->folds |= 1u << fold;
         else {
             fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived; got '%s'\n", spec);
             exit(1);
         }
-        spec = strchr(spec, ',');
-        if (spec != NULL)
-            spec++;
     }
-    k->files = !(k->summary || k->peaks || k->joint || k->evidence || k->autocorr || k->predict || k->pointwise ||
-                 k->derived) ||
-               format_given;
-    if (k->pointwise) /* a malformed APEMOST_POINTWISE_TAIL ends the program here, before any file is opened */
-        (void)run_pointwise_tail_from_env();
-#ifdef HISTOGRAMS_MINMAX
-    if (k->summary) {
-        fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "
-                        "would have to be known before the first sample\n");
-        exit(1);
-    }
-#endif
-}
-
-static FILE *open_or_die(const char *name, const char *mode) {
-    FILE *f = fopen(name, mode);
-    if (f == NULL) {
-        fprintf(stderr, "opening file %s failed\n", name);
-        perror("opening file failed");
-        exit(1);
-    }
-    return f;
+    k->files = k->folds == 0 || format_given;
+    run_folds_check(k->folds); /* what a fold refuses ends the program here, before any file is opened */
 }
 
 static void sink_open(sample_sink *k, mcmc **chains, unsigned int n_beta, unsigned int n_par, unsigned int n_swap,
@@ -383,7 +325,7 @@ static void sink_open(sample_sink *k, mcmc **chains, unsigned int n_beta, unsign
         u32b = k->n_param_chains;
         if (probe != NULL)
             fclose(probe);
-        k->bin = open_or_die("samples.bin", fresh ? "wb" : "ab");
+        k->bin = run_open_or_die("samples.bin", fresh ? "wb" : "ab");
         if (fresh) {
             memset(header, 0, sizeof header);
             memcpy(header, SINK_MAGIC, 8);
@@ -402,18 +344,16 @@ static void sink_open(sample_sink *k, mcmc **chains, unsigned int n_beta, unsign
         k->prob_files = (FILE **)mem_calloc(n_beta, sizeof(FILE *));
         for (i = 0; i < n_beta; i++) {
             sprintf(name, "prob-chain%d.dump", i);
-            k->prob_files[i] = open_or_die(name, mode);
+            k->prob_files[i] = run_open_or_die(name, mode);
         }
     }
 }
 
-/* the binary sink, rows of iterations first+1 .. first+n_steps of a sharded ladder.  The rows arrive per
+/* the binary sink, the n_steps rows of a batch of a sharded ladder, `skip` its first kept step.  The rows arrive per
  * shard: h[j] = [n_steps][chains of shard j][n_par+2], shard j holding chains [lo[j], lo[j+1]) */
 static void sink_write(sample_sink *k, double *const *h, const unsigned int *lo, unsigned int n_shards,
-                       unsigned long first, unsigned long n_steps) {
+                       unsigned long skip, unsigned long n_steps) {
     const unsigned int n_par = k->n_par;
-    /* first kept step of this batch: iteration numbers count from 1 */
-    const unsigned long skip = (k->thin - (first % k->thin) - 1) % k->thin;
     /* one record per kept iteration: params of chains 0..n_param_chains-1, then (prob, prob - prior)
      * of every chain; packed for the whole batch, written with one call */
     const size_t record = (size_t)k->n_param_chains * n_par + 2 * (size_t)k->n_beta;
@@ -482,7 +422,7 @@ static void sink_write_text(sample_sink *k, mcmc **chains, char *const *text, ui
             FILE *pf = k->prob_files ? k->prob_files[i] : NULL;
             if (pf == NULL) {
                 sprintf(name, "prob-chain%d.dump", i);
-                pf = open_or_die(name, k->batches == 0 ? k->mode : "a");
+                pf = run_open_or_die(name, k->batches == 0 ? k->mode : "a");
             }
             fwrite(text[j] + off[s], 1, off[s + 1] - off[s], pf);
             if (k->prob_files == NULL)
@@ -511,110 +451,6 @@ static void sink_close(sample_sink *k) {
             fclose(k->prob_files[i]);
         mem_free(k->prob_files);
     }
-}
-
-/* the kept samples a bounded run will produce from iteration `iter` on; an unbounded run ends the program */
-static uint64_t planned_samples(const char *token, const char *why, unsigned int n_swap, unsigned long iter,
-                                unsigned long max_iterations, unsigned long thin) {
-    unsigned long end = iter;
-    if (max_iterations == 0) {
-        fprintf(stderr, "APEMOST_DUMP=%s needs a bounded run (MAX_ITERATIONS > 0): %s\n", token, why);
-        exit(1);
-    }
-    if (end < max_iterations) /* whole rounds: the last one may run past max_iterations */
-        end += (max_iterations - iter + n_swap - 1) / n_swap * n_swap;
-    return end / thin - iter / thin; /* iterations thin, 2 thin, ... are kept */
-}
-
-/* APEMOST_DUMP=summary: one device summary per shard (chain 0's histograms on shard 0).  The batch size
- * of the error estimate is floor(sqrt(samples planned)); --append loads summary.bin and keeps its own. */
-static void summary_open(run_summary *r, apemost_ladder *l, mcmc **chains, const unsigned int *lo,
-                         unsigned int n_shards, unsigned int n_swap, unsigned long iter, unsigned long max_iterations,
-                         unsigned long thin, const char *mode) {
-    const unsigned int n_beta = lo[n_shards], n_par = get_n_par(chains[0]);
-    uint64_t planned, b;
-    run_summary old;
-    int resumed = 0;
-    unsigned int j, p;
-    planned = planned_samples("summary", "the batch size of the error estimate is fixed before the first sample", n_swap,
-                              iter, max_iterations, thin);
-    memset(&old, 0, sizeof old);
-    if (mode[0] == 'a' && run_summary_read(RUN_SUMMARY_FILE, &old) == 0) {
-        if (old.n_beta != n_beta || old.n_par != n_par || old.nbins != NBINS || old.thin != thin || old.n_hist != 1) {
-            fprintf(stderr, "%s: written by a run of another shape (chains, parameters, NBINS or thin:N); "
-                            "cannot append\n", RUN_SUMMARY_FILE);
-            exit(1);
-        }
-        resumed = 1;
-    } else if (mode[0] == 'a')
-        fprintf(stderr, "--append: no %s, the summary starts with this run\n", RUN_SUMMARY_FILE);
-    r->n_beta = n_beta;
-    r->n_par = n_par;
-    r->nbins = NBINS;
-    r->n_hist = 1;
-    r->thin = thin;
-    r->n = resumed ? old.n : 0;
-    r->bs = resumed ? old.bs : (uint64_t)sqrt((double)planned);
-    if (r->bs < 1)
-        r->bs = 1;
-    r->max_batches = run_summary_batches(r->n + planned, r->bs);
-    run_summary_alloc(r);
-    for (p = 0; p < n_par; p++) {
-        r->lo[p] = get_params_min_for(chains[0], p);
-        r->hi[p] = get_params_max_for(chains[0], p);
-        if (resumed && (old.lo[p] != r->lo[p] || old.hi[p] != r->hi[p])) {
-            fprintf(stderr, "%s: parameter %u had the range [%g, %g], now [%g, %g]; cannot append\n",
-                    RUN_SUMMARY_FILE, p, old.lo[p], old.hi[p], r->lo[p], r->hi[p]);
-            exit(1);
-        }
-    }
-    if (resumed) {
-        memcpy(r->prob_sum, old.prob_sum, n_beta * sizeof(double));
-        memcpy(r->hist, old.hist, (size_t)n_par * NBINS * sizeof(uint64_t));
-        for (p = 0; p < n_par; p++) /* closed batches and the open one, at the new capacity's stride */
-            for (b = 0; b <= old.n_batches; b++)
-                r->batch_sums[p * (r->max_batches + 1) + b] = old.batch_sums[p * (old.max_batches + 1) + b];
-        run_summary_free(&old);
-    }
-    r->n_batches = run_summary_batches(r->n, r->bs);
-    for (j = 0; j < n_shards; j++) {
-        apemost_hip_sampler *s = apemost_ladder_shard(l, j);
-        apemost_hip_summary_config c;
-        apemost_hip_summary_view v;
-        c.n_hist_chains = j == 0 ? 1 : 0;
-        c.nbins = NBINS;
-        c.batch_size = r->bs;
-        c.max_batches = r->max_batches;
-        c.lo = r->lo;
-        c.hi = r->hi;
-        apemost_hip_or_die(apemost_hip_summary_begin(s, &c), "summary_begin");
-        if (resumed) {
-            v.n = &r->n;
-            v.prob_sum = r->prob_sum + lo[j];
-            v.hist = j == 0 ? r->hist : NULL;
-            v.batch_sums = j == 0 ? r->batch_sums : NULL;
-            v.n_batches = NULL;
-            apemost_hip_or_die(apemost_hip_summary_set(s, &v), "summary_set");
-        }
-    }
-}
-
-/* collects the shards' summaries into summary.bin */
-static void summary_close(run_summary *r, apemost_ladder *l, const unsigned int *lo, unsigned int n_shards) {
-    unsigned int j;
-    for (j = 0; j < n_shards; j++) {
-        apemost_hip_sampler *s = apemost_ladder_shard(l, j);
-        apemost_hip_summary_view v;
-        v.n = &r->n;
-        v.prob_sum = r->prob_sum + lo[j];
-        v.hist = j == 0 ? r->hist : NULL;
-        v.batch_sums = j == 0 ? r->batch_sums : NULL;
-        v.n_batches = j == 0 ? &r->n_batches : NULL;
-        apemost_hip_or_die(apemost_hip_summary_get(s, &v), "summary_get");
-        apemost_hip_or_die(apemost_hip_summary_end(s), "summary_end");
-    }
-    run_summary_write(RUN_SUMMARY_FILE, r);
-    run_summary_free(r);
 }
 
 /* The sampler loop.  The device runs batches of rounds (apemost_hip_run: n_swap steps per chain,
@@ -646,13 +482,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
     uint64_t text_streams[APEMOST_MAX_SHARDS], text_bytes[APEMOST_MAX_SHARDS], text_scratch[APEMOST_MAX_SHARDS];
     unsigned int lo[APEMOST_MAX_SHARDS + 1], n_shards, i, j;
     int k = 0, device_pack, rows_on_host, text_sink;
-    run_summary summary;
-    run_joint joint;
-    run_derived derived;
-    run_evidence evidence;
-    run_autocorr autocorr;
-    run_predict predict;
-    run_pointwise pointwise;
+    run_fold_ctx folds;
 
     if (max_rounds < 1)
         max_rounds = 1;
@@ -668,7 +498,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         fprintf(acceptance_file, "\n");
         fclose(acceptance_file);
     }
-    acceptance_file = open_or_die("acceptance_rate.dump", mode);
+    acceptance_file = run_open_or_die("acceptance_rate.dump", mode);
 
     l = apemost_ladder_open(chains, n_beta);
     n_shards = apemost_ladder_shards(l);
@@ -691,7 +521,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
             const size_t n_local = lo[j + 1] - lo[j];
             void *p = NULL;
             apemost_hip_or_die(apemost_hip_samples_alloc(s, max_rounds * n_swap, &d_samples[i][j]), "samples_alloc");
-            p = NULL; /* (the text sink and a summary alone bring no rows to the host) */
+            p = NULL; /* (the text sink and the folds alone bring no rows to the host) */
             if (device_pack || rows_on_host)
                 apemost_hip_or_die(apemost_hip_host_alloc(max_rounds * n_swap * n_local * (n_par + 2) * sizeof(double), &p),
                                    "host_alloc");
@@ -710,41 +540,19 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
                 h_offsets[i][j] = (uint64_t *)p;
             }
         }
-    memset(&summary, 0, sizeof summary);
-    if (sink.summary)
-        summary_open(&summary, l, chains, lo, n_shards, n_swap, iter, max_iterations, sink.thin, mode);
-    if (sink.peaks) /* chain 0 lives on shard 0 */
-        run_peaks_open(apemost_ladder_shard(l, 0), chains[0],
-                       planned_samples("peaks", "the columns kept on the device are sized before the first sample", n_swap,
-                                       iter, max_iterations, sink.thin),
-                       mode[0] == 'a');
-    if (sink.joint) /* chain 0 lives on shard 0 */
-        run_joint_open(&joint, apemost_ladder_shard(l, 0), chains[0], NBINS, sink.thin, mode[0] == 'a');
-    if (sink.derived) /* chain 0 lives on shard 0; a bad line of the derived file ends the program here */
-        run_derived_open(&derived, apemost_ladder_shard(l, 0), chains[0], NBINS,
-                         planned_samples("derived", "the batch size of the error estimate is fixed before the first sample",
-                                         n_swap, iter, max_iterations, sink.thin),
-                         sink.thin, mode[0] == 'a');
-    if (sink.evidence) /* every chain: one fold per shard */
-        run_evidence_open(&evidence, l, chains, lo, n_shards,
-                          planned_samples("evidence", "the batch size of the error estimate is fixed before the first sample",
-                                          n_swap, iter, max_iterations, sink.thin),
-                          sink.thin, mode[0] == 'a');
-    if (sink.autocorr) /* chain 0 lives on shard 0 */
-        run_autocorr_open(&autocorr, apemost_ladder_shard(l, 0), chains[0], sink.thin, mode[0] == 'a');
-    if (sink.predict) { /* chain 0 lives on shard 0 */
-        (void)planned_samples("predict", "predict.bin and predict.txt are written when the run ends", n_swap, iter,
-                              max_iterations, sink.thin);
-        run_predict_open(&predict, apemost_ladder_shard(l, 0), chains[0], apemost_ladder_model(l), sink.thin,
-                         mode[0] == 'a');
-    }
-    if (sink.pointwise) { /* chain 0 lives on shard 0 */
-        const uint64_t planned =
-            planned_samples("pointwise", "pointwise.bin, pointwise.txt and criteria.txt are written when the run ends",
-                            n_swap, iter, max_iterations, sink.thin);
-        run_pointwise_open(&pointwise, apemost_ladder_shard(l, 0), chains[0], apemost_ladder_model(l),
-                           apemost_ladder_sigma(l), sink.thin, mode[0] == 'a', planned);
-    }
+    folds.l = l;
+    folds.chains = chains;
+    folds.lo = lo;
+    folds.n_shards = n_shards;
+    folds.n_swap = n_swap;
+    folds.iter = iter;
+    folds.max_iterations = max_iterations;
+    folds.thin = sink.thin;
+    folds.append = mode[0] == 'a';
+    folds.model = apemost_ladder_model(l);
+    folds.sigma = apemost_ladder_sigma(l);
+    folds.nbins = NBINS;
+    run_folds_open(sink.folds, &folds);
     for (i = 0; i < 2 && device_pack; i++)
         apemost_hip_or_die(apemost_hip_samples_alloc(apemost_ladder_shard(l, 0), max_rounds * n_swap, &d_packed[i]),
                            "samples_alloc");
@@ -771,10 +579,12 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         apemost_ladder_run(l, rounds_now, n_swap, d_samples[k]);
     while (rounds_now > 0) {
         const unsigned long n_steps = rounds_now * n_swap, iter_after = iter + n_steps;
+        /* first kept step of this batch: iteration numbers count from 1 */
+        const unsigned long skip = (sink.thin - (iter % sink.thin) - 1) % sink.thin;
         uint64_t kept = 0;
         if (device_pack)
             apemost_hip_or_die(apemost_hip_samples_pack_read_async(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
-                                                                   (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin,
+                                                                   skip, sink.thin,
                                                                    (int32_t)sink.n_param_chains, 0, d_packed[k],
                                                                    h_samples[k][0], h_counts[k][0], &kept),
                                "samples_pack_read_async");
@@ -785,44 +595,13 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         /* the text lines are formatted on the device, on the stream of those reads (the wait below covers it) */
         for (j = 0; j < n_shards && text_sink; j++)
             apemost_hip_or_die(apemost_hip_samples_text_read_async(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
-                                                                   (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin,
+                                                                   skip, sink.thin,
                                                                    (int32_t)sink_shard_param_chains(&sink, lo, j), d_text[k][j],
                                                                    text_scratch[j], h_text[k][j], text_bytes[j],
                                                                    h_offsets[k][j], text_streams[j] + 1),
                                "samples_text_read_async");
-        /* the summary folds the batch on the device, on the stream of those reads (the wait below covers it) */
-        for (j = 0; j < n_shards && sink.summary; j++)
-            apemost_hip_or_die(apemost_hip_summary_accumulate(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
-                                                              (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
-                               "summary_accumulate");
-        if (sink.peaks) /* chain 0's columns grow on the same stream */
-            apemost_hip_or_die(apemost_hip_peaks_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
-                                                            (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
-                               "peaks_accumulate");
-        if (sink.joint) /* chain 0's pair histograms and moments, on the same stream */
-            apemost_hip_or_die(apemost_hip_joint_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
-                                                            (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
-                               "joint_accumulate");
-        if (sink.derived) /* functions of chain 0's rows, on the same stream */
-            apemost_hip_or_die(apemost_hip_derived_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
-                                                              (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
-                               "derived_accumulate");
-        for (j = 0; j < n_shards && sink.evidence; j++) /* every chain's prob - prior column, on the same stream */
-            apemost_hip_or_die(apemost_hip_evidence_accumulate(apemost_ladder_shard(l, j), d_samples[k][j], n_steps,
-                                                               (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
-                               "evidence_accumulate");
-        if (sink.autocorr) /* chain 0's columns, on the same stream */
-            apemost_hip_or_die(apemost_hip_autocorr_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
-                                                               (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
-                               "autocorr_accumulate");
-        if (sink.predict) /* chain 0's model curve, on the same stream */
-            apemost_hip_or_die(apemost_hip_predict_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
-                                                              (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
-                               "predict_accumulate");
-        if (sink.pointwise) /* chain 0's pointwise log-likelihood, on the same stream */
-            apemost_hip_or_die(apemost_hip_pointwise_accumulate(apemost_ladder_shard(l, 0), d_samples[k][0], n_steps,
-                                                                (sink.thin - (iter % sink.thin) - 1) % sink.thin, sink.thin),
-                               "pointwise_accumulate");
+        /* the requested folds take the batch on the device, on the stream of those reads (the wait below covers it) */
+        run_folds_accumulate(sink.folds, &folds, d_samples[k], n_steps, skip);
         /* no rows on the host (the text sink, or no sample files): only the counters and chain 0's latest point
          * cross (a packed read that keeps no step) */
         for (j = 0; j < n_shards && !device_pack && !rows_on_host; j++)
@@ -838,7 +617,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
         if (device_pack)
             sink_write_packed(&sink, h_samples[k][0], (unsigned long)kept);
         else if (rows_on_host)
-            sink_write(&sink, h_samples[k], lo, n_shards, iter, n_steps);
+            sink_write(&sink, h_samples[k], lo, n_shards, skip, n_steps);
         else if (text_sink)
             sink_write_text(&sink, chains, h_text[k], h_offsets[k], lo, n_shards);
         iter = iter_after;
@@ -880,22 +659,7 @@ static void run_sampler(mcmc **chains, const unsigned int n_beta, const unsigned
 #ifdef TRACK_REPLICAS
     apemost_write_replica_flow(l);
 #endif
-    if (sink.summary)
-        summary_close(&summary, l, lo, n_shards);
-    if (sink.peaks)
-        run_peaks_close(apemost_ladder_shard(l, 0), chains[0]);
-    if (sink.joint)
-        run_joint_close(&joint, apemost_ladder_shard(l, 0), chains[0]);
-    if (sink.derived)
-        run_derived_close(&derived, apemost_ladder_shard(l, 0));
-    if (sink.evidence)
-        run_evidence_close(&evidence, l, lo, n_shards);
-    if (sink.autocorr)
-        run_autocorr_close(&autocorr, apemost_ladder_shard(l, 0), chains[0]);
-    if (sink.predict)
-        run_predict_close(&predict, apemost_ladder_shard(l, 0), chains[0]);
-    if (sink.pointwise)
-        run_pointwise_close(&pointwise, apemost_ladder_shard(l, 0));
+    run_folds_close(sink.folds, &folds);
     for (i = 0; i < 2; i++)
         for (j = 0; j < n_shards; j++) {
             apemost_hip_samples_free(apemost_ladder_shard(l, j), d_samples[i][j]);

@@ -1,6 +1,5 @@
 /* autocorr.bin reader and writer, the estimators and autocorr.txt of the APEMOST_DUMP token `autocorr`
  * (run_autocorr.h).  No device and no chain is needed here. */
-#define RUN_AUTOCORR_STANDALONE
 #include "run_autocorr.h"
 
 #include <math.h>
@@ -197,19 +196,11 @@ void run_autocorr_write_text(const char *path, const run_autocorr *r, const char
             fprintf(f, "%s\t", names[col]);
         else
             fprintf(f, "%s\t", col == r->n_par ? "prob" : "prob-prior");
-        run_print_value(f, mean);
-        fprintf(f, "\t");
-        run_print_value(f, acov[0]);
-        fprintf(f, "\t");
-        run_print_value(f, ts);
+        run_print_values(f, 3, mean, acov[0], ts);
         fprintf(f, "\t%ld\t", window);
-        run_print_value(f, n / ts);
-        fprintf(f, "\t");
         t = acov[0] * ts;
         t = t / n;
-        run_print_value(f, sqrt(t));
-        fprintf(f, "\t");
-        run_print_value(f, tg);
+        run_print_values(f, 3, n / ts, sqrt(t), tg);
         fprintf(f, "\n");
     }
     free(acov);

@@ -5,8 +5,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "apemost_bridge.h"
 #include "mcmc_gettersetter.h"
+#include "run_fold.h"
+
+static run_autocorr autocorr;
 
 static void autocorr_view(run_autocorr *r, apemost_hip_autocorr_view *v) {
     v->n = &r->n;
@@ -31,14 +33,21 @@ static unsigned int lags_from_env(void) {
     return (unsigned int)v;
 }
 
-void run_autocorr_open(run_autocorr *r, apemost_hip_sampler *s, const mcmc *chain0, uint64_t thin, int append) {
-    const unsigned int n_par = get_n_par(chain0);
+/* begins the fold of chain 0: all parameters and prob - prior, max_lag from APEMOST_AUTOCORR_LAGS.  With c->append
+ * autocorr.bin is loaded and the fold goes on from it; a file of another shape, max_lag or thin ends the program. */
+void run_autocorr_open(const run_fold_ctx *ctx, uint64_t planned) {
+    run_autocorr *r = &autocorr;
+    apemost_hip_sampler *s = apemost_ladder_shard(ctx->l, 0);
+    const unsigned int n_par = get_n_par(ctx->chains[0]);
+    const uint64_t thin = ctx->thin;
+    const int append = ctx->append;
     const int32_t chain = 0;
     apemost_hip_autocorr_config c;
     apemost_hip_autocorr_view v;
     run_autocorr old;
     int found = -1;
     unsigned int p;
+    (void)planned;
     memset(r, 0, sizeof *r);
     memset(&old, 0, sizeof old);
     r->n_par = n_par;
@@ -81,12 +90,15 @@ void run_autocorr_open(run_autocorr *r, apemost_hip_sampler *s, const mcmc *chai
     }
 }
 
-void run_autocorr_close(run_autocorr *r, apemost_hip_sampler *s, const mcmc *chain0) {
+/* collects the accumulator, writes autocorr.bin and autocorr.txt, and frees everything */
+void run_autocorr_close(const run_fold_ctx *ctx) {
+    run_autocorr *r = &autocorr;
+    apemost_hip_sampler *s = apemost_ladder_shard(ctx->l, 0);
     apemost_hip_autocorr_view v;
     autocorr_view(r, &v);
     apemost_hip_or_die(apemost_hip_autocorr_get(s, &v), "autocorr_get");
     apemost_hip_or_die(apemost_hip_autocorr_end(s), "autocorr_end");
     run_autocorr_write(RUN_AUTOCORR_FILE, r);
-    run_autocorr_write_text(RUN_AUTOCORR_TEXT, r, get_params_descr(chain0));
+    run_autocorr_write_text(RUN_AUTOCORR_TEXT, r, get_params_descr(ctx->chains[0]));
     run_autocorr_free(r);
 }

@@ -28,15 +28,6 @@ static char *copy_text(const char *s, size_t len) {
     return p;
 }
 
-static size_t tri_count(const run_derived *r) {
-    return (size_t)r->n_col * (r->n_col + 1) / 2;
-}
-
-uint64_t run_derived_batches(uint64_t n, uint64_t bs);
-uint64_t run_derived_batches(uint64_t n, uint64_t bs) {
-    return bs == 1 ? n : (n + 1) / bs;
-}
-
 /* a number in full, as Python's float() reads it too: no hexadecimal form */
 static int parse_number(const char *tok, double *v) {
     char *end;
@@ -196,7 +187,7 @@ void run_derived_alloc(run_derived *r) {
     r->vmax = (double *)alloc_or_die(nc, sizeof(double));
     r->origin = (double *)alloc_or_die(nc, sizeof(double));
     r->sum = (double *)alloc_or_die(nc, sizeof(double));
-    r->cross = (double *)alloc_or_die(tri_count(r), sizeof(double));
+    r->cross = (double *)alloc_or_die(run_tri_count(r->n_col), sizeof(double));
     r->counts = (uint64_t *)alloc_or_die((size_t)r->n_pairs * r->nbins * r->nbins, sizeof(uint64_t));
 }
 
@@ -262,7 +253,7 @@ int run_derived_read(const char *path, run_derived *r) {
     read_or_die(u64, sizeof(uint64_t), 5, f, path);
     if (memcmp(magic, RUN_DERIVED_MAGIC, 8) != 0 || u32[0] != RUN_DERIVED_VERSION || u32[1] != 1 || u32[2] < 1 ||
         u32[2] > APEMOST_DERIVED_MAX_COLUMNS || u32[3] < 1 || u32[3] > 512 || u32[4] > u32[2] * (u32[2] - 1) / 2 ||
-        u32[5] > 65535 || u64[2] < 1 || u64[3] > ((uint64_t)1 << 40) || u64[4] != run_derived_batches(u64[0], u64[2]) ||
+        u32[5] > 65535 || u64[2] < 1 || u64[3] > ((uint64_t)1 << 40) || u64[4] != run_batches_closed(u64[0], u64[2]) ||
         u64[4] > u64[3]) {
         fprintf(stderr, "%s: not a derived file of version %d and one kept chain\n", path, RUN_DERIVED_VERSION);
         exit(1);
@@ -304,7 +295,7 @@ int run_derived_read(const char *path, run_derived *r) {
     read_or_die(r->vmax, sizeof(double), r->n_col, f, path);
     read_or_die(r->origin, sizeof(double), r->n_col, f, path);
     read_or_die(r->sum, sizeof(double), r->n_col, f, path);
-    read_or_die(r->cross, sizeof(double), tri_count(r), f, path);
+    read_or_die(r->cross, sizeof(double), run_tri_count(r->n_col), f, path);
     read_or_die(r->counts, sizeof(uint64_t), (size_t)r->n_pairs * r->nbins * r->nbins, f, path);
     fclose(f);
     return 0;
@@ -325,7 +316,7 @@ void run_derived_write(const char *path, const run_derived *r) {
     u64[1] = r->thin;
     u64[2] = r->bs;
     u64[3] = r->max_batches;
-    u64[4] = run_derived_batches(r->n, r->bs);
+    u64[4] = run_batches_closed(r->n, r->bs);
     fwrite(RUN_DERIVED_MAGIC, 1, 8, f);
     fwrite(u32, sizeof(uint32_t), 6, f);
     fwrite(u64, sizeof(uint64_t), 5, f);
@@ -347,28 +338,16 @@ void run_derived_write(const char *path, const run_derived *r) {
     fwrite(r->vmax, sizeof(double), r->n_col, f);
     fwrite(r->origin, sizeof(double), r->n_col, f);
     fwrite(r->sum, sizeof(double), r->n_col, f);
-    fwrite(r->cross, sizeof(double), tri_count(r), f);
+    fwrite(r->cross, sizeof(double), run_tri_count(r->n_col), f);
     fwrite(r->counts, sizeof(uint64_t), (size_t)r->n_pairs * r->nbins * r->nbins, f);
     run_close_or_die(f, path);
-}
-
-/* the summary's edge b of n over [lo, hi]: summary_edge of apemost_amd/csrc/pt_summary.h, the same two products and
- * one sum, unfused */
-static double derived_edge(double lo, double hi, unsigned int b, unsigned int n) {
-    const double f1 = (double)(n - b) / (double)n, f2 = (double)b / (double)n;
-    double e = f1 * lo;
-    const double t = f2 * hi;
-    e = e + t;
-    if (b == n)
-        e += (hi - lo) / 10000;
-    return e;
 }
 
 /* mean = origin + sum / n; sd = sqrt((cross_cc - sum^2 / n) / (n - 1)); mcse = batch_means_error() about that mean:
  * apemost_amd/derived.py, operation for operation */
 void run_derived_write_text(const run_derived *r) {
     const double n = (double)r->n, n1 = n - 1.0;
-    const uint64_t nb = run_derived_batches(r->n, r->bs);
+    const uint64_t nb = run_batches_closed(r->n, r->bs);
     FILE *f = run_open_or_die("derived.txt", "w");
     unsigned int c, b;
     uint64_t k;
@@ -387,15 +366,7 @@ void run_derived_write_text(const run_derived *r) {
         }
         mcse = (nb > 0 && err >= 0) ? sqrt(err / (double)nb) : sqrt(-1.0);
         fprintf(f, "%s\t%lu\t", r->names[c], (unsigned long)r->n);
-        run_print_value(f, mean);
-        fprintf(f, "\t");
-        run_print_value(f, sqrt(var));
-        fprintf(f, "\t");
-        run_print_value(f, mcse);
-        fprintf(f, "\t");
-        run_print_value(f, r->vmin[c]);
-        fprintf(f, "\t");
-        run_print_value(f, r->vmax[c]);
+        run_print_values(f, 5, mean, sqrt(var), mcse, r->vmin[c], r->vmax[c]);
         fprintf(f, "\t%lu\n", (unsigned long)r->nonfinite[c]);
         diag += r->n_col - c; /* (c, c) of the row-major upper triangle */
         /* counts * (hi - lo) / nbins / total, as analyse scales a parameter's histogram */
@@ -405,8 +376,8 @@ void run_derived_write_text(const run_derived *r) {
         sprintf(name, "%s.histogram", r->names[c]);
         h = run_open_or_die(name, "w");
         for (b = 0; b < r->nbins; b++) {
-            fprintf(h, "%.15e %.15e ", derived_edge(r->lo[c], r->hi[c], b, r->nbins),
-                    derived_edge(r->lo[c], r->hi[c], b + 1, r->nbins));
+            fprintf(h, "%.15e %.15e ", run_summary_edge(r->lo[c], r->hi[c], b, r->nbins),
+                    run_summary_edge(r->lo[c], r->hi[c], b + 1, r->nbins));
             run_print_value(h, (double)hist[b] * scale);
             fprintf(h, "\n");
         }

@@ -1,16 +1,15 @@
 /* the device side of the APEMOST_DUMP token `derived` (run_derived.h): the derived file, begin, resume, collect */
 #include "run_derived.h"
 
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "apemost_bridge.h"
 #include "mcmc_gettersetter.h"
+#include "run_fold.h"
 #include "run_io.h"
 
-uint64_t run_derived_batches(uint64_t n, uint64_t bs);
+static run_derived derived;
 
 static void derived_view(run_derived *r, apemost_hip_derived_view *v) {
     memset(v, 0, sizeof *v);
@@ -44,9 +43,17 @@ static char *whole_file(const char *path) {
     return text;
 }
 
-void run_derived_open(run_derived *r, apemost_hip_sampler *s, const mcmc *chain0, unsigned int nbins, uint64_t planned,
-                      uint64_t thin, int append) {
-    const unsigned int n_par = get_n_par(chain0);
+/* reads and checks the derived file (a bad line ends the program with its number), then begins the fold of chain 0 for
+ * `planned` more kept samples: c->nbins bins, batches of floor(sqrt(planned)).  With c->append derived.bin is loaded and
+ * the accumulation goes on from it with its own batch size; a file of other columns, ranges, nbins or thin ends the
+ * program with the messages a summary.bin of another shape gets. */
+void run_derived_open(const run_fold_ctx *ctx, uint64_t planned) {
+    run_derived *r = &derived;
+    apemost_hip_sampler *s = apemost_ladder_shard(ctx->l, 0);
+    const mcmc *chain0 = ctx->chains[0];
+    const unsigned int n_par = get_n_par(chain0), nbins = ctx->nbins;
+    const uint64_t thin = ctx->thin;
+    const int append = ctx->append;
     const char *path = getenv("APEMOST_DERIVED_FILE");
     const int32_t chain = 0;
     apemost_hip_derived_config c;
@@ -82,20 +89,13 @@ void run_derived_open(run_derived *r, apemost_hip_sampler *s, const mcmc *chain0
                             "cannot append\n", RUN_DERIVED_FILE);
             exit(1);
         }
-        for (i = 0; i < r->n_col; i++)
-            if (old.lo[i] != r->lo[i] || old.hi[i] != r->hi[i]) {
-                fprintf(stderr, "%s: column %u had the range [%g, %g], now [%g, %g]; cannot append\n", RUN_DERIVED_FILE, i,
-                        old.lo[i], old.hi[i], r->lo[i], r->hi[i]);
-                exit(1);
-            }
+        run_check_ranges_or_die(RUN_DERIVED_FILE, "column", r->n_col, old.lo, old.hi, r->lo, r->hi);
         resumed = 1;
     } else if (append)
         fprintf(stderr, "--append: no %s, the derived quantities start with this run\n", RUN_DERIVED_FILE);
     r->n = resumed ? old.n : 0;
-    r->bs = resumed ? old.bs : (uint64_t)sqrt((double)planned);
-    if (r->bs < 1)
-        r->bs = 1;
-    r->max_batches = run_derived_batches(r->n + planned, r->bs);
+    r->bs = run_batch_size(resumed, old.bs, planned);
+    r->max_batches = run_batches_closed(r->n + planned, r->bs);
     r->pairs = (int32_t *)run_alloc_or_die((size_t)r->n_pairs * 2, sizeof(int32_t), "derived quantities");
     for (i = 0; i < r->n_col && r->n_pairs > 0; i++)
         for (j = i + 1; j < r->n_col; j++, q++) {
@@ -130,7 +130,7 @@ void run_derived_open(run_derived *r, apemost_hip_sampler *s, const mcmc *chain0
         memcpy(r->cross, old.cross, nc * (nc + 1) / 2 * sizeof(double));
         memcpy(r->counts, old.counts, (size_t)r->n_pairs * nbins * nbins * sizeof(uint64_t));
         for (i = 0; i < r->n_col; i++) /* closed batches and the open one, at the new capacity's stride */
-            for (b = 0; b <= run_derived_batches(old.n, old.bs); b++)
+            for (b = 0; b <= run_batches_closed(old.n, old.bs); b++)
                 r->batch[(size_t)i * (size_t)(r->max_batches + 1) + b] = old.batch[(size_t)i * (size_t)(old.max_batches + 1) + b];
         derived_view(r, &v);
         apemost_hip_or_die(apemost_hip_derived_set(s, &v), "derived_set");
@@ -138,7 +138,10 @@ void run_derived_open(run_derived *r, apemost_hip_sampler *s, const mcmc *chain0
     }
 }
 
-void run_derived_close(run_derived *r, apemost_hip_sampler *s) {
+/* collects the accumulator, writes derived.bin, derived.txt and the .histogram files, and frees everything */
+void run_derived_close(const run_fold_ctx *ctx) {
+    run_derived *r = &derived;
+    apemost_hip_sampler *s = apemost_ladder_shard(ctx->l, 0);
     apemost_hip_derived_view v;
     derived_view(r, &v);
     apemost_hip_or_die(apemost_hip_derived_get(s, &v), "derived_get");

@@ -6,8 +6,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "apemost_bridge.h"
-#include "mcmc_gettersetter.h"
 #include "run_io.h"
 
 /* run_io.h with this file's word in the messages */
@@ -17,25 +15,21 @@
 #define RUN_JOINT_MAGIC "APEMOSTJ"
 #define RUN_JOINT_VERSION 1
 
-static size_t tri_count(const run_joint *r) {
-    return (size_t)r->n_par * (r->n_par + 1) / 2;
-}
-
 static size_t tri_index(const run_joint *r, unsigned int i, unsigned int j) {
     return (size_t)i * r->n_par - (size_t)i * (i > 0 ? i - 1 : 0) / 2 + (j - i);
 }
 
-static void joint_alloc(run_joint *r) {
+void run_joint_alloc(run_joint *r) {
     r->pairs = (int32_t *)alloc_or_die((size_t)r->n_pairs * 2, sizeof(int32_t));
     r->lo = (double *)alloc_or_die(r->n_par, sizeof(double));
     r->hi = (double *)alloc_or_die(r->n_par, sizeof(double));
     r->origin = (double *)alloc_or_die(r->n_par, sizeof(double));
     r->sum = (double *)alloc_or_die(r->n_par, sizeof(double));
-    r->cross = (double *)alloc_or_die(tri_count(r), sizeof(double));
+    r->cross = (double *)alloc_or_die(run_tri_count(r->n_par), sizeof(double));
     r->counts = (uint64_t *)alloc_or_die((size_t)r->n_pairs * r->nbins * r->nbins, sizeof(uint64_t));
 }
 
-static void joint_free(run_joint *r) {
+void run_joint_free(run_joint *r) {
     free(r->pairs);
     free(r->lo);
     free(r->hi);
@@ -46,8 +40,7 @@ static void joint_free(run_joint *r) {
     memset(r, 0, sizeof *r);
 }
 
-/* 0: read; -1: no such file.  *n_keep and *chain receive the kept chains and the first of them */
-static int joint_read(const char *path, run_joint *r, uint32_t *n_keep, int32_t *chain) {
+int run_joint_read(const char *path, run_joint *r, uint32_t *n_keep, int32_t *chain) {
     FILE *f = fopen(path, "rb");
     char magic[8];
     uint32_t u32[6];
@@ -76,20 +69,20 @@ static int joint_read(const char *path, run_joint *r, uint32_t *n_keep, int32_t 
         r->counts = NULL;
         return 0;
     }
-    joint_alloc(r);
+    run_joint_alloc(r);
     read_or_die(chain, sizeof(int32_t), 1, f, path);
     read_or_die(r->pairs, sizeof(int32_t), (size_t)r->n_pairs * 2, f, path);
     read_or_die(r->lo, sizeof(double), r->n_par, f, path);
     read_or_die(r->hi, sizeof(double), r->n_par, f, path);
     read_or_die(r->origin, sizeof(double), r->n_par, f, path);
     read_or_die(r->sum, sizeof(double), r->n_par, f, path);
-    read_or_die(r->cross, sizeof(double), tri_count(r), f, path);
+    read_or_die(r->cross, sizeof(double), run_tri_count(r->n_par), f, path);
     read_or_die(r->counts, sizeof(uint64_t), (size_t)r->n_pairs * r->nbins * r->nbins, f, path);
     fclose(f);
     return 0;
 }
 
-static void joint_write(const char *path, const run_joint *r) {
+void run_joint_write(const char *path, const run_joint *r) {
     FILE *f = run_open_or_die(path, "wb");
     uint32_t u32[6];
     uint64_t u64[2];
@@ -111,102 +104,12 @@ static void joint_write(const char *path, const run_joint *r) {
     fwrite(r->hi, sizeof(double), r->n_par, f);
     fwrite(r->origin, sizeof(double), r->n_par, f);
     fwrite(r->sum, sizeof(double), r->n_par, f);
-    fwrite(r->cross, sizeof(double), tri_count(r), f);
+    fwrite(r->cross, sizeof(double), run_tri_count(r->n_par), f);
     fwrite(r->counts, sizeof(uint64_t), (size_t)r->n_pairs * r->nbins * r->nbins, f);
     run_close_or_die(f, path);
 }
 
-static void joint_view(run_joint *r, apemost_hip_joint_view *v) {
-    v->n = &r->n;
-    v->counts = r->counts;
-    v->origin = r->origin;
-    v->sum = r->sum;
-    v->cross = r->cross;
-}
-
-void run_joint_open(run_joint *r, apemost_hip_sampler *s, const mcmc *chain0, unsigned int nbins, uint64_t thin,
-                    int append) {
-    const unsigned int n_par = get_n_par(chain0);
-    const int32_t chain = 0;
-    apemost_hip_joint_config c;
-    apemost_hip_joint_view v;
-    run_joint old;
-    uint32_t old_keep = 0;
-    int32_t old_chain = -1;
-    int resumed = 0;
-    unsigned int i, j, p, q = 0;
-    memset(&old, 0, sizeof old);
-    memset(r, 0, sizeof *r);
-    r->n_par = n_par;
-    r->nbins = nbins;
-    r->n_pairs = n_par * (n_par - 1) / 2;
-    r->thin = thin;
-    if (append && joint_read(RUN_JOINT_FILE, &old, &old_keep, &old_chain) == 0) {
-        if (old_keep != 1 || old_chain != 0 || old.n_par != n_par || old.nbins != nbins || old.thin != thin ||
-            old.n_pairs != r->n_pairs) {
-            fprintf(stderr, "%s: written by a run of another shape (chains, parameters, NBINS or thin:N); "
-                            "cannot append\n", RUN_JOINT_FILE);
-            exit(1);
-        }
-        resumed = 1;
-    } else if (append)
-        fprintf(stderr, "--append: no %s, the joint marginals start with this run\n", RUN_JOINT_FILE);
-    joint_alloc(r);
-    for (i = 0; i < n_par; i++)
-        for (j = i + 1; j < n_par; j++, q++) {
-            r->pairs[2 * q] = (int32_t)i;
-            r->pairs[2 * q + 1] = (int32_t)j;
-        }
-    for (p = 0; p < n_par; p++) {
-        r->lo[p] = get_params_min_for(chain0, p);
-        r->hi[p] = get_params_max_for(chain0, p);
-        if (resumed && (old.lo[p] != r->lo[p] || old.hi[p] != r->hi[p])) {
-            fprintf(stderr, "%s: parameter %u had the range [%g, %g], now [%g, %g]; cannot append\n", RUN_JOINT_FILE, p,
-                    old.lo[p], old.hi[p], r->lo[p], r->hi[p]);
-            exit(1);
-        }
-    }
-    if (resumed && memcmp(old.pairs, r->pairs, (size_t)r->n_pairs * 2 * sizeof(int32_t)) != 0) {
-        fprintf(stderr, "%s: written by a run of another shape (chains, parameters, NBINS or thin:N); "
-                        "cannot append\n", RUN_JOINT_FILE);
-        exit(1);
-    }
-    c.n_keep = 1;
-    c.chains = &chain;
-    c.nbins = (int32_t)nbins;
-    c.n_pairs = 0;
-    c.pairs = NULL; /* all pairs, in the order written above */
-    c.lo = r->lo;
-    c.hi = r->hi;
-    apemost_hip_or_die(apemost_hip_joint_begin(s, &c), "joint_begin");
-    if (resumed) {
-        r->n = old.n;
-        memcpy(r->origin, old.origin, n_par * sizeof(double));
-        memcpy(r->sum, old.sum, n_par * sizeof(double));
-        memcpy(r->cross, old.cross, tri_count(r) * sizeof(double));
-        memcpy(r->counts, old.counts, (size_t)r->n_pairs * nbins * nbins * sizeof(uint64_t));
-        joint_view(r, &v);
-        apemost_hip_or_die(apemost_hip_joint_set(s, &v), "joint_set");
-    }
-    if (old.lo != NULL)
-        joint_free(&old);
-}
-
-/* "%.15e", a NaN of either sign as nan */
-/* the summary's edge b of n over [lo, hi] (gsl_histogram_set_ranges_uniform, the top one widened as create_hist()).
- * The definition it must follow is summary_edge of apemost_amd/csrc/pt_summary.h, which bins the samples: the same
- * two products and one sum, unfused (summary.edges of apemost_amd/summary.py is the Python statement of it). */
-static double joint_edge(double lo, double hi, unsigned int b, unsigned int n) {
-    const double f1 = (double)(n - b) / (double)n, f2 = (double)b / (double)n;
-    double e = f1 * lo;
-    const double t = f2 * hi;
-    e = e + t;
-    if (b == n)
-        e += (hi - lo) / 10000;
-    return e;
-}
-
-static void write_pair(const run_joint *r, unsigned int q, const char **names) {
+void run_joint_write_pair(const run_joint *r, unsigned int q, const char **names) {
     const unsigned int i = (unsigned int)r->pairs[2 * q], j = (unsigned int)r->pairs[2 * q + 1], n = r->nbins;
     const uint64_t *c = r->counts + (size_t)q * n * n;
     char name[500], (*ey)[32];
@@ -217,10 +120,10 @@ static void write_pair(const run_joint *r, unsigned int q, const char **names) {
     f = run_open_or_die(name, "w");
     ey = (char(*)[32])alloc_or_die((size_t)n + 1, 32);
     for (b = 0; b <= n; b++)
-        sprintf(ey[b], "%.15e", joint_edge(r->lo[j], r->hi[j], b, n));
+        sprintf(ey[b], "%.15e", run_summary_edge(r->lo[j], r->hi[j], b, n));
     for (a = 0; a < n; a++) {
-        sprintf(x0, "%.15e", joint_edge(r->lo[i], r->hi[i], a, n));
-        sprintf(x1, "%.15e", joint_edge(r->lo[i], r->hi[i], a + 1, n));
+        sprintf(x0, "%.15e", run_summary_edge(r->lo[i], r->hi[i], a, n));
+        sprintf(x1, "%.15e", run_summary_edge(r->lo[i], r->hi[i], a + 1, n));
         for (b = 0; b < n; b++)
             fprintf(f, "%s %s %s %s %lu\n", x0, x1, ey[b], ey[b + 1], (unsigned long)c[(size_t)a * n + b]);
         fprintf(f, "\n");
@@ -231,7 +134,7 @@ static void write_pair(const run_joint *r, unsigned int q, const char **names) {
 
 /* cov_ij = (cross_ij - sum_i sum_j / n) / (n - 1); corr_ij = cov_ij / (sqrt(cov_ii) sqrt(cov_jj)), the diagonal 1 where
  * the variance is finite and positive and NaN elsewhere: apemost_amd/joint.py, operation for operation */
-static void write_correlation(const run_joint *r) {
+void run_joint_write_correlation(const run_joint *r) {
     const unsigned int np = r->n_par;
     const double n = (double)r->n, n1 = n - 1.0;
     double *cov = (double *)alloc_or_die((size_t)np * np, sizeof(double));
@@ -263,18 +166,4 @@ static void write_correlation(const run_joint *r) {
     free(cov);
     free(sd);
     run_close_or_die(f, "correlation.matrix");
-}
-
-void run_joint_close(run_joint *r, apemost_hip_sampler *s, const mcmc *chain0) {
-    const char **names = get_params_descr(chain0);
-    apemost_hip_joint_view v;
-    unsigned int q;
-    joint_view(r, &v);
-    apemost_hip_or_die(apemost_hip_joint_get(s, &v), "joint_get");
-    apemost_hip_or_die(apemost_hip_joint_end(s), "joint_end");
-    joint_write(RUN_JOINT_FILE, r);
-    for (q = 0; q < r->n_pairs; q++)
-        write_pair(r, q, names);
-    write_correlation(r);
-    joint_free(r);
 }

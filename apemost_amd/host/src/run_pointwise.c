@@ -1,6 +1,5 @@
 /* pointwise.bin reader and writer, pointwise.txt and criteria.txt of the APEMOST_DUMP token `pointwise`
  * (run_pointwise.h).  No device and no chain is needed here. */
-#define RUN_POINTWISE_STANDALONE
 #include "run_pointwise.h"
 
 #include <math.h>
@@ -235,21 +234,7 @@ void run_pointwise_write_text(const char *path, const run_pointwise *r) {
     uint32_t i;
     for (i = 0; i < r->n_data; i++) {
         const pointwise_datum d = datum(r, i);
-        run_print_value(f, r->x[i]);
-        fprintf(f, "\t");
-        run_print_value(f, r->y[i]);
-        fprintf(f, "\t");
-        run_print_value(f, d.mean);
-        fprintf(f, "\t");
-        run_print_value(f, sqrt(d.var));
-        fprintf(f, "\t");
-        run_print_value(f, d.lppd);
-        fprintf(f, "\t");
-        run_print_value(f, d.var);
-        fprintf(f, "\t");
-        run_print_value(f, d.elpd_loo);
-        fprintf(f, "\t");
-        run_print_value(f, d.ess);
+        run_print_values(f, 8, r->x[i], r->y[i], d.mean, sqrt(d.var), d.lppd, d.var, d.elpd_loo, d.ess);
         fprintf(f, "\n");
     }
     run_close_or_die(f, path);

@@ -5,8 +5,11 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "apemost_bridge.h"
 #include "mcmc_gettersetter.h"
+#include "run_fold.h"
+#include "run_io.h"
+
+static run_pointwise pointwise;
 
 static void pointwise_view(run_pointwise *r, apemost_hip_pointwise_view *v) {
     v->n = &r->n;
@@ -72,8 +75,17 @@ static void tail_open(run_pointwise *r, apemost_hip_sampler *s, int asked, int r
     }
 }
 
-void run_pointwise_open(run_pointwise *r, apemost_hip_sampler *s, const mcmc *chain0, int model, double sigma,
-                        uint64_t thin, int append, uint64_t planned) {
+/* begins the fold of chain 0 over its data.  With c->append pointwise.bin is loaded and the fold goes on from it; a file
+ * of another shape, data, sigma or thin ends the program.  APEMOST_POINTWISE_TAIL begins the tail as well (`planned`
+ * kept samples size it under auto); with c->append pointwise_tail.bin is loaded, and one of another shape, capacity or
+ * sample count than pointwise.bin's ends the program. */
+void run_pointwise_open(const run_fold_ctx *ctx, uint64_t planned) {
+    run_pointwise *r = &pointwise;
+    apemost_hip_sampler *s = apemost_ladder_shard(ctx->l, 0);
+    const mcmc *chain0 = ctx->chains[0];
+    const int model = ctx->model, append = ctx->append;
+    const double sigma = ctx->sigma;
+    const uint64_t thin = ctx->thin;
     const int32_t chain = 0;
     const int tail = run_pointwise_tail_from_env();
     apemost_hip_pointwise_config c;
@@ -133,14 +145,14 @@ void run_pointwise_open(run_pointwise *r, apemost_hip_sampler *s, const mcmc *ch
         tail_open(r, s, tail, found == 0, planned);
 }
 
-void run_pointwise_close(run_pointwise *r, apemost_hip_sampler *s) {
+/* collects the accumulator, evaluates the term at the mean parameters on the device, writes the three files, and
+ * frees everything */
+void run_pointwise_close(const run_fold_ctx *ctx) {
+    run_pointwise *r = &pointwise;
+    apemost_hip_sampler *s = apemost_ladder_shard(ctx->l, 0);
     apemost_hip_pointwise_view v;
-    double *mean = (double *)calloc(r->n_par > 0 ? r->n_par : 1, sizeof(double));
+    double *mean = (double *)run_alloc_or_die(r->n_par, sizeof(double), "pointwise");
     uint32_t p;
-    if (mean == NULL) {
-        fprintf(stderr, "pointwise: out of memory\n");
-        exit(1);
-    }
     pointwise_view(r, &v);
     apemost_hip_or_die(apemost_hip_pointwise_get(s, &v), "pointwise_get");
     if (r->tail.capacity > 0) {

@@ -1,6 +1,5 @@
 /* predict.bin reader and writer, the quantiles and predict.txt of the APEMOST_DUMP token `predict` (run_predict.h).
  * No device and no chain is needed here. */
-#define RUN_PREDICT_STANDALONE
 #include "run_predict.h"
 
 #include <math.h>
@@ -132,17 +131,9 @@ void run_predict_write(const char *path, const run_predict *r) {
 
 /* the run summary's edges: GSL's uniform ranges, the top one widened */
 void run_predict_edges(const run_predict *r, double *edges) {
-    const double n = (double)r->nbins;
     uint32_t b;
-    for (b = 0; b <= r->nbins; b++) {
-        const double f1 = (double)(r->nbins - b) / n, f2 = (double)b / n;
-        const double t1 = f1 * r->lo, t2 = f2 * r->hi;
-        edges[b] = t1 + t2;
-    }
-    if (r->nbins > 0) {
-        const double w = r->hi - r->lo;
-        edges[r->nbins] += w / 10000;
-    }
+    for (b = 0; b <= r->nbins; b++)
+        edges[b] = run_summary_edge(r->lo, r->hi, b, r->nbins);
 }
 
 /* Predict.quantile of apemost_amd/predict.py, operation for operation */
@@ -190,28 +181,12 @@ void run_predict_write_text(const char *path, const run_predict *r, const double
         var = t / n;
         if (var < 0)
             var = 0.0;
-        run_print_value(f, r->x[i]);
-        fprintf(f, "\t");
-        run_print_value(f, y[i]);
-        fprintf(f, "\t");
-        run_print_value(f, mean);
-        fprintf(f, "\t");
-        run_print_value(f, sqrt(var));
-        fprintf(f, "\t");
-        run_print_value(f, ratio ? y[i] / mean : y[i] - mean);
-        fprintf(f, "\t");
-        run_print_value(f, r->vmin[i]);
-        fprintf(f, "\t");
-        run_print_value(f, r->vmax[i]);
-        fprintf(f, "\t");
-        run_print_value(f, best[i]);
+        run_print_values(f, 8, r->x[i], y[i], mean, sqrt(var), ratio ? y[i] / mean : y[i] - mean, r->vmin[i], r->vmax[i],
+                         best[i]);
         if (r->nbins > 0) {
             fprintf(f, "\t");
-            run_print_value(f, run_predict_quantile(r, edges, i, 0.5));
-            fprintf(f, "\t");
-            run_print_value(f, run_predict_quantile(r, edges, i, (1 - 0.68) / 2));
-            fprintf(f, "\t");
-            run_print_value(f, run_predict_quantile(r, edges, i, (1 + 0.68) / 2));
+            run_print_values(f, 3, run_predict_quantile(r, edges, i, 0.5), run_predict_quantile(r, edges, i, (1 - 0.68) / 2),
+                             run_predict_quantile(r, edges, i, (1 + 0.68) / 2));
         }
         fprintf(f, "\n");
     }

@@ -5,8 +5,11 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "apemost_bridge.h"
 #include "mcmc_gettersetter.h"
+#include "run_fold.h"
+#include "run_io.h"
+
+static run_predict predict;
 
 static void predict_view(run_predict *r, apemost_hip_predict_view *v) {
     v->n = &r->n;
@@ -49,13 +52,22 @@ static void bins_from_env(run_predict *r) {
     }
 }
 
-void run_predict_open(run_predict *r, apemost_hip_sampler *s, const mcmc *chain0, int model, uint64_t thin, int append) {
+/* begins the fold of chain 0 over column 0 of its data; histograms when APEMOST_PREDICT_BINS and APEMOST_PREDICT_RANGE
+ * are both set.  With c->append predict.bin is loaded and the fold goes on from it; a file of another shape, range or
+ * thin ends the program.  (The bounded run is needed for the refusal alone: `planned` sizes nothing.) */
+void run_predict_open(const run_fold_ctx *ctx, uint64_t planned) {
+    run_predict *r = &predict;
+    apemost_hip_sampler *s = apemost_ladder_shard(ctx->l, 0);
+    const mcmc *chain0 = ctx->chains[0];
+    const int model = ctx->model, append = ctx->append;
+    const uint64_t thin = ctx->thin;
     const int32_t chain = 0;
     apemost_hip_predict_config c;
     apemost_hip_predict_view v;
     run_predict old;
     int found = -1;
     uint32_t i;
+    (void)planned;
     memset(r, 0, sizeof *r);
     memset(&old, 0, sizeof old);
     r->n_par = get_n_par(chain0);
@@ -114,14 +126,16 @@ void run_predict_open(run_predict *r, apemost_hip_sampler *s, const mcmc *chain0
     }
 }
 
-void run_predict_close(run_predict *r, apemost_hip_sampler *s, const mcmc *chain0) {
+/* collects the accumulator, evaluates the best-fit curve on the device, writes predict.bin and predict.txt, and frees
+ * everything */
+void run_predict_close(const run_fold_ctx *ctx) {
+    run_predict *r = &predict;
+    apemost_hip_sampler *s = apemost_ladder_shard(ctx->l, 0);
+    const mcmc *chain0 = ctx->chains[0];
     apemost_hip_predict_view v;
-    double *y = (double *)calloc(r->n_x, sizeof(double)), *best = (double *)calloc(r->n_x, sizeof(double));
+    double *y = (double *)run_alloc_or_die(r->n_x, sizeof(double), "predict");
+    double *best = (double *)run_alloc_or_die(r->n_x, sizeof(double), "predict");
     uint32_t i;
-    if (y == NULL || best == NULL) {
-        fprintf(stderr, "predict: out of memory\n");
-        exit(1);
-    }
     predict_view(r, &v);
     apemost_hip_or_die(apemost_hip_predict_get(s, &v), "predict_get");
     apemost_hip_or_die(apemost_hip_predict_end(s), "predict_end");

@@ -12,22 +12,6 @@
 #define RUN_SUMMARY_MAGIC "APEMOSTS"
 #define RUN_SUMMARY_VERSION 1
 
-int run_summary_requested(void) {
-    const char *spec = getenv("APEMOST_DUMP");
-    while (spec != NULL && *spec != 0) {
-        if (strncmp(spec, "summary", 7) == 0 && (spec[7] == 0 || spec[7] == ','))
-            return 1;
-        spec = strchr(spec, ',');
-        if (spec != NULL)
-            spec++;
-    }
-    return 0;
-}
-
-uint64_t run_summary_batches(uint64_t n, uint64_t bs) {
-    return bs == 1 ? n : (n + 1) / bs;
-}
-
 void run_summary_alloc(run_summary *r) {
     const size_t n_hp = (size_t)r->n_hist * r->n_par;
     r->lo = (double *)alloc_or_die(r->n_par, sizeof(double));
@@ -73,7 +57,7 @@ int run_summary_read(const char *path, run_summary *r) {
     r->n = u64[0];
     r->n_batches = u64[1];
     r->max_batches = u64[2];
-    if (r->bs < 1 || r->n_batches > r->max_batches || r->n_batches != run_summary_batches(r->n, r->bs)) {
+    if (r->bs < 1 || r->n_batches > r->max_batches || r->n_batches != run_batches_closed(r->n, r->bs)) {
         fprintf(stderr, "%s: inconsistent run summary\n", path);
         exit(1);
     }

@@ -2,7 +2,6 @@
  *   autocorr_check <autocorr.bin> <autocorr.txt> <again.bin> <name>...
  * reads the state, writes the text file from it and the state again.  tests/test_autocorr_cpu.py builds it with the
  * address and undefined-behaviour sanitizers and compares the files with what apemost_amd/autocorr.py writes. */
-#define RUN_AUTOCORR_STANDALONE
 #include "run_autocorr.h"
 
 #include <stdio.h>

@@ -1,7 +1,6 @@
 /* The C host's pointwise.bin reader and writer, pointwise.txt and criteria.txt (apemost_amd/host/src/run_pointwise.c)
  * with a main of their own: pointwise_check <pointwise.bin> <pointwise.txt> <criteria.txt> <copy.bin>.  Built by
  * tests/test_pointwise_cpu.py under the address and undefined-behaviour sanitizers; no device. */
-#define RUN_POINTWISE_STANDALONE
 #include "run_pointwise.h"
 
 int main(int argc, char **argv) {

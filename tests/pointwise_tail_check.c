@@ -2,7 +2,6 @@
  * `pointwise_tail_check in.bin out.bin` reads the one and writes the other; `pointwise_tail_check capacity N` prints
  * run_pointwise_tail_capacity_for(N).  Built and run by tests/test_pointwise_tail_cpu.py under the address and
  * undefined-behaviour sanitizers; no device.  Exit status 2 + what run_pointwise_tail_read returned where that is not 0. */
-#define RUN_POINTWISE_STANDALONE
 #include "run_pointwise.h"
 
 #include <stdio.h>

@@ -1,7 +1,6 @@
 /* The C host's predict.bin reader and writer and predict.txt (apemost_amd/host/src/run_predict.c) with a main of their
  * own: predict_check <predict.bin> <curves: y[n_x] then best[n_x], raw doubles> <predict.txt> <copy.bin>.  Built by
  * tests/test_predict_cpu.py under the address and undefined-behaviour sanitizers; no device. */
-#define RUN_PREDICT_STANDALONE
 #include "run_predict.h"
 
 #include <stdio.h>
