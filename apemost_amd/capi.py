@@ -132,6 +132,12 @@ class PointwiseJointView(C.Structure):
     _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("m", _dp), ("S", _dp)]
 
 
+class CheckView(C.Structure):
+    _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("sum_u", _dp), ("m", _dp), ("S", _dp), ("SU", _dp),
+                ("stat_origin", _dp), ("stat_sum", _dp), ("stat_sq", _dp), ("stat_min", _dp), ("stat_max", _dp),
+                ("counts", _up)]
+
+
 class DerivedConfig(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("n_col", C.c_int32),
                 ("code", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("n_const", C.c_int32), ("consts", _dp),
@@ -196,6 +202,8 @@ EXPORTS = [
     "apemost_hip_pointwise_loglike_at",
     "apemost_hip_derived_check", "apemost_hip_derived_begin", "apemost_hip_derived_accumulate",
     "apemost_hip_derived_get", "apemost_hip_derived_set", "apemost_hip_derived_end", "apemost_hip_derived_eval",
+    "apemost_hip_check_begin", "apemost_hip_check_accumulate", "apemost_hip_check_get", "apemost_hip_check_set",
+    "apemost_hip_check_lengths", "apemost_hip_check_end", "apemost_hip_check_values", "apemost_hip_check_null_edges",
 ]
 
 _lib = None
@@ -350,6 +358,14 @@ def lib():
     L.apemost_hip_pointwise_joint_set.argtypes = [vp, C.POINTER(PointwiseJointView)]
     L.apemost_hip_pointwise_loglike_at.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]
     ip = C.POINTER(C.c_int32)
+    L.apemost_hip_check_begin.argtypes = [vp, C.c_int32, ip, C.c_int32, _dp]
+    L.apemost_hip_check_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_check_get.argtypes = [vp, C.POINTER(CheckView)]
+    L.apemost_hip_check_set.argtypes = [vp, C.POINTER(CheckView)]
+    L.apemost_hip_check_lengths.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.apemost_hip_check_end.argtypes = [vp]
+    L.apemost_hip_check_values.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp]
+    L.apemost_hip_check_null_edges.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]
     L.apemost_hip_derived_check.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int32, ip]
     L.apemost_hip_derived_begin.argtypes = [vp, C.POINTER(DerivedConfig)]
     L.apemost_hip_derived_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]

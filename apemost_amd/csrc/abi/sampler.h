@@ -185,6 +185,26 @@ static void fold_free(PointwiseFold &f) {
     f = {};
 }
 
+// on-device predictive checks (pt_check.h): the predictive CDF of every datum and three discrepancy statistics per
+// kept sample
+struct CheckFold {
+    bool open;
+    int n_keep;
+    int n_data;  // the width of every [n_keep][n_data] array: the longest data among the kept chains' ladders
+    int n_edges; // edges per statistic; 0: no counts
+    double c, inv_sigma; // 1 / (-2 sigma^2), 1 / sigma
+    u64 n;
+    int *d_chains;
+    int *d_len;          // [n_keep] data per kept chain where they differ (a ragged batch), else nullptr
+    double *d_x, *d_y;   // [n_keep][n_data]
+    double *d_state;     // the seven [n_keep][n_data] words, one after the other (kCheckWords)
+    double *d_stat;      // origin, sum, sq, min, max: [n_keep][3] each, one after the other (kCheckStatWords)
+    double *d_T;         // [n_keep][3][kPointwisePiece]: the statistics of a piece's kept samples
+    double *d_edges;     // [3][n_edges], or nullptr
+    u64 *d_counts;       // [n_keep][3][n_edges + 2], or nullptr
+    FoldMem mem;
+};
+
 } // namespace
 
 struct apemost_hip_sampler {
@@ -283,6 +303,7 @@ struct apemost_hip_sampler {
     PredictFold pr;
     PointwiseFold pw;
     DerivedFold dv;
+    CheckFold ck;
 };
 
 // the data rows of ladder b and its column-major matrix on the device (an ordinary sampler: b = 0)
@@ -338,6 +359,7 @@ static void release(apemost_hip_sampler *s) {
     fold_free(s->pr);
     fold_free(s->pw);
     fold_free(s->dv);
+    fold_free(s->ck);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {

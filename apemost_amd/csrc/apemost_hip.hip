@@ -1,6 +1,7 @@
 // apemost_hip.hip -- kernels and C ABI of the gfx950 parallel-tempering engine
 // (declared in include/apemost_hip.h).  Written for MI355X only.
 #include "pt_autocorr.h"
+#include "pt_check.h"
 #include "pt_derived.h"
 #include "pt_evidence.h"
 #include "pt_joint.h"
@@ -1919,6 +1920,7 @@ extern "C" int apemost_hip_samples_wait(apemost_hip_sampler *s) {
 #include "abi/fold_predict.h"
 #include "abi/fold_pointwise.h"
 #include "abi/fold_derived.h"
+#include "abi/fold_check.h"
 
 // Host arithmetic only (no device): tools/peaks.c:130, 177-200 and the selection sort of src/gsl_helper.c:102-127.
 extern "C" int apemost_hip_peaks_table(const apemost_hip_peaks_view *v, int32_t n_par, int32_t k, int32_t p,

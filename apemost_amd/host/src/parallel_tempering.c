@@ -243,6 +243,11 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            2 .. 4096; auto sizes it for the samples the run plans) the fold keeps its tail, the largest
  *            leave-one-out log weights of every datum, and writes pointwise_tail.bin as well: `python -m
  *            apemost_amd.psis DIR` turns the two files into Pareto-smoothed leave-one-out and the Pareto k table
+ *   check    fold posterior predictive checks of chain 0 on the device: per datum the predictive CDF at the observed
+ *            value (PIT, leave-one-out PIT, the residual's moments), per kept sample the discrepancy statistics FIT,
+ *            EXTREME and SERIAL, histogrammed over the APEMOST_CHECK_BINS (1 .. 4096, default 256) null quantiles: at
+ *            the end write check.bin, check.txt and check_stats.txt (run_check.h).  Needs a built-in model, no
+ *            bounded run.  Combines with every other token and writes no sample file by itself, like pointwise
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -287,7 +292,7 @@ static void sink_parse(sample_sink *k) {
         else if ((fold = run_fold_find(spec)) >= 0)
             k->folds |= 1u << fold;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived, check; got '%s'\n", spec);
             exit(1);
         }
     }

@@ -903,6 +903,80 @@ class HipSampler:
                                                                out.ctypes.data_as(capi._dp)))
         return out[0] if one else out
 
+    # -- on-device predictive checks (apemost_amd/check.py) ---------------------------------------------
+    def check_begin(self, chains=(0,), nbins=256, edges=None, thin=1):
+        """start the fold of the predictive checks (apemost_amd/check.py, apemost_amd/csrc/pt_check.h) over the kept samples
+        of the local chains `chains` (strictly increasing), each on columns 0 and 1 of its own ladder's data as they are
+        now: per datum the predictive CDF at the observed value (PIT, leave-one-out PIT, the residual's moments), per
+        kept sample the three discrepancy statistics FIT, EXTREME and SERIAL, histogrammed over nbins slots.  edges
+        [3][nbins - 1]: the slots' edges per statistic; None: the null quantiles j / nbins of check.null_edges for the
+        kept chains' data length, so that the histogram is that of the posterior predictive p-value.  nbins = 1 keeps no
+        histogram.  The checks mean what they say for a chain at beta = 1: chain 0, the default."""
+        from . import check as ck
+        self._ck_chains = np.ascontiguousarray(chains, dtype=np.int32)
+        assert self._ck_chains.ndim == 1
+        self._ck_thin = int(thin)
+        lads = [int(c) // self.chains_per_ladder if self.n_ladders > 1 else 0
+                for c in self._ck_chains.tolist() if 0 <= c < self.n_chains]
+        lads = lads if len(lads) == len(self._ck_chains) else [0] * len(self._ck_chains)
+        self._ck_data = np.stack([_rectangle([self._x0[b] for b in lads]), _rectangle([self._y0[b] for b in lads])], axis=1)
+        if edges is None:
+            n_edges = int(nbins) - 1
+            lens = sorted({len(self._x0[b]) for b in lads})
+            if n_edges > 0 and len(lens) > 1:
+                raise ValueError("the kept chains' ladders hold %s data: the null quantiles depend on the length; pass "
+                                 "edges, or begin one fold per length" % lens)
+            edges = (np.stack([ck.null_edges(self.cfg.model, q, lens[0], n_edges) for q in range(ck.N_STATS)])
+                     if n_edges > 0 and lens else np.zeros((ck.N_STATS, 0)))
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if edges.ndim != 2 or edges.shape[0] != ck.N_STATS:
+            raise ValueError("edges: [3][n_edges], one ascending row per statistic")
+        self._ck_edges = edges
+        capi.check(self.L.apemost_hip_check_begin(self._h, len(self._ck_chains),
+                                                  self._ck_chains.ctypes.data_as(C.POINTER(C.c_int32)), edges.shape[1],
+                                                  edges.ctypes.data_as(capi._dp) if edges.shape[1] else None))
+
+    def check_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]; asynchronous
+        (check() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_check_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def check(self):
+        """the fold so far as a check.Check (synchronises with the accumulates issued so far)"""
+        from .check import Check
+        c = Check.empty(self._ck_chains, self._ck_data[:, 0], self._ck_data[:, 1], self._ck_edges, self.cfg.model,
+                        self.cfg.sigma, self._ck_thin, self.n_ladders)
+        capi.check(self.L.apemost_hip_check_get(self._h, C.byref(c.view())))
+        c.lengths = self._fold_lengths(self.L.apemost_hip_check_lengths, c.n_keep, c.n_data)
+        return c
+
+    def check_set(self, c):
+        """load a Check (a resumed run) into the fold begun with the same configuration"""
+        assert c.origin.shape == self._ck_data[:, 0].shape and np.array_equal(c.chains, self._ck_chains)
+        assert c.edges.tobytes() == self._ck_edges.tobytes()
+        capi.check(self.L.apemost_hip_check_set(self._h, C.byref(c.view())))
+
+    def check_end(self):
+        capi.check(self.L.apemost_hip_check_end(self._h))
+
+    def check_values(self, params, x, y):
+        """(e, u, T): the residual e and the predictive CDF u, [n][n_x] each, and the three statistics T [n][3] of the
+        parameter rows params [n][n_par] (or one row) over the caller's data x, y [n_x], by the fold's own device
+        functions: the stated meaning of what check_accumulate folds"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        one = params.ndim == 1
+        params = np.ascontiguousarray(params.reshape(-1, self.n_par))
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if len(x) != len(y):
+            raise ValueError("x holds %d values, y %d" % (len(x), len(y)))
+        e, u, T = np.zeros((len(params), len(x))), np.zeros((len(params), len(x))), np.zeros((len(params), 3))
+        capi.check(self.L.apemost_hip_check_values(self._h, len(params), params.ctypes.data_as(capi._dp), len(x),
+                                                   x.ctypes.data_as(capi._dp), y.ctypes.data_as(capi._dp),
+                                                   e.ctypes.data_as(capi._dp), u.ctypes.data_as(capi._dp),
+                                                   T.ctypes.data_as(capi._dp)))
+        return (e[0], u[0], T[0]) if one else (e, u, T)
+
     # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------
     def samples_text_bound(self, n_steps, skip=0, thin=1, n_param_chains=1):
         """(streams, host text bytes, device scratch bytes) of one samples_text batch"""

@@ -1243,6 +1243,84 @@ int apemost_hip_derived_end(apemost_hip_sampler *s);
  * fold's meaning.  APEMOST_HIP_ERR_INVALID without derived_begin. */
 int apemost_hip_derived_eval(apemost_hip_sampler *s, uint64_t n, const double *rows, double *out);
 
+/* ---- on-device predictive checks: PIT, leave-one-out PIT and discrepancy p-values without dumps ----
+ * Is the model adequate for these data?  Per datum (x_i, y_i) -- columns 0 and 1 of the sampler's data as they are at
+ * begin -- and kept sample of the kept chains, with v the model curve of apemost_hip_predict_* at x_i and l the term of
+ * apemost_hip_pointwise_* (the operation order is specified at the head of apemost_amd/csrc/pt_check.h):
+ *   simplesin, sine3    e = (y_i - v) * (1.0 / sigma), the standardised residual;  u = 0.5 * erfc(e * -sqrt(1/2));
+ *   pulse, pulse_vrot   e = y_i / v, the ratio, Exp(1) under the model;  u = -expm1(-e);
+ * u is the predictive CDF at y_i and a = u - 0.5.  A series is one (kept chain k, datum i) pair, s = k * n_data + i:
+ *   n                      kept samples so far;
+ *   origin[s], sum[s], sq[s]   e of the first sample and, with d = e - origin, the sequential sums of d and of d * d;
+ *   sum_u[s]               the sequential sum of u: pit_i = sum_u / n, the posterior predictive PIT;
+ *   m[s], S[s], SU[s]      the running log-sum-exp of -l (the pointwise fold's m_dn and S_dn, bit for bit) and the sum
+ *                          of u under the same weights: loo_pit_i = SU / S, the leave-one-out PIT.
+ * Per kept sample, three statistics T over the kept chain's L data, every sum in the fixed order of the joint
+ * predictive (64 lane partials by i % 64, then the adjacent-pairs tree):
+ *   APEMOST_CHECK_FIT      sine: sum e * e (null: chi^2 with L degrees of freedom); pulse: sum e (null: Gamma(L, 1));
+ *   APEMOST_CHECK_EXTREME  sine: max |e_i|; pulse: max e_i (a NaN is skipped; -inf where every term is NaN);
+ *   APEMOST_CHECK_SERIAL   sum over i >= 1 of a_i * a_{i-1}: null mean 0 and variance (L - 1) / 144; it sees an
+ *                          unmodelled periodic signal.
+ * Per kept chain and statistic q, at [k][q]: stat_origin, stat_sum, stat_sq (of T, as above), stat_min, stat_max (0
+ * before there is a sample; a NaN is skipped), and with n_edges > 0 the exact counts [k][q][n_edges + 2]: slot
+ * b = #{j : edges[q][j] <= T}, the last slot counts NaN.  With the edges at the null quantiles j / (n_edges + 1)
+ * (apemost_hip_check_null_edges) slot b holds the samples whose null CDF lies in [b, b + 1) / (n_edges + 1): the
+ * posterior predictive p-value of T to a half-width of 1 / (2 (n_edges + 1)).
+ * No filter: a non-finite v gives what IEEE arithmetic gives and touches its own kept chain's words only.  Every word
+ * equals a sequential host loop whatever the boundaries of the accumulate calls are.  Ladder batches, ragged batches and
+ * sharded ladders: as apemost_hip_pointwise_* (a kept chain takes its own ladder's data; apemost_hip_check_lengths).
+ * APEMOST_MODEL_USER: every entry point returns APEMOST_HIP_ERR_UNSUPPORTED, a user hook has no CDF. */
+#define APEMOST_CHECK_FIT 0
+#define APEMOST_CHECK_EXTREME 1
+#define APEMOST_CHECK_SERIAL 2
+#define APEMOST_CHECK_STATS 3
+#define APEMOST_CHECK_MAX_EDGES 4095
+typedef struct {
+    uint64_t *n;              /* kept samples */
+    double *origin, *sum, *sq, *sum_u, *m, *S, *SU; /* [n_keep][n_data] */
+    double *stat_origin, *stat_sum, *stat_sq, *stat_min, *stat_max; /* [n_keep][3] */
+    uint64_t *counts;         /* [n_keep][3][n_edges + 2] (nothing where n_edges == 0) */
+} apemost_hip_check_view; /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates and initialises the accumulator.  chains: host [n_keep], local chain indices, strictly increasing.
+ * edges: host [3][n_edges], per statistic finite and strictly ascending, or NULL with n_edges == 0 (no counts).  A fold
+ * begun before is dropped once the new configuration has been accepted; a refused begin leaves it as it was.
+ * APEMOST_HIP_ERR_INVALID, before any device work: n_keep or an index out of range, indices not strictly increasing,
+ * n_keep * n_data above 2^20 series, more than 512 parameters, n_edges outside [0, 4095], edges NULL with n_edges > 0,
+ * an edge that is not finite or not above the one before. */
+int apemost_hip_check_begin(apemost_hip_sampler *s, int32_t n_keep, const int32_t *chains, int32_t n_edges,
+                            const double *edges);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2]) in launches of at
+ * most 8192 kept steps; asynchronous and queued like apemost_hip_pointwise_accumulate.  APEMOST_HIP_ERR_INVALID, before
+ * any device work, without check_begin or with thin == 0. */
+int apemost_hip_check_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                 uint64_t thin);
+/* copies the accumulator out (synchronises with the accumulates issued so far) */
+int apemost_hip_check_get(apemost_hip_sampler *s, const apemost_hip_check_view *v);
+/* loads a view saved by check_get into a fold begun with the same configuration (a resumed run) */
+int apemost_hip_check_set(apemost_hip_sampler *s, const apemost_hip_check_view *v);
+/* len[n_keep]: the data kept chain k of the open fold really has (apemost_hip_pointwise_lengths' meaning): series past
+ * them are never written and keep their initial zeros */
+int apemost_hip_check_lengths(apemost_hip_sampler *s, int32_t *len);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_check_end(apemost_hip_sampler *s);
+/* the stated meaning: e, u host [n][n_x] and T host [n][3] of the caller's parameter rows params host [n][n_par] over
+ * the caller's data x, y host [n_x], by the fold's own device functions.  Synchronous; needs no fold and reads nothing
+ * of the sampler's data.  APEMOST_HIP_ERR_INVALID for n < 1, n_x < 1, a NULL array or n * n_x above 2^26. */
+int apemost_hip_check_values(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x, const double *x,
+                             const double *y, double *e, double *u, double *T);
+/* edges[j], j = 0 .. n_edges - 1: the null quantile (j + 1) / (n_edges + 1) of statistic `stat` of a built-in `model`
+ * over n_data data.  A host function: no sampler, no device.
+ *   FIT      exact: the regularised incomplete gamma function (series and continued fraction) inverted by bisection;
+ *   EXTREME  exact: erf(t / sqrt 2)^L for the sine models (bisection), (1 - exp(-t))^L for the pulse models (closed form);
+ *   SERIAL   approximate: the normal quantile with the exact null mean 0 and variance (L - 1) / 144; the statistic is
+ *            a sum of L - 1 bounded, 1-dependent terms and the approximation is poor for small L.  For n_data == 1 the
+ *            statistic is +0.0 whatever the data and has no null law: the edges are those of n_data == 2, so that a
+ *            fold can be begun, and its p-value means nothing.
+ * The edges are strictly ascending, SERIAL's symmetric about 0.  APEMOST_HIP_ERR_INVALID for n_data < 1, n_edges
+ * outside [1, 4095], an unknown stat or NULL edges; APEMOST_HIP_ERR_UNSUPPORTED for APEMOST_MODEL_USER. */
+int apemost_hip_check_null_edges(int32_t model, int32_t stat, int32_t n_data, int32_t n_edges, double *edges);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
