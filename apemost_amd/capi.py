@@ -138,6 +138,12 @@ class CheckView(C.Structure):
                 ("counts", _up)]
 
 
+class PeriodogramView(C.Structure):
+    _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("pmin", _dp), ("pmax", _dp), ("sum_c", _dp),
+                ("sum_s", _dp), ("exceed", _up), ("peak_origin", _dp), ("peak_sum", _dp), ("peak_sq", _dp), ("peak_min", _dp),
+                ("peak_max", _dp), ("peak_counts", _up)]
+
+
 class DerivedConfig(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("n_col", C.c_int32),
                 ("code", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("n_const", C.c_int32), ("consts", _dp),
@@ -204,6 +210,9 @@ EXPORTS = [
     "apemost_hip_derived_get", "apemost_hip_derived_set", "apemost_hip_derived_end", "apemost_hip_derived_eval",
     "apemost_hip_check_begin", "apemost_hip_check_accumulate", "apemost_hip_check_get", "apemost_hip_check_set",
     "apemost_hip_check_lengths", "apemost_hip_check_end", "apemost_hip_check_values", "apemost_hip_check_null_edges",
+    "apemost_hip_periodogram_begin", "apemost_hip_periodogram_accumulate", "apemost_hip_periodogram_get",
+    "apemost_hip_periodogram_set", "apemost_hip_periodogram_lengths", "apemost_hip_periodogram_end",
+    "apemost_hip_periodogram_values",
 ]
 
 _lib = None
@@ -366,6 +375,14 @@ def lib():
     L.apemost_hip_check_end.argtypes = [vp]
     L.apemost_hip_check_values.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp]
     L.apemost_hip_check_null_edges.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]
+    L.apemost_hip_periodogram_begin.argtypes = [vp, C.c_int32, ip, C.c_int32, _dp, _dp, _dp]
+    L.apemost_hip_periodogram_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_periodogram_get.argtypes = [vp, C.POINTER(PeriodogramView)]
+    L.apemost_hip_periodogram_set.argtypes = [vp, C.POINTER(PeriodogramView)]
+    L.apemost_hip_periodogram_lengths.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.apemost_hip_periodogram_end.argtypes = [vp]
+    L.apemost_hip_periodogram_values.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp,
+                                                 _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]
     L.apemost_hip_derived_check.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int32, ip]
     L.apemost_hip_derived_begin.argtypes = [vp, C.POINTER(DerivedConfig)]
     L.apemost_hip_derived_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]

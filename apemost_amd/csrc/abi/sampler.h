@@ -205,6 +205,29 @@ struct CheckFold {
     FoldMem mem;
 };
 
+// on-device residual periodogram (pt_periodogram.h): the power of every kept sample's residuals on a frequency grid
+struct PeriodogramFold {
+    bool open;
+    int n_keep;
+    int n_data; // the width of every [n_keep][n_data] array: the longest data among the kept chains' ladders
+    int n_freq;
+    int piece;  // kept steps of one launch: what the scratch arrays have room for, <= kPeriodogramPiece
+    u64 n;
+    int *d_chains;
+    int *d_len;          // [n_keep] data per kept chain where they differ (a ragged batch), else nullptr
+    double *d_x, *d_y;   // [n_keep][n_data]
+    double *d_freqs, *d_weights, *d_level; // [n_freq], [n_keep][n_freq][3], [n_keep]
+    double *d_state;     // the seven [n_keep][n_freq] words, one after the other (kPeriodogramWords)
+    u64 *d_exceed;       // [n_keep][n_freq]
+    double *d_peak;      // origin, sum, sq, min, max: [n_keep] each, one after the other (kPeriodogramPeakWords)
+    u64 *d_peak_counts;  // [n_keep][n_freq + 1]
+    double *d_r;         // [n_keep][piece][n_data]: a piece's residuals
+    double *d_C, *d_S, *d_P; // [n_keep][piece][n_freq] each
+    double *d_pk_m;      // [n_keep][piece]
+    int *d_pk_arg;       // [n_keep][piece]
+    FoldMem mem;
+};
+
 } // namespace
 
 struct apemost_hip_sampler {
@@ -304,6 +327,7 @@ struct apemost_hip_sampler {
     PointwiseFold pw;
     DerivedFold dv;
     CheckFold ck;
+    PeriodogramFold pg;
 };
 
 // the data rows of ladder b and its column-major matrix on the device (an ordinary sampler: b = 0)
@@ -360,6 +384,7 @@ static void release(apemost_hip_sampler *s) {
     fold_free(s->pw);
     fold_free(s->dv);
     fold_free(s->ck);
+    fold_free(s->pg);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {

@@ -248,6 +248,12 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            EXTREME and SERIAL, histogrammed over the APEMOST_CHECK_BINS (1 .. 4096, default 256) null quantiles: at
  *            the end write check.bin, check.txt and check_stats.txt (run_check.h).  Needs a built-in model, no
  *            bounded run.  Combines with every other token and writes no sample file by itself, like pointwise
+ *   periodogram  fold the residual periodogram of chain 0 on the device: per kept sample the Lomb-Scargle power of
+ *            y - model on the grid APEMOST_PERIODOGRAM_FREQS=lo:hi:n (required; n in 1 .. 2^20), per frequency its
+ *            moments, extremes, the power of the mean residual and the count above -ln(0.01 / n), and the histogram
+ *            of the highest peak's frequency: at the end write periodogram.bin and periodogram.txt
+ *            (run_periodogram.h).  Needs a bounded run and simplesin or sine3.  Combines with every other token and
+ *            writes no sample file by itself, like check
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -292,7 +298,7 @@ static void sink_parse(sample_sink *k) {
         else if ((fold = run_fold_find(spec)) >= 0)
             k->folds |= 1u << fold;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived, check; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived, check, periodogram; got '%s'\n", spec);
             exit(1);
         }
     }

@@ -9,7 +9,7 @@
 
 /* In the order the folds open and close.  Only summary and evidence fold every chain, so one fold per shard; the
  * others fold chain 0, which lives on shard 0.  joint and autocorr size nothing by the samples to come and run
- * unbounded too, and so does check; predict needs the bound only for its refusal. */
+ * unbounded too, and so does check; predict needs the bound only for its refusal, and so does periodogram. */
 const run_fold run_folds[RUN_FOLDS] = {
     {"summary", BATCH_SIZE_WHY, 1, run_summary_open, run_summary_close, apemost_hip_summary_accumulate},
     {"peaks", "the columns kept on the device are sized before the first sample", 0, run_peaks_open, run_peaks_close,
@@ -22,7 +22,9 @@ const run_fold run_folds[RUN_FOLDS] = {
      apemost_hip_predict_accumulate},
     {"pointwise", "pointwise.bin, pointwise.txt and criteria.txt are written when the run ends", 0, run_pointwise_open,
      run_pointwise_close, apemost_hip_pointwise_accumulate},
-    {"check", NULL, 0, run_check_open, run_check_close, apemost_hip_check_accumulate}};
+    {"check", NULL, 0, run_check_open, run_check_close, apemost_hip_check_accumulate},
+    {"periodogram", "periodogram.bin and periodogram.txt are written when the run ends", 0, run_periodogram_open,
+     run_periodogram_close, apemost_hip_periodogram_accumulate}};
 
 static int item_is(const char *spec, const char *token) {
     const size_t len = strlen(token);
@@ -60,6 +62,8 @@ void run_folds_check(unsigned int mask) {
         (void)run_pointwise_tail_from_env();
     if (in_mask(mask, "check"))
         (void)run_check_bins_from_env();
+    if (in_mask(mask, "periodogram"))
+        run_periodogram_check_env();
 #ifdef HISTOGRAMS_MINMAX
     if (in_mask(mask, "summary")) {
         fprintf(stderr, "APEMOST_DUMP=summary cannot be combined with -DHISTOGRAMS_MINMAX: the histogram range "

@@ -977,6 +977,92 @@ class HipSampler:
                                                    T.ctypes.data_as(capi._dp)))
         return (e[0], u[0], T[0]) if one else (e, u, T)
 
+    # -- on-device residual periodogram (apemost_amd/periodogram.py) -------------------------------------
+    def periodogram_begin(self, chains=(0,), freqs=None, kind="lomb_scargle", sigma=None, weights=None, level=np.inf,
+                          thin=1):
+        """start the fold of the residual periodogram (apemost_amd/periodogram.py, apemost_amd/csrc/pt_periodogram.h) over
+        the kept samples of the local chains `chains` (strictly increasing), each on columns 0 and 1 of its own ladder's
+        data as they are now: per kept sample the power of y - model on the frequencies `freqs` [n_freq] (any doubles, in
+        any order), folded per frequency into moments, extremes, the coherent amplitude and the count above `level` (one
+        number, or one per kept chain), and per kept chain into the histogram of the highest peak's frequency.  weights
+        [n_keep][n_freq][3] (or [n_freq][3] for every kept chain): the quadratic form's; None: periodogram.weights of
+        `kind` over each kept chain's abscissae with `sigma` (None: the sampler's).  simplesin and sine3 only."""
+        from . import periodogram as pg
+        if freqs is None:
+            raise ValueError("freqs: the frequency grid [n_freq]")
+        self._pg_chains = np.ascontiguousarray(chains, dtype=np.int32)
+        assert self._pg_chains.ndim == 1
+        self._pg_thin = int(thin)
+        n_keep = len(self._pg_chains)
+        self._pg_freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        lads = [int(c) // self.chains_per_ladder if self.n_ladders > 1 else 0
+                for c in self._pg_chains.tolist() if 0 <= c < self.n_chains]
+        lads = lads if len(lads) == n_keep else [0] * n_keep
+        sigma = self.cfg.sigma if sigma is None else float(sigma)
+        if weights is None:
+            by_ladder = {b: pg.weights(self._x0[b], self._pg_freqs, kind, sigma) for b in sorted(set(lads))}
+            weights = np.stack([by_ladder[b] for b in lads]) if lads else np.zeros((0, len(self._pg_freqs), 3))
+        weights = np.asarray(weights, dtype=np.float64)
+        if weights.ndim == 2:
+            weights = np.broadcast_to(weights, (n_keep,) + weights.shape)
+        if weights.shape != (n_keep, len(self._pg_freqs), 3):
+            raise ValueError("weights: [n_keep][n_freq][3], here %r for %d kept chains and %d frequencies"
+                             % (weights.shape, n_keep, len(self._pg_freqs)))
+        self._pg_weights = np.ascontiguousarray(weights)
+        self._pg_level = np.ascontiguousarray(np.broadcast_to(np.asarray(level, dtype=np.float64), (n_keep,)))
+        self._pg_sigma = sigma
+        capi.check(self.L.apemost_hip_periodogram_begin(self._h, n_keep, self._pg_chains.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        len(self._pg_freqs), self._pg_freqs.ctypes.data_as(capi._dp),
+                                                        self._pg_weights.ctypes.data_as(capi._dp),
+                                                        self._pg_level.ctypes.data_as(capi._dp)))
+
+    def periodogram_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """fold the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]; asynchronous
+        (periodogram() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_periodogram_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def periodogram(self):
+        """the fold so far as a periodogram.Periodogram (synchronises with the accumulates issued so far)"""
+        from .periodogram import Periodogram
+        lens = np.zeros(len(self._pg_chains), dtype=np.int32)
+        capi.check(self.L.apemost_hip_periodogram_lengths(self._h, lens.ctypes.data_as(C.POINTER(C.c_int32))))
+        p = Periodogram.empty(self._pg_chains, self._pg_freqs, self._pg_weights, self._pg_level, lens, self.cfg.model,
+                              self._pg_sigma, self._pg_thin, self.n_ladders)
+        capi.check(self.L.apemost_hip_periodogram_get(self._h, C.byref(p.view())))
+        return p
+
+    def periodogram_set(self, p):
+        """load a Periodogram (a resumed run) into the fold begun with the same configuration"""
+        assert np.array_equal(p.chains, self._pg_chains) and p.freqs.tobytes() == self._pg_freqs.tobytes()
+        assert p.weights.tobytes() == self._pg_weights.tobytes() and p.level.tobytes() == self._pg_level.tobytes()
+        capi.check(self.L.apemost_hip_periodogram_set(self._h, C.byref(p.view())))
+
+    def periodogram_end(self):
+        capi.check(self.L.apemost_hip_periodogram_end(self._h))
+
+    def periodogram_values(self, params, x, y, freqs, weights):
+        """a dict of r [n][n_x], the table c, s [n_freq][n_x], C, S, P [n][n_freq], peak [n] and arg [n] (int32) of the
+        parameter rows params [n][n_par] over the caller's data x, y [n_x], frequencies [n_freq] and weights
+        [n_freq][3], by the fold's own device functions: the stated meaning of what periodogram_accumulate folds"""
+        params = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1, self.n_par))
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if len(x) != len(y):
+            raise ValueError("x holds %d values, y %d" % (len(x), len(y)))
+        if weights.shape != (len(freqs), 3):
+            raise ValueError("weights: [n_freq][3], here %r for %d frequencies" % (weights.shape, len(freqs)))
+        n, nx, nf = len(params), len(x), len(freqs)
+        out = dict(r=np.zeros((n, nx)), c=np.zeros((nf, nx)), s=np.zeros((nf, nx)), C=np.zeros((n, nf)), S=np.zeros((n, nf)),
+                   P=np.zeros((n, nf)), peak=np.zeros(n), arg=np.zeros(n, dtype=np.int32))
+        dp = capi._dp
+        capi.check(self.L.apemost_hip_periodogram_values(
+            self._h, n, params.ctypes.data_as(dp), nx, x.ctypes.data_as(dp), y.ctypes.data_as(dp), nf,
+            freqs.ctypes.data_as(dp), weights.ctypes.data_as(dp), *[out[f].ctypes.data_as(dp) for f in "rcsCSP"],
+            out["peak"].ctypes.data_as(dp), out["arg"].ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
     # -- the reference's text dumps, formatted on the device (apemost_amd/csrc/pt_text.h) -----------------
     def samples_text_bound(self, n_steps, skip=0, thin=1, n_param_chains=1):
         """(streams, host text bytes, device scratch bytes) of one samples_text batch"""

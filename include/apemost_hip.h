@@ -1321,6 +1321,69 @@ int apemost_hip_check_values(apemost_hip_sampler *s, int32_t n, const double *pa
  * outside [1, 4095], an unknown stat or NULL edges; APEMOST_HIP_ERR_UNSUPPORTED for APEMOST_MODEL_USER. */
 int apemost_hip_check_null_edges(int32_t model, int32_t stat, int32_t n_data, int32_t n_edges, double *edges);
 
+/* ---- on-device residual periodogram: posterior power on a frequency grid without dumps ----
+ * What is left in the residuals, and at which frequency?  For APEMOST_MODEL_SIMPLESIN and APEMOST_MODEL_SINE3.  Per kept
+ * sample of the kept chains, with (x_i, y_i) columns 0 and 1 of the kept chain's own ladder's data as they are at begin,
+ * r_i = y_i - v the residual of apemost_hip_check_* before its scaling, and nu_j the caller's frequencies (the operation
+ * order is specified at the head of apemost_amd/csrc/pt_periodogram.h):
+ *   s_ij = sin(2 pi nu_j x_i), c_ij = sin(2 pi (nu_j x_i + 0.25)), the device sine of the likelihoods (NaN out of its range);
+ *   C_j = sum_i r_i c_ij, S_j = sum_i r_i s_ij, fused multiply-adds from +0.0 in ascending i;
+ *   P_j = ((wcc C) C + (wcs C) S) + (wss S) S with the caller's weights (wcc, wcs, wss) of [k][j]: a quadratic form, whose
+ *   normalisation (Lomb-Scargle, Schuster, squared amplitude) is the host's (apemost_amd/periodogram.py).
+ * A series is one (kept chain k, frequency j) pair, s = k * n_freq + j:
+ *   n                      kept samples so far;
+ *   origin[s], sum[s], sq[s]   P of the first sample and, with d = P - origin, the sequential sums of d and of d * d;
+ *   pmin[s], pmax[s]       the extremes of P (a NaN is skipped; 0 before there is a sample);
+ *   sum_c[s], sum_s[s]     the sequential sums of C and S: the periodogram of the mean residual follows by linearity;
+ *   exceed[s]              #{t : P > level[k]} (a NaN P is not counted).
+ * Per kept sample the highest peak m = max_j P_j and arg, the first j that holds it (n_freq where no P is above -inf; a
+ * NaN never wins); per kept chain k: peak_origin, peak_sum, peak_sq, peak_min, peak_max of m, and peak_counts[k][arg]++
+ * over [n_freq + 1] slots.
+ * No filter: non-finite values touch their own kept chain's words only.  Every word equals a sequential host loop
+ * whatever the boundaries of the accumulate calls are.  Ladder batches, ragged batches and sharded ladders: as
+ * apemost_hip_check_* (a kept chain takes its own ladder's data; apemost_hip_periodogram_lengths).
+ * APEMOST_MODEL_PULSE, APEMOST_MODEL_PULSE_VROT (their data already are a power spectrum) and APEMOST_MODEL_USER (no
+ * residual law here): every entry point returns APEMOST_HIP_ERR_UNSUPPORTED. */
+#define APEMOST_PERIODOGRAM_MAX_FREQ (1 << 20)
+#define APEMOST_PERIODOGRAM_PIECE 512
+typedef struct {
+    uint64_t *n;              /* kept samples */
+    double *origin, *sum, *sq, *pmin, *pmax, *sum_c, *sum_s; /* [n_keep][n_freq] */
+    uint64_t *exceed;         /* [n_keep][n_freq] */
+    double *peak_origin, *peak_sum, *peak_sq, *peak_min, *peak_max; /* [n_keep] */
+    uint64_t *peak_counts;    /* [n_keep][n_freq + 1] */
+} apemost_hip_periodogram_view; /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates and initialises the accumulator.  chains: host [n_keep], local chain indices, strictly increasing.  freqs:
+ * host [n_freq], any doubles but NaN, in any order.  weights: host [n_keep][n_freq][3] = (wcc, wcs, wss); level: host
+ * [n_keep].  A fold begun before is dropped once the new configuration has been accepted; a refused begin leaves it as
+ * it was.  APEMOST_HIP_ERR_INVALID, before any device work: n_keep or an index out of range, indices not strictly
+ * increasing, n_keep * n_data above 2^20 or n_keep * n_freq above 2^24 series, more than 512 parameters, n_freq outside
+ * [1, 2^20], a NULL array, a NaN in freqs, weights or level (an infinite weight or level is allowed). */
+int apemost_hip_periodogram_begin(apemost_hip_sampler *s, int32_t n_keep, const int32_t *chains, int32_t n_freq,
+                                  const double *freqs, const double *weights, const double *level);
+/* folds the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2]) in launches of at
+ * most 512 kept steps; asynchronous and queued like apemost_hip_check_accumulate.  APEMOST_HIP_ERR_INVALID, before any
+ * device work, without periodogram_begin or with thin == 0. */
+int apemost_hip_periodogram_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                       uint64_t thin);
+/* copies the accumulator out (synchronises with the accumulates issued so far) */
+int apemost_hip_periodogram_get(apemost_hip_sampler *s, const apemost_hip_periodogram_view *v);
+/* loads a view saved by periodogram_get into a fold begun with the same configuration (a resumed run) */
+int apemost_hip_periodogram_set(apemost_hip_sampler *s, const apemost_hip_periodogram_view *v);
+/* len[n_keep]: the data kept chain k of the open fold really has (apemost_hip_check_lengths' meaning) */
+int apemost_hip_periodogram_lengths(apemost_hip_sampler *s, int32_t *len);
+/* frees the accumulator (apemost_hip_destroy does too) */
+int apemost_hip_periodogram_end(apemost_hip_sampler *s);
+/* the stated meaning: for the caller's parameter rows params host [n][n_par], data x, y host [n_x], freqs host [n_freq]
+ * and weights w host [n_freq][3]: r host [n][n_x], the table c, s host [n_freq][n_x], C, S, P host [n][n_freq], peak host
+ * [n] and arg host [n], by the fold's own device functions.  Synchronous; needs no fold and reads nothing of the sampler's
+ * data.  APEMOST_HIP_ERR_INVALID for n < 1, n_x < 1, n_freq outside [1, 2^20], a NULL array, or one of n * n_x,
+ * n_freq * n_x and n * n_freq above 2^26. */
+int apemost_hip_periodogram_values(apemost_hip_sampler *s, int32_t n, const double *params, int32_t n_x, const double *x,
+                                   const double *y, int32_t n_freq, const double *freqs, const double *w, double *r,
+                                   double *c, double *s_out, double *C, double *S, double *P, double *peak, int32_t *arg);
+
 /* ---- replica flow (APEMOST_HIP_FLAG_TRACK_REPLICAS; the specification is at the flag) ---------
  * Without the flag all three return APEMOST_HIP_ERR_UNSUPPORTED. */
 typedef struct {
