@@ -44,10 +44,8 @@ __host__ __device__ constexpr bool has_producer(int waves) { return waves >= 4; 
 //   pulse      256 x  1024 (n_swap  1): 7.84e7 /   -    / 7.81e7     128 x 16384: 2.43e7 / 2.60e7
 //   pulse      256 x  1024 (n_swap  7): 1.19e8 / 0.89e8 / 1.04e8     128 x 65536: 6.7e6 / 7.2e6
 // With 2 it loses to 4 (128 x 1024: 1.48e8): the data vector no longer fits the registers.
-#ifndef APEMOST_OB_WAVES_MASK
-#define APEMOST_OB_WAVES_MASK 0x110
-#endif
-__host__ __device__ constexpr bool has_one_barrier(int waves) { return (APEMOST_OB_WAVES_MASK >> waves) & 1; }
+constexpr unsigned kObWavesMask = 0x110; // bit w: there is a kernel with w likelihood waves
+__host__ __device__ constexpr bool has_one_barrier(int waves) { return (kObWavesMask >> waves) & 1; }
 __host__ __device__ constexpr int block_threads(int waves, bool) { return waves * kWave; }
 // Which instantiations of pt_round_ob_kernel take a ladder's own data length from its ladder words (ladder_view).
 // All but one: the pulse_vrot variant with eight likelihood waves, the data read through L2 and a helper wavefront.  With
@@ -471,7 +469,8 @@ __device__ __forceinline__ void swap_in_launch(E &e, const DevArrays &d, const C
 
 // (the pulse model's one-wave kernel sits at the edge of three resident waves per SIMD, 168 registers:
 // ladders of 1500+ chains run 2048: 1.29 vs 1.54e8 steps/s with two)
-constexpr int round_min_waves(int model, int waves) { return model % kVariantModel == APEMOST_MODEL_PULSE && waves == 1 ? APEMOST_PULSE_MIN_WAVES : 1; }
+constexpr int kPulseMinWaves = 3;
+constexpr int round_min_waves(int model, int waves) { return model % kVariantModel == APEMOST_MODEL_PULSE && waves == 1 ? kPulseMinWaves : 1; }
 template <int MODEL, int WAVES, bool LDS_DATA, bool PROD>
 __global__ __launch_bounds__(block_threads(WAVES, PROD)) __attribute__((amdgpu_waves_per_eu(round_min_waves(MODEL, WAVES), 8)))
 void pt_round_kernel(const RoundArgs grid) {
@@ -545,9 +544,6 @@ void pt_round_kernel(const RoundArgs grid) {
 // Diagnostic build (-DAPEMOST_STAMPS): per wave of workgroup 0, the cycles between leaving a step's
 // barrier and arriving at the next one (g_stamps[wave]); g_stamps[15] = whole steps of the owner,
 // barrier to barrier.  Tells which role the others wait for.
-#ifndef APEMOST_MERGED_ALL
-#define APEMOST_MERGED_ALL 0 // (experiment: the sine models' round kernel through attempts2() too; see ObEngine::owner_publish)
-#endif
 #ifdef APEMOST_STAMPS
 #define OB_STAMP_DECL u64 ob_busy = 0, ob_t0 = 0, ob_total = 0, ob_prev = 0
 #define OB_STAMP_BEGIN ob_t0 = __builtin_amdgcn_s_memtime()
@@ -562,12 +558,11 @@ void pt_round_kernel(const RoundArgs grid) {
 #define OB_STAMP_FLUSH
 #endif
 
-// APEMOST_OWNER_PRIO_PHASE (experiment, round 4): the owner at APEMOST_OWNER_PRIO for the first part of its step only
-// -- up to the decision and bookkeeping (3), up to the proposal in flight (2), up to the prepared proposals (1) --
-// and at priority 0 for the rest: the likelihood wave on its SIMD is the last at the barrier, the owner is not.
-#ifndef APEMOST_OWNER_PRIO_PHASE
-#define APEMOST_OWNER_PRIO_PHASE 0
-#endif
+// s_setprio levels of the one-barrier kernels: the owner's, for its whole step (dropping it for the step's later part
+// lost 0.5-12 %, profiles/r04_owner_prio_phase.txt), and, with a helper wavefront, likelihood wave 0's (see where it is set)
+constexpr int kOwnerPrio = 3;
+constexpr int kLik0Prio = 3;
+
 // The rounds base .. base+63 of this launch whose opening swap attempt involves chain c (bit r - base):
 // lane l draws the pair of round base + l from the replicated swap stream.  A swap attempt touches
 // its two chains only (src/parallel_tempering_interaction.c:99-141): for every other chain the
@@ -602,10 +597,6 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
     if constexpr (ob_takes_ladder_length(MODEL, LW, LDS_DATA, HELPER))
         ladder_length<MODEL>(a, c);
     e.setup_common(a.d, a.sh, c, lds);
-#if APEMOST_OB_HELPER_SIMD
-    if (HELPER && e.hw > LW + 3 && !e.is_helper())
-        return; // (placeholders: see APEMOST_OB_HELPER_SIMD)
-#endif
     OB_STAMP_DECL;
     // bit r % 64: the pipeline restarts at the start of round r (parity 0, the owner's first proposal
     // from the current point, one barrier more): at the launch's start and where a swap attempt moves
@@ -622,11 +613,8 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
         // 1440, the helper 1490: profiles/r04_pulse_helper_wave.txt): it goes first on its SIMD.  Config 4 2.69 ->
         // 2.71e8 steps/s whatever the owner's priority.  Without the helper the owner is the last wave and this
         // costs 20 % (config 2: 2.14 -> 1.69e8).
-#ifndef APEMOST_LIK0_PRIO
-#define APEMOST_LIK0_PRIO 3
-#endif
         if (HELPER && e.hw == 0)
-            __builtin_amdgcn_s_setprio(APEMOST_LIK0_PRIO);
+            __builtin_amdgcn_s_setprio(kLik0Prio);
         int p = 0; // parity of the step about to start
         for (unsigned r = 0; r < a.n_rounds; r++) {
             if ((r & 63) == 0)
@@ -682,9 +670,6 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
     } else if (e.is_helper()) {
         // (HELPER) the helper alone: the barrier sequence of a producer, helper_step per step
         if constexpr (decltype(e)::kHelperWave) {
-#ifdef APEMOST_HELPER_PRIO
-            __builtin_amdgcn_s_setprio(APEMOST_HELPER_PRIO); // (experiment, round 4: tools/experiments/r04_session14.sh)
-#endif
             e.setup_lanes(a.sh, c);
             e.setup_helper(a.d, a.sh, c);
             __syncthreads();
@@ -710,10 +695,7 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
         }
     } else {
         // the others wait for this wave at every barrier and it has little to issue: let it go first
-#ifndef APEMOST_OWNER_PRIO
-#define APEMOST_OWNER_PRIO 3
-#endif
-        __builtin_amdgcn_s_setprio(APEMOST_OWNER_PRIO);
+        __builtin_amdgcn_s_setprio(kOwnerPrio);
         e.setup_lanes(a.sh, c);
         e.setup_owner(a.d, a.sh, c);
         chain_load(e, a.d, a.sh, c, a.cur);
@@ -754,13 +736,8 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
 #endif
                 // one batch of LDS reads: the redraw flag, what the prepared proposals settled on
                 // for my parameter, and (owner_results) the partial sums
-#if APEMOST_OWNER_PRIO_PHASE
-                __builtin_amdgcn_s_setprio(APEMOST_OWNER_PRIO); // (dropped in the step's later part, see below)
-#endif
                 const int pending = *e.s_flag(p);
-#if APEMOST_HOIST_CAND
                 const double2 nx = e.owner_fetch_next_cand(); // (with the step's first batch of LDS reads)
-#endif
                 if (open) {
                     e.owner_fetch_selected(p);
                     e.owner_results(p, my_sample);
@@ -768,33 +745,13 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
                         my_sample += sample_stride;
                 }
                 const bool redraw_pending = __builtin_amdgcn_readfirstlane(pending) != 0;
-#if APEMOST_OWNER_PRIO_PHASE == 3
-                __builtin_amdgcn_s_setprio(0);
-#endif
                 e.owner_choose(p, !open);
-#if APEMOST_OWNER_PRIO_PHASE == 2
-                __builtin_amdgcn_s_setprio(0);
-#endif
                 if (redraw_pending) // rare: a proposal in LDS has just been replaced
                     __syncthreads();
-#if !APEMOST_HOIST_CAND
-                const double2 nx = e.owner_fetch_next_cand();
-#endif
-#ifdef APEMOST_EXP_OWNER_SLACK
-                // TIMING ONLY (results are garbage; tools/experiments/r04_slack.sh): the owner arrives at the
-                // step's barrier with half of its work done and publishes behind it -- what a step costs when
-                // nobody waits for the owner's whole program (the two-step look-ahead of DESIGN.md 9 would
-                // give it that slack).  The redraw flag is never set in this build.
-                __syncthreads();
-                e.template owner_publish<Model<MODEL % kVariantModel>::kHasPrior || APEMOST_MERGED_ALL>(p, nx);
-                e.tick++;
-                OB_STAMP_END;
-#else
-                e.template owner_publish<Model<MODEL % kVariantModel>::kHasPrior || APEMOST_MERGED_ALL>(p, nx);
+                e.template owner_publish<Model<MODEL % kVariantModel>::kHasPrior>(p, nx);
                 e.tick++;
                 OB_STAMP_END;
                 __syncthreads();
-#endif
 #ifdef APEMOST_STAMPS
                 ob_total += __builtin_amdgcn_s_memtime() - ob_t0;
 #endif
@@ -1011,14 +968,12 @@ __device__ __forceinline__ void calib_log_progress(const E &e, const CalibArgs &
     }
 }
 
-#ifndef APEMOST_CALIB_MIN_WAVES
-#define APEMOST_CALIB_MIN_WAVES(waves) ((waves) == 1 ? 2 : 1)
-#endif
 // (one-wave workgroups: at least two of them per SIMD, i.e. at most 256 registers -- the state machine
 // around the step costs the compiler a dozen registers more than the round kernel has, and a ladder of
 // 2048 chains wants both of its waves per SIMD resident)
+constexpr int calib_min_waves(int waves) { return waves == 1 ? 2 : 1; }
 template <int MODEL, int WAVES, bool LDS_DATA, bool PROD>
-__global__ __launch_bounds__(block_threads(WAVES, PROD)) __attribute__((amdgpu_waves_per_eu(APEMOST_CALIB_MIN_WAVES(WAVES), 8)))
+__global__ __launch_bounds__(block_threads(WAVES, PROD)) __attribute__((amdgpu_waves_per_eu(calib_min_waves(WAVES), 8)))
 void pt_calibrate_kernel(const CalibArgs grid) {
     extern __shared__ __align__(16) double lds[];
     // The state machine's record lives in LDS, in the six control doubles behind the fail flag: it is
@@ -1193,10 +1148,6 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
     const int slot = a.list[blockIdx.x];
     const int c = a.first + slot;
     e.setup_common(a.d, a.sh, c, lds);
-#if APEMOST_OB_HELPER_SIMD
-    if (HELPER && e.hw > LW + 3 && !e.is_helper())
-        return; // (placeholders: see APEMOST_OB_HELPER_SIMD)
-#endif
     volatile int *s_steps = (volatile int *)(lds + kObCtl); // word 0 (word 2 is the fail flag)
     if (e.is_lik()) {
         e.setup_lik(a.d, a.sh, c);
@@ -1260,7 +1211,7 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
             }
         }
     } else {
-        __builtin_amdgcn_s_setprio(APEMOST_OWNER_PRIO);
+        __builtin_amdgcn_s_setprio(kOwnerPrio);
         const int n = a.sh.n_par;
         const apemost_hip_calib_config &cfg = a.cfg;
         e.setup_lanes(a.sh, c);
@@ -1323,9 +1274,7 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
             int which_prev = -1;         // ... and what the step in flight proposed
             for (int s = 0; s < n_steps; s++) {
                 const int pending = *e.s_flag(p);
-#if APEMOST_HOIST_CAND
                 const double2 nx = e.owner_fetch_next_cand();
-#endif
                 if (open) {
                     e.owner_fetch_selected(p);
                     e.owner_results(p, nullptr, which_prev, !burn);
@@ -1335,9 +1284,6 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
                 if (redraw_pending)
                     __syncthreads();
                 const int which_next = !sweep ? -1 : (which + 1 == n ? 0 : which + 1);
-#if !APEMOST_HOIST_CAND
-                const double2 nx = e.owner_fetch_next_cand();
-#endif
                 e.template owner_publish<true>(p, nx, which_next);
                 e.tick++;
                 __syncthreads();

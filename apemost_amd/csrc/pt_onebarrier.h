@@ -138,41 +138,22 @@ struct ObThreshold<APEMOST_MODEL_PULSE_VROT> : ObThreshold<APEMOST_MODEL_PULSE> 
     } while (0)
 #endif
 
-#ifndef APEMOST_OB_WAVE_PERM
-#define APEMOST_OB_WAVE_PERM 0
-#endif
-// The likelihood waves' step, read in the code object (round 4, profiles/r04_lik_step_microfixes.txt): measured on, kept on.
-#ifndef APEMOST_OB_SKIP_LOOPS
-#define APEMOST_OB_SKIP_LOOPS 1
-#endif
-#ifndef APEMOST_OB_PART_FIRST
-#define APEMOST_OB_PART_FIRST 1
-#endif
-#ifndef APEMOST_OB_FLAG_LATE
-#define APEMOST_OB_FLAG_LATE 0
-#endif
 // HELPER: a ninth (LW + 5th) wavefront that computes the proposal's half of the threshold (the prior's logarithms);
 // for the models with a prior only, and only where the host finds one workgroup per CU (nine-wave workgroups do not
 // fit a CU twice under the kernel's register budget: ladders of 257-512 chains keep the eight-wave form).
 __host__ __device__ constexpr bool ob_can_help(int model) {
     return model % kVariantModel == APEMOST_MODEL_PULSE || model % kVariantModel == APEMOST_MODEL_PULSE_VROT;
 }
-// (experiment, round 4: APEMOST_OB_HELPER_SIMD = s puts s wavefronts that end at once between the producers and the
-// helper, so that the helper -- wave w runs on SIMD w mod 4 -- lands on SIMD s instead of beside likelihood wave 0 and the owner)
-#ifndef APEMOST_OB_HELPER_SIMD
-#define APEMOST_OB_HELPER_SIMD 0
-#endif
-__host__ __device__ constexpr int ob_block(int lw, bool helper) { return (lw + 4 + (helper ? 1 + APEMOST_OB_HELPER_SIMD : 0)) * kWave; }
+__host__ __device__ constexpr int ob_block(int lw, bool helper) { return (lw + 4 + (helper ? 1 : 0)) * kWave; }
 
 // Register budget of the one-barrier kernels: waves per SIMD the compiler must leave room for.  Eight- and twelve-wave
 // workgroups share a CU two by two (4 per SIMD: 128 registers); the nine-wave ones (four likelihood waves + helper)
 // have a CU to themselves, three waves on SIMD 0: 168 registers, the calibration kernel stops spilling (12-13
 // registers at 128) -- config 4 2.668 -> 2.697e8 steps/s, calibration 0.328 -> 0.320 s (profiles/r04_pulse_helper_wave.txt).
-#ifndef APEMOST_OB_HELPER_EU
-#define APEMOST_OB_HELPER_EU 3
-#endif
+constexpr int kObWavesPerEu = 4;
+constexpr int kObHelperEu = 3;
 __host__ __device__ constexpr int ob_waves_per_eu(int lw, bool helper) {
-    return helper && lw == 4 ? APEMOST_OB_HELPER_EU : APEMOST_OB_WAVES_PER_EU;
+    return helper && lw == 4 ? kObHelperEu : kObWavesPerEu;
 }
 
 template <int MODEL, int LW, bool LDS_DATA, bool HELPER = false>
@@ -187,15 +168,11 @@ struct ObEngine {
     static constexpr int kBlock = ob_block(LW, HELPER);
     static constexpr bool kHelperWave = HELPER; // the proposal's half of the threshold comes from a wavefront of its own
     static constexpr int kWide = LW < 8 ? 4 : 2;
-    static constexpr int kShortChain = LW >= APEMOST_SHORT_CHAIN_WAVES ? 1 : LW >= APEMOST_EVEN_ODD_WAVES ? 2 : 0;
     static constexpr bool kVariants = MODEL >= kVariantModel; // see kVariantModel (pt_device.h)
     static constexpr int kBase = MODEL % kVariantModel;
     static constexpr bool kSine = kBase == APEMOST_MODEL_SIMPLESIN || kBase == APEMOST_MODEL_SINE3;
     static constexpr bool kUser = Model<kBase>::kIndexed; // a user-supplied model: the decision through finish()
-#ifndef APEMOST_PHILOX_MERGED
-#define APEMOST_PHILOX_MERGED 2 // 0: never, 1: always, 2: the sine models
-#endif
-    static constexpr bool kMergedPhilox = APEMOST_PHILOX_MERGED == 1 || (APEMOST_PHILOX_MERGED == 2 && kSine);
+    static constexpr bool kMergedPhilox = kSine;
 
     // ---- identity ----
     int lane, hw;  // lane, hardware wave index in the workgroup
@@ -204,7 +181,7 @@ struct ObEngine {
     __device__ __forceinline__ bool is_lik() const { return hw < LW; }
     __device__ __forceinline__ bool is_owner() const { return hw == LW; }
     __device__ __forceinline__ bool is_producer() const { return hw > LW && hw <= LW + kProducers; }
-    __device__ __forceinline__ bool is_helper() const { return kHelperWave && hw == LW + kProducers + 1 + APEMOST_OB_HELPER_SIMD; }
+    __device__ __forceinline__ bool is_helper() const { return kHelperWave && hw == LW + kProducers + 1; }
 
     int n_par, n_data;
     int Q, grp, qidx, n_cand_lanes;
@@ -256,13 +233,6 @@ struct ObEngine {
     __device__ __forceinline__ void setup_common(const DevArrays &d, const ChainShape &sh, int c, double *lds_) {
         lane = threadIdx.x & (kWave - 1);
         hw = threadIdx.x / kWave;
-#if APEMOST_OB_WAVE_PERM
-        // (experiment, round 4) which role a hardware wave takes, i.e. which roles share a SIMD (wave w runs on
-        // SIMD w mod 4): 1 = owner + a producer on SIMD 0, two likelihood waves on SIMD 1; 2 = owner + producer,
-        // likelihood waves in two pairs, two producers together.  One nibble per hardware wave, LW = 4 only.
-        if (LW == 4 && !kHelperWave)
-            hw = (int)(((APEMOST_OB_WAVE_PERM == 1 ? 0x76352104u : 0x73256104u) >> (4 * hw)) & 0xFu);
-#endif
         wave = hw == LW ? 0 : hw + 1;
         tid = hw * kWave + lane;
         n_par = sh.n_par;
@@ -525,42 +495,40 @@ struct ObEngine {
         lp.init();
         int i = tid;
         if (rows_in_regs) {
-            add_terms<kWide, kShortChain, false>(m, row_x, row_y, acc, lp);
+            add_terms<kWide, false>(m, row_x, row_y, acc, lp);
             i = n_data;
         }
-#if APEMOST_OB_SKIP_LOOPS
         // The whole vector is one pass held in registers (configs 2 and 4): all three loops below are empty -- but each
         // loop test is per lane (v_cmp -> s_and_saveexec -> s_cbranch_execz -> s_or exec) and sat on the step's dependent
-        // chain; ONE uniform test in front of them: config 2 2.078 -> 2.141e8 steps/s (+3 %), config 4 +0.8 %.
-        if (!rows_in_regs)
-#endif
-        {
-        if (LW < 8) {
-            for (; i + 3 * kLikThreads < n_data; i += 4 * kLikThreads) {
-                const double x4[4] = {xs[i], xs[i + kLikThreads], xs[i + 2 * kLikThreads], xs[i + 3 * kLikThreads]};
-                const double y4[4] = {ys[i], ys[i + kLikThreads], ys[i + 2 * kLikThreads], ys[i + 3 * kLikThreads]};
-                add_terms<4, kShortChain, false>(m, x4, y4, acc, lp);
+        // chain; ONE uniform test in front of them: config 2 2.078 -> 2.141e8 steps/s (+3 %), config 4 +0.8 %
+        // (round 4, read in the code object: profiles/r04_lik_step_microfixes.txt).
+        if (!rows_in_regs) {
+            if (LW < 8) {
+                for (; i + 3 * kLikThreads < n_data; i += 4 * kLikThreads) {
+                    const double x4[4] = {xs[i], xs[i + kLikThreads], xs[i + 2 * kLikThreads], xs[i + 3 * kLikThreads]};
+                    const double y4[4] = {ys[i], ys[i + kLikThreads], ys[i + 2 * kLikThreads], ys[i + 3 * kLikThreads]};
+                    add_terms<4, false>(m, x4, y4, acc, lp);
+                    if constexpr (Model<kBase>::kLogProduct)
+                        lp.renorm();
+                }
+            }
+            for (; i + kLikThreads < n_data; i += 2 * kLikThreads) {
+                const double x2[2] = {xs[i], xs[i + kLikThreads]};
+                const double y2[2] = {ys[i], ys[i + kLikThreads]};
+                add_terms<2, false>(m, x2, y2, acc, lp);
                 if constexpr (Model<kBase>::kLogProduct)
                     lp.renorm();
             }
-        }
-        for (; i + kLikThreads < n_data; i += 2 * kLikThreads) {
-            const double x2[2] = {xs[i], xs[i + kLikThreads]};
-            const double y2[2] = {ys[i], ys[i + kLikThreads]};
-            add_terms<2, kShortChain, false>(m, x2, y2, acc, lp);
-            if constexpr (Model<kBase>::kLogProduct)
-                lp.renorm();
-        }
-        for (; i < n_data; i += kLikThreads) {
-            const double x1[1] = {xs[i]}, y1[1] = {ys[i]};
-            if constexpr (Model<kBase>::kLogProduct) {
-                add_terms<1, kShortChain, false>(m, x1, y1, acc, lp);
-                lp.renorm();
-            } else if constexpr (Model<kBase>::kFusedAcc)
-                add_terms<1, kShortChain, false>(m, x1, y1, acc, lp);
-            else
-                acc += m.term(xs[i], ys[i]);
-        }
+            for (; i < n_data; i += kLikThreads) {
+                const double x1[1] = {xs[i]}, y1[1] = {ys[i]};
+                if constexpr (Model<kBase>::kLogProduct) {
+                    add_terms<1, false>(m, x1, y1, acc, lp);
+                    lp.renorm();
+                } else if constexpr (Model<kBase>::kFusedAcc)
+                    add_terms<1, false>(m, x1, y1, acc, lp);
+                else
+                    acc += m.term(xs[i], ys[i]);
+            }
         }
         if constexpr (Model<kBase>::kLogProduct) {
             acc += lp.template finish<false>(m.tab);
@@ -632,46 +600,29 @@ struct ObEngine {
 #pragma unroll
         for (int w = 0; w < LW; w++)
             part[w] = sp[w];
-#if APEMOST_OB_PART_FIRST
         // The partial sums FIRST in the LDS queue: the add tree is the head of the step's chain, the proposal rows are
         // not needed before the select behind it (left to itself the compiler requests the threshold, the flag and the
         // four row reads ahead of them).  Worth nothing by itself beyond the skipped loops; kept with mov_dpp, with
         // which it is the fastest combination measured (2.141 / 2.394e8 at configs 2 / 4).
         asm volatile("" ::: "memory");
-#endif
         double limit = *s_thr(parity);
         if constexpr (kSplit)
             limit = ObThreshold<kBase>::limit(*s_thx(parity), limit); // (one subtraction beside the partial sums' tree)
         const int pending = *s_flag(parity);
         m.fetch2(s_prop(parity, 0), s_prop(parity, 1));
-#if !APEMOST_OB_FLAG_LATE
         if (__builtin_amdgcn_readfirstlane(pending) != 0) {
             // rare: the owner is replacing a proposal that could not be prepared (redraw path);
             // every wave of the workgroup takes this barrier, then the rows are read again
             __syncthreads();
             m.fetch2(s_prop(parity, 0), s_prop(parity, 1));
         }
-#endif
 #pragma unroll
         for (int span = 1; span < LW; span *= 2) {
 #pragma unroll
             for (int w = 0; w + span < LW; w += 2 * span)
                 part[w] += part[w + span];
         }
-#if APEMOST_OB_FLAG_LATE
-        // (measured and not taken, round 4: 2.06-2.14e8 at config 2 depending on what else is switched on, never above the
-        // combinations without it) the redraw flag's test BEHIND the add tree: the decision needs the partial sums
-        // and the threshold only, and a branch in front of the tree holds the wave until the flag has come back
-        const bool first = part[0] < limit;
-        asm volatile("" : "+v"(part[0]));
-        if (__builtin_amdgcn_readfirstlane(pending) != 0) {
-            __syncthreads();
-            m.fetch2(s_prop(parity, 0), s_prop(parity, 1));
-        }
-        m.pick2(first, n_par);
-#else
         m.pick2(part[0] < limit, n_par);
-#endif
         const double mine = lik_partial();
         if (lane == 63)
             s_part(parity ^ 1)[hw] = mine;
@@ -801,10 +752,6 @@ struct ObEngine {
             if (lane < n_par)
                 s_urow(1)[lane] = row[lane];
         }
-#ifdef APEMOST_EXP_NO_ATTEMPTS
-        if (lane < n_par)
-            s_prop(1, 0)[lane] = s_prop(1, 1)[lane] = row[lane];
-#endif
         if (lane == 0) {
             *s_thr(0) = kSplit ? 0.0 : __builtin_inf();
             if constexpr (kSplit)
@@ -906,11 +853,7 @@ struct ObEngine {
     // two prepared proposals of the step after it into the other parity
     __device__ __forceinline__ void owner_choose(int parity, bool first) {
         double *row = s_prop(parity, (first || accepted) ? 0 : 1);
-#ifdef APEMOST_EXP_OWNER_SLACK
-        const u64 failed = 0;
-#else
         const u64 failed = first ? 0 : (accepted ? fail_a : fail_r);
-#endif
         // the value my parameter takes in the chosen proposal was read back when the proposals were
         // prepared (sel_a / sel_r): no trip to LDS between the accept decision and the next proposals
         par_val = (first || accepted) ? sel_a : sel_r;
@@ -928,7 +871,7 @@ struct ObEngine {
         OB_SEG(2); // the proposal in flight
     }
     // candidates of the next tick: published by the barrier that opened this step; requested with the
-    // step's first batch of LDS reads (APEMOST_HOIST_CAND: config 2 2.036 -> 2.066e8 steps/s, config 4
+    // step's first batch of LDS reads (config 2 2.036 -> 2.066e8 steps/s, config 4
     // 2.29 -> 2.33e8, tools/experiments/gpu_exp_hoist.sh), not where the proposals need them
     __device__ __forceinline__ double2 owner_fetch_next_cand() const { return s_cand(tick + 1)[lane]; }
     // MERGED: both prepared proposals through attempts2() (measured, tools/experiments/gpu_exp_hoist.sh with
@@ -941,22 +884,13 @@ struct ObEngine {
         next_y = nx.x;
         next_s = nx.y;
         // the two proposals of the next step: from the proposal in flight, from the current point
-#ifdef APEMOST_EXP_NO_ATTEMPTS
-        // TIMING ONLY (results are garbage; tools/experiments/r04_session18.sh, 20): what the step costs when somebody
-        // else prepares the proposals, before that somebody's own cost
-        fail_a = fail_r = 0;
-#else
         if constexpr (MERGED) {
             attempts2(par_val, cur, next_y, next_s, s_prop(next, 0), s_prop(next, 1), which_next, fail_a, fail_r);
         } else {
             fail_a = attempts(par_val, next_y, next_s, s_prop(next, 0), which_next);
             fail_r = attempts(cur, next_y, next_s, s_prop(next, 1), which_next);
         }
-#endif
         OB_SEG(3); // next candidates, both prepared proposals
-#if defined(APEMOST_OWNER_PRIO_PHASE) && APEMOST_OWNER_PRIO_PHASE == 1
-        __builtin_amdgcn_s_setprio(0);
-#endif
         // S_max of the step in flight (kSplit: the chain's half of it; the helper adds the proposal's)
         double prior_new = 0;
         if constexpr (Model<kBase>::kHasPrior && !kSplit && !kUser) {
@@ -977,11 +911,7 @@ struct ObEngine {
             *s_thr(next) = thr;
             if constexpr (kUser)
                 *s_thx(next) = lu;
-#ifdef APEMOST_EXP_OWNER_SLACK
-            *s_flag(next) = 0;
-#else
             *s_flag(next) = (fail_a | fail_r) != 0 ? 1 : 0;
-#endif
         }
         OB_SEG(5); // threshold, flags
     }

@@ -3,13 +3,13 @@
 The data sum of a Metropolis step is written twice and splits into regimes by n_data.  With T = 64 * waves lanes
 per chain:
 
-  * Engine::cache_rows and Engine::lane_sum (apemost_amd/csrc/pt_device.h:1870-1892 and 1940-2046): rows held in
+  * Engine::cache_rows and Engine::lane_sum (apemost_amd/csrc/pt_device.h:1763-1783 and 1832-1937): rows held in
     registers when n_data == kWide * T exactly (kWide = 4 below eight waves, 2 at eight); the software-pipelined
     loop of n_data // (4 T) passes for waves <= 2 and the kPrefetch models (simplesin, sine3, pulse_vrot: two
     passes per trip, the second one advancing only while k + 1 < passes, an odd count leaving one pass behind
     the loop); the 4-wide loop for waves < 8 where the pipelined loop does not exist; the 2-wide loop; the
     1-wide tail.
-  * ObEngine::cache_rows and ObEngine::lik_partial (apemost_amd/csrc/pt_onebarrier.h:510-582): the same without
+  * ObEngine::cache_rows and ObEngine::lik_partial (apemost_amd/csrc/pt_onebarrier.h:480-550): the same without
     the pipelined loop, for the four and eight likelihood waves of the one-barrier kernels.
 
 regimes() restates both as a walk over the lanes; lengths() is the list of lengths the GPU tests run, chosen so
@@ -29,8 +29,8 @@ from tests import loglike_ref
 K_WAVE = 64
 MODELS = ("simplesin", "sine3", "pulse", "pulse_vrot")
 WAVES = (1, 2, 4, 6, 8)
-PREFETCH_MODELS = ("simplesin", "sine3", "pulse_vrot")      # Model::kPrefetch, pt_device.h:649, 777, 1208
-ONE_BARRIER_WAVES = (4, 8)                                  # APEMOST_OB_WAVES_MASK, pt_kernels.h:47-50
+PREFETCH_MODELS = ("simplesin", "sine3", "pulse_vrot")      # Model::kPrefetch, pt_device.h:540, 668, 1099
+ONE_BARRIER_WAVES = (4, 8)                                  # kObWavesMask, pt_kernels.h:47-48
 BIG_LDS = 64 * 1024                                         # beyond it a kernel opts in (enable_big_lds)
 
 
@@ -39,17 +39,17 @@ def threads(waves):
 
 
 def k_wide(waves):
-    """Engine::kWide (pt_device.h:1873) and ObEngine::kWide (pt_onebarrier.h:189)"""
+    """Engine::kWide (pt_device.h:1766) and ObEngine::kWide (pt_onebarrier.h:170)"""
     return 4 if waves < 8 else 2
 
 
 def pipelined(waves, model):
-    """Engine::kPipelined (pt_device.h:1881)"""
+    """Engine::kPipelined (pt_device.h:1772)"""
     return waves <= 2 and model in PREFETCH_MODELS
 
 
 def pipe_passes(n_data, waves, model):
-    """passes of the software-pipelined loop (pt_device.h:1962); 0 where it does not run"""
+    """passes of the software-pipelined loop (pt_device.h:1853); 0 where it does not run"""
     if not pipelined(waves, model) or n_data == k_wide(waves) * threads(waves):
         return 0
     return n_data // (4 * threads(waves))
@@ -94,13 +94,13 @@ def _walk(n_data, t, kw, pipe, wide4):
 
 
 def two_phase_walk(n_data, waves, model):
-    """Engine::lane_sum, pt_device.h:1940-2046"""
+    """Engine::lane_sum, pt_device.h:1832-1937"""
     pipe = pipelined(waves, model)
     return _walk(n_data, threads(waves), k_wide(waves), pipe, waves < 8 and not pipe)
 
 
 def one_barrier_walk(n_data, waves):
-    """ObEngine::lik_partial, pt_onebarrier.h:521-582 (LW = waves likelihood wavefronts)"""
+    """ObEngine::lik_partial, pt_onebarrier.h:492-550 (LW = waves likelihood wavefronts)"""
     assert waves in ONE_BARRIER_WAVES
     return _walk(n_data, threads(waves), k_wide(waves), False, waves < 8)
 

@@ -3,7 +3,7 @@ the head of apemost_amd/csrc/pt_predict.h) that shares nothing with the kernels 
 
 The four curves are restated with every operation -- every FMA included -- rounded once from exact rational arithmetic
 (fractions.Fraction; int / int true division rounds correctly, to nearest even).  sin_cw is restated step by step as
-tools/check_sine.py does, in the form that ships (APEMOST_SIN_FOLD_N): fm = fma(u, 2.0, magic), the parity is the low
+tools/check_sine.py does, in the form that ships (sin_multiple): fm = fma(u, 2.0, magic), the parity is the low
 bit of fm.  Where an operand is not finite the operation is Python's own float arithmetic, which gives IEEE's inf and
 NaN.  An exact zero result is +0 here whatever IEEE's sign would be: the tests' inputs avoid exact cancellations.
 The pulse curves are plain IEEE operations: `pulse_numpy` states them with numpy for tests that need many samples.

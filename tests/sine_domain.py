@@ -3,7 +3,7 @@ which a Cody-Waite reduction and an odd polynomial go wrong, a true sine to hold
 the sine a likelihood kernel computed back out of HipSampler.loglike.  CPU only; shared by
 tests/test_sine_domain_cpu.py and tests/test_gpu_sine_domain.py.
 
-The sine's argument is x = fl(kTwoPi * u) of a phase in turns u; the shipped form (APEMOST_SIN_FOLD_N) takes the
+The sine's argument is x = fl(kTwoPi * u) of a phase in turns u; the shipped form (sin_multiple) takes the
 multiple of pi from the phase, n = rint(2 u), so r = x - n pi leaves [-pi/2, pi/2], the interval the polynomial was
 fitted on, wherever 2 u is within an ulp of a half integer.  phases() is the fixed list, in named classes:
 

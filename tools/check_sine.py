@@ -4,9 +4,8 @@ odd polynomial on [-pi/2, pi/2]) against 200-bit arithmetic, operation by operat
 rounds them (every FMA rounds once).  Reports the absolute error (what a likelihood sees: it adds
 a sin() to numbers of order one) and the relative error in ulp, for the kernel's two-term
 reduction and for a three-term one (which keeps the relative error near the zeros of the sine at
-the price of one more FMA per sine), and compares the two evaluation orders of the polynomial:
-Horner (shortest instruction count) and Estrin (shortest dependent chain).  Both forms of the multiple of pi are
-reported: n = rint(x / pi), and the one that ships, n = rint(2 u) from the phase in turns (fm = fma(u, 2, magic)).
+the price of one more FMA per sine); the polynomial by Horner's scheme, as the kernel has it.  Both forms of the
+multiple of pi are reported: n = rint(x / pi), and the one that ships, n = rint(2 u) from the phase in turns (fm = fma(u, 2, magic)).
 
     python tools/check_sine.py [samples]"""
 import math
@@ -29,7 +28,7 @@ def fma(a, b, c):
 
 
 def reduce_(x, terms=2, u=None):
-    """u: the phase in turns, x = fl(2 pi u): the form that ships (APEMOST_SIN_FOLD_N), n = rint(2 u)"""
+    """u: the phase in turns, x = fl(2 pi u): the form that ships (sin_multiple), n = rint(2 u)"""
     fm = fma(x, INV_PI, MAGIC) if u is None else fma(u, 2.0, MAGIC)
     fn = fm - MAGIC
     r = fma(fn, NPI_HI, x)
@@ -49,19 +48,6 @@ def horner(x, terms=2, u=None):
     return -v if odd else v
 
 
-def estrin(x, terms=2):
-    r, odd = reduce_(x, terms)
-    z = r * r
-    z2 = z * z
-    p01, p23 = fma(z, S[1], S[0]), fma(z, S[3], S[2])
-    p45, p67 = fma(z, S[5], S[4]), fma(z, S[7], S[6])
-    z4 = z2 * z2
-    lo, hi = fma(z2, p23, p01), fma(z2, p67, p45)
-    q = fma(z4, hi, lo)
-    v = fma(r * z, q, r)
-    return -v if odd else v
-
-
 def ulp_err(got, x):
     ref = mp.sin(mp.mpf(x))
     if ref == 0:
@@ -73,7 +59,7 @@ def ulp_err(got, x):
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
     rnd = random.Random(1)
-    worst = {"abs2": 0.0, "ulp2": 0.0, "ulp2_away": 0.0, "ulp3": 0.0, "estrin_abs2": 0.0, "estrin_ulp3": 0.0}
+    worst = {"abs2": 0.0, "ulp2": 0.0, "ulp2_away": 0.0, "ulp3": 0.0}
     for i in range(n):
         kind = i % 5
         if kind == 0:
@@ -93,8 +79,6 @@ def main():
         if abs(ref) > 1e-6:
             worst["ulp2_away"] = max(worst["ulp2_away"], ulp_err(h2, x))
         worst["ulp3"] = max(worst["ulp3"], ulp_err(h3, x))
-        worst["estrin_abs2"] = max(worst["estrin_abs2"], float(abs(mp.mpf(estrin(x, 2)) - ref)))
-        worst["estrin_ulp3"] = max(worst["estrin_ulp3"], ulp_err(estrin(x, 3), x))
     # the form that ships: n = rint(2 u) from the phase in turns, x = fl(2 pi u).  The two forms differ where 2 u is
     # within an ulp of a half integer: there r leaves [-pi/2, pi/2] (tests/sine_domain.py holds the list and the bound)
     two_pi = 2.0 * 3.14159265358979323846264338328
@@ -120,7 +104,6 @@ def main():
     print("  kernel (two-term reduction, Horner): absolute %.3g; relative %.3g ulp where |sin| > 1e-6, %.3g ulp anywhere"
           % (worst["abs2"], worst["ulp2_away"], worst["ulp2"]))
     print("  three-term reduction, Horner: %.3g ulp anywhere" % worst["ulp3"])
-    print("  Estrin: absolute %.3g (two-term), %.3g ulp (three-term)" % (worst["estrin_abs2"], worst["estrin_ulp3"]))
 
 
 if __name__ == "__main__":
