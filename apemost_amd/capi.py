@@ -92,6 +92,18 @@ class EvidenceView(C.Structure):
     _fields_ = [("n", _up), ("origin", _dp), ("sum", _dp), ("sq", _dp), ("batch", _dp), ("m", _dp), ("S", _dp)]
 
 
+class MbarConfig(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("betas", _dp)]
+
+
+class MbarView(C.Structure):
+    _fields_ = [("n", _up), ("n_bad", _up), ("ell", _dp)]
+
+
+class MbarSums(C.Structure):
+    _fields_ = [("m", _dp), ("S0", _dp), ("S1", _dp), ("S2", _dp), ("SS", _dp), ("G", _dp), ("ell_first", _dp)]
+
+
 class AutocorrConfig(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("max_lag", C.c_int32), ("n_cols", C.c_int32),
                 ("cols", C.POINTER(C.c_int32))]
@@ -195,6 +207,8 @@ EXPORTS = [
     "apemost_hip_joint_end",
     "apemost_hip_evidence_begin", "apemost_hip_evidence_accumulate", "apemost_hip_evidence_get",
     "apemost_hip_evidence_set", "apemost_hip_evidence_end",
+    "apemost_hip_mbar_begin", "apemost_hip_mbar_accumulate", "apemost_hip_mbar_get", "apemost_hip_mbar_set",
+    "apemost_hip_mbar_end", "apemost_hip_mbar_iterate", "apemost_hip_mbar_evaluate", "apemost_hip_mbar_log_weights",
     "apemost_hip_autocorr_begin", "apemost_hip_autocorr_accumulate", "apemost_hip_autocorr_get",
     "apemost_hip_autocorr_set", "apemost_hip_autocorr_end",
     "apemost_hip_predict_begin", "apemost_hip_predict_accumulate", "apemost_hip_predict_get",
@@ -340,6 +354,14 @@ def lib():
     L.apemost_hip_evidence_get.argtypes = [vp, C.POINTER(EvidenceView)]
     L.apemost_hip_evidence_set.argtypes = [vp, C.POINTER(EvidenceView)]
     L.apemost_hip_evidence_end.argtypes = [vp]
+    L.apemost_hip_mbar_begin.argtypes = [vp, C.POINTER(MbarConfig)]
+    L.apemost_hip_mbar_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_mbar_get.argtypes = [vp, C.POINTER(MbarView)]
+    L.apemost_hip_mbar_set.argtypes = [vp, C.POINTER(MbarView)]
+    L.apemost_hip_mbar_end.argtypes = [vp]
+    L.apemost_hip_mbar_iterate.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp]
+    L.apemost_hip_mbar_evaluate.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, _dp, C.c_int32, C.POINTER(MbarSums)]
+    L.apemost_hip_mbar_log_weights.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, C.c_double, _dp]
     L.apemost_hip_autocorr_begin.argtypes = [vp, C.POINTER(AutocorrConfig)]
     L.apemost_hip_autocorr_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
     L.apemost_hip_autocorr_get.argtypes = [vp, C.POINTER(AutocorrView)]

@@ -122,6 +122,23 @@ struct EvidenceFold {
     FoldMem mem;
 };
 
+// on-device MBAR (pt_mbar.h): loglike of every kept step of every chain, resident; n = kept steps stored
+struct MbarFold {
+    bool open;
+    int K, L; // chains per ladder, ladders
+    u64 capacity;
+    u64 tiles_max; // tiles of a ladder's whole store: ceil(capacity * K / kMbarTile)
+    u64 n;
+    double *d_betas, *d_ell, *d_lnD;
+    double *d_g;      // [2][n_chains]: g of the iteration under way and of the one before
+    double *d_c;      // [n_chains]
+    double *d_beta_t; // [n_chains]: the targets of one piece of an evaluate
+    double *d_part;   // [kMbarWords][n_chains][tiles_max]
+    double *d_out;    // [2 + kMbarWords][n_chains]: m, the sums, G
+    unsigned long long *d_bad, *d_mkey; // [n_ladders], [n_chains]
+    FoldMem mem;
+};
+
 // on-device autocorrelation (pt_autocorr.h): lag sums of kept chains' columns
 struct AutocorrFold {
     bool open;
@@ -328,6 +345,7 @@ struct apemost_hip_sampler {
     DerivedFold dv;
     CheckFold ck;
     PeriodogramFold pg;
+    MbarFold mb;
 };
 
 // the data rows of ladder b and its column-major matrix on the device (an ordinary sampler: b = 0)
@@ -385,6 +403,7 @@ static void release(apemost_hip_sampler *s) {
     fold_free(s->dv);
     fold_free(s->ck);
     fold_free(s->pg);
+    fold_free(s->mb);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {

@@ -6,6 +6,7 @@
 #include "pt_evidence.h"
 #include "pt_joint.h"
 #include "pt_kernels.h"
+#include "pt_mbar.h"
 #include "pt_peaks.h"
 #include "pt_periodogram.h"
 #include "pt_pointwise.h"
@@ -1923,6 +1924,7 @@ extern "C" int apemost_hip_samples_wait(apemost_hip_sampler *s) {
 #include "abi/fold_derived.h"
 #include "abi/fold_check.h"
 #include "abi/fold_periodogram.h"
+#include "abi/fold_mbar.h"
 
 // Host arithmetic only (no device): tools/peaks.c:130, 177-200 and the selection sort of src/gsl_helper.c:102-127.
 extern "C" int apemost_hip_peaks_table(const apemost_hip_peaks_view *v, int32_t n_par, int32_t k, int32_t p,

@@ -254,6 +254,14 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            of the highest peak's frequency: at the end write periodogram.bin and periodogram.txt
  *            (run_periodogram.h).  Needs a bounded run and simplesin or sine3.  Combines with every other token and
  *            writes no sample file by itself, like check
+ *   mbar     keep loglike = (prob - prior) / beta of EVERY kept step of EVERY chain on the device and at the end solve
+ *            the MBAR equations there (Shirts & Chodera 2008): write mbar.bin (the store and the free energies
+ *            ln Z(beta_k) - ln Z(beta_0)) and mbar.txt (per rung beta, ln Z, E[loglike], Var[loglike] and the effective
+ *            sample size of the whole ladder's samples there; then ln p(D|M,I) = ln Z(1) - ln Z(0) with its block
+ *            error; run_mbar.h).  APEMOST_MBAR_TOL (default 1e-10) and APEMOST_MBAR_ITER (default 10000) set the
+ *            solver's tolerance and iteration cap.  Needs a bounded run, positive, strictly decreasing betas and the
+ *            whole ladder on one device.  Combines with every other token and writes no sample file by itself, like
+ *            periodogram
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -298,7 +306,7 @@ static void sink_parse(sample_sink *k) {
         else if ((fold = run_fold_find(spec)) >= 0)
             k->folds |= 1u << fold;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived, check, periodogram; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived, check, periodogram, mbar; got '%s'\n", spec);
             exit(1);
         }
     }

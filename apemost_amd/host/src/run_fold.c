@@ -5,15 +5,18 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "run_mbar.h"
+
 #define BATCH_SIZE_WHY "the batch size of the error estimate is fixed before the first sample"
+#define KEPT_ON_DEVICE_WHY "the columns kept on the device are sized before the first sample"
 
 /* In the order the folds open and close.  Only summary and evidence fold every chain, so one fold per shard; the
  * others fold chain 0, which lives on shard 0.  joint and autocorr size nothing by the samples to come and run
- * unbounded too, and so does check; predict needs the bound only for its refusal, and so does periodogram. */
+ * unbounded too, and so does check; predict needs the bound only for its refusal, and so does periodogram.  mbar keeps
+ * every chain's column on one device: its one fold is shard 0's, and more shards than that are refused below. */
 const run_fold run_folds[RUN_FOLDS] = {
     {"summary", BATCH_SIZE_WHY, 1, run_summary_open, run_summary_close, apemost_hip_summary_accumulate},
-    {"peaks", "the columns kept on the device are sized before the first sample", 0, run_peaks_open, run_peaks_close,
-     apemost_hip_peaks_accumulate},
+    {"peaks", KEPT_ON_DEVICE_WHY, 0, run_peaks_open, run_peaks_close, apemost_hip_peaks_accumulate},
     {"joint", NULL, 0, run_joint_open, run_joint_close, apemost_hip_joint_accumulate},
     {"derived", BATCH_SIZE_WHY, 0, run_derived_open, run_derived_close, apemost_hip_derived_accumulate},
     {"evidence", BATCH_SIZE_WHY, 1, run_evidence_open, run_evidence_close, apemost_hip_evidence_accumulate},
@@ -24,7 +27,8 @@ const run_fold run_folds[RUN_FOLDS] = {
      run_pointwise_close, apemost_hip_pointwise_accumulate},
     {"check", NULL, 0, run_check_open, run_check_close, apemost_hip_check_accumulate},
     {"periodogram", "periodogram.bin and periodogram.txt are written when the run ends", 0, run_periodogram_open,
-     run_periodogram_close, apemost_hip_periodogram_accumulate}};
+     run_periodogram_close, apemost_hip_periodogram_accumulate},
+    {"mbar", KEPT_ON_DEVICE_WHY, 0, run_mbar_open, run_mbar_close, apemost_hip_mbar_accumulate}};
 
 static int item_is(const char *spec, const char *token) {
     const size_t len = strlen(token);
@@ -71,6 +75,16 @@ void run_folds_check(unsigned int mask) {
         exit(1);
     }
 #endif
+    if (in_mask(mask, "mbar")) { /* (APEMOST_DEVICES=0,1,...: one shard per device named) */
+        const char *devices = getenv("APEMOST_DEVICES");
+        if (devices != NULL && strchr(devices, ',') != NULL) {
+            fprintf(stderr, "APEMOST_DUMP=mbar needs the whole ladder on one device, APEMOST_DEVICES=%s names several: "
+                            "the solve reads every chain\n", devices);
+            exit(1);
+        }
+        (void)run_mbar_tol_from_env();
+        (void)run_mbar_iter_from_env();
+    }
 }
 
 uint64_t planned_samples(const char *token, const char *why, unsigned int n_swap, unsigned long iter,

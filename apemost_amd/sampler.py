@@ -629,6 +629,44 @@ class HipSampler:
     def evidence_end(self):
         capi.check(self.L.apemost_hip_evidence_end(self._h))
 
+    # -- on-device MBAR (apemost_amd/mbar.py) -------------------------------------------------------
+    def mbar_begin(self, capacity, betas=None, thin=1):
+        """start the store of loglike = column n_par+1 / beta of every kept step of every local chain, with room for
+        `capacity` kept steps (capacity * n_chains <= 2^28).  betas: the ladder-major betas of the local chains (None:
+        the sampler's own), positive and strictly decreasing in every ladder.  Not for a shard of a sharded ladder."""
+        from .mbar import check_betas
+        if betas is None:
+            betas = self.get_state(fields=("beta",)).beta
+        self._mb_betas = check_betas(betas, self.n_ladders)
+        assert self._mb_betas.shape == (self.n_chains,)
+        self._mb_thin = int(thin)
+        cfg = capi.MbarConfig(capacity=capacity, betas=self._mb_betas.ctypes.data_as(capi._dp))
+        capi.check(self.L.apemost_hip_mbar_begin(self._h, C.byref(cfg)))
+        self._mb_capacity = int(capacity)
+
+    def mbar_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """append the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]; asynchronous
+        (mbar() or a sample read's wait before the rows are overwritten)"""
+        capi.check(self.L.apemost_hip_mbar_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def mbar(self):
+        """the store so far as an Mbar whose passes run on this sampler's device (synchronises with the accumulates
+        issued so far); it computes on the open fold, so it is good until the next mbar_begin, mbar_set or mbar_end"""
+        from .mbar import Mbar
+        n = np.zeros(1, dtype=np.uint64)
+        capi.check(self.L.apemost_hip_mbar_get(self._h, C.byref(capi.MbarView(n=n.ctypes.data_as(capi._up)))))
+        mb = Mbar(np.zeros((int(n[0]), self.n_chains)), self._mb_betas, self.n_ladders, None, self._mb_thin, self)
+        capi.check(self.L.apemost_hip_mbar_get(self._h, C.byref(mb.view())))
+        return mb
+
+    def mbar_set(self, mb):
+        """load an Mbar's store (a resumed run) into the fold begun with the same betas"""
+        assert mb.betas.tobytes() == self._mb_betas.tobytes() and mb.n <= self._mb_capacity
+        capi.check(self.L.apemost_hip_mbar_set(self._h, C.byref(mb.view())))
+
+    def mbar_end(self):
+        capi.check(self.L.apemost_hip_mbar_end(self._h))
+
     # -- on-device autocorrelation (apemost_amd/autocorr.py) ----------------------------------------
     def autocorr_begin(self, chains=(0,), max_lag=1024, cols=None, thin=1):
         """start the lag sums of the columns `cols` (None: the parameters and prob - prior) of the local chains

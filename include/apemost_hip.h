@@ -822,6 +822,73 @@ int apemost_hip_evidence_set(apemost_hip_sampler *s, const apemost_hip_evidence_
 /* frees the accumulator (apemost_hip_destroy does too) */
 int apemost_hip_evidence_end(apemost_hip_sampler *s);
 
+/* ---- on-device MBAR: evidence and reweighting from every chain's samples ------------------------
+ * The multistate Bennett acceptance ratio (Shirts & Chodera 2008) over a tempered ladder: the minimum-variance
+ * estimate of every ln Z(beta_k) from the loglike of EVERY kept step of EVERY chain, and the weights that carry those
+ * samples to any beta.  The fold stores, for every local chain c and kept step, l = v / beta_c (one IEEE division) of
+ * column n_par+1 (v = prob - prior = beta * loglike) in ell[capacity][n_chains], and counts per ladder the stored
+ * values that are not finite.  A ladder has K chains; its sample n = (kept step t, chain c) is taken in stored order
+ * (step-major, the chain fastest).  With g_k the running estimate of ln Z(beta_k) and T kept steps in the range
+ * [t0, t0 + t_count):
+ *   lnD_n = ln sum_j exp(beta_j l_n + c_j),   c_j = ln T - g_j              (row pass)
+ *   G_t   = ln sum_n exp(beta_t l_n - lnD_n)                                (column pass, any target beta_t >= 0)
+ *   g <- G(g) at the sampled betas                                          (one self-consistent iteration)
+ * G(g + a) = G(g) + a: the library never normalises, the caller subtracts g_0 and judges convergence.  The order of
+ * every operation -- one rounded multiply and one rounded add per x, the exact maxima, tiles of 4096 samples counted
+ * from the range's first, 64 lane partials through the adjacent-pairs tree, tile partials in tile order -- is stated
+ * in csrc/pt_mbar.h and restated in apemost_amd/mbar.py: a range equals a fold that holds only its rows, a ladder of
+ * a batch the sampler that holds it alone, n_iter updates n_iter calls, all on the bits.
+ * Whole ladders, ladder batches and ragged batches (the ladders are independent; betas ladder-major).  The fold
+ * evaluates no model, so every model is allowed.  A shard of a sharded ladder (n_chains_global > n_chains) is
+ * APEMOST_HIP_ERR_UNSUPPORTED: the solve needs every chain on one device. */
+typedef struct {
+    uint64_t capacity;        /* kept steps the store has room for; capacity * n_chains <= 2^28 */
+    const double *betas;      /* host [n_chains], ladder-major: finite, positive, strictly decreasing in every ladder */
+} apemost_hip_mbar_config;
+typedef struct {
+    uint64_t *n;              /* kept steps stored */
+    uint64_t *n_bad;          /* [n_ladders]: stored values that are not finite */
+    double *ell;              /* [n][n_chains]: the first n rows of the store */
+} apemost_hip_mbar_view;      /* host arrays; any pointer may be NULL (that part is skipped) */
+typedef struct {
+    double *m, *S0, *S1, *S2, *SS, *G; /* [n_ladders][n_t] */
+    double *ell_first;        /* [n_ladders]: l of the range's first sample */
+} apemost_hip_mbar_sums;      /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates the store, lnD and the tile-partial scratch.  An mbar fold begun before is dropped once the new
+ * configuration has been accepted; a begin that is refused leaves it open as it was.  APEMOST_HIP_ERR_INVALID, before
+ * any device work, for a NULL config, betas that are missing or break the rule above, capacity == 0 or capacity *
+ * n_chains > 2^28 (the message names the largest capacity that fits). */
+int apemost_hip_mbar_begin(apemost_hip_sampler *s, const apemost_hip_mbar_config *cfg);
+/* appends l of the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2]) to the store.
+ * Asynchronous and queued like apemost_hip_evidence_accumulate.  APEMOST_HIP_ERR_INVALID, before any device work,
+ * without mbar_begin, with thin == 0, or when the kept steps go beyond capacity. */
+int apemost_hip_mbar_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                uint64_t thin);
+/* copies the store out (synchronises with the accumulates issued so far) */
+int apemost_hip_mbar_get(apemost_hip_sampler *s, const apemost_hip_mbar_view *v);
+/* loads a view saved by mbar_get into a fold begun with the same betas; APEMOST_HIP_ERR_INVALID when n > capacity */
+int apemost_hip_mbar_set(apemost_hip_sampler *s, const apemost_hip_mbar_view *v);
+/* frees the store (apemost_hip_destroy does too) */
+int apemost_hip_mbar_end(apemost_hip_sampler *s);
+/* n_iter updates g <- G(g) over the kept steps [t0, t0 + t_count); g_inout [n_chains] holds g before and after,
+ * g_prev_out [n_chains] (may be NULL) g before the last update.  Synchronises.  APEMOST_HIP_ERR_INVALID for an empty
+ * range, a range past n, n_iter < 1, or a ladder with stored non-finite values (the message gives the count). */
+int apemost_hip_mbar_iterate(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, uint32_t n_iter, double *g_inout,
+                             double *g_prev_out);
+/* for the targets betas_t [n_t], each finite and >= 0 (0 included), shared by all ladders, and the free energies g
+ * [n_chains]: m_t = max_n x_tn with x_tn = beta_t l_n - lnD_n, and with e = exp(x_tn - m_t), d = l_n - ell_first the
+ * sums S0 = sum e, S1 = sum e d, S2 = sum (e d) d, SS = sum e e, and G = m + log(S0) with the device's log: ln Z(beta_t)
+ * on the scale of g, and at a sampled beta the g the next mbar_iterate would give that chain, on the bits.
+ * E[l] = ell_first + S1 / S0, Var[l] = S2 / S0 - (S1 / S0)^2, Kish's effective sample size S0^2 / SS.  The refusals of
+ * mbar_iterate. */
+int apemost_hip_mbar_evaluate(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, const double *g,
+                              const double *betas_t, int32_t n_t, const apemost_hip_mbar_sums *out);
+/* host_out [t_count][n_chains] = beta_t l_n - lnD_n - G_t (two rounded differences): the log weights, normalised per
+ * ladder, with which a caller reweights whatever it kept of those rows to beta_t.  The refusals of mbar_iterate. */
+int apemost_hip_mbar_log_weights(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, const double *g, double beta_t,
+                                 double *host_out);
+
 /* ---- on-device autocorrelation: lag sums, integrated times, effective sample size ---------------
  * How many independent samples a run holds: what the autocorrelation function of sample columns needs, accumulated
  * from the sample rows while they are still on the device.  A series is one (kept chain, column) pair, series
