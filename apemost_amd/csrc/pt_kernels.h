@@ -15,7 +15,9 @@ namespace apemost {
 // ===========================================================================
 
 // LDS carve (doubles): proposed params [2][64], wave partials [2][16], 8 control words, the logarithm's table
-constexpr int kLdsLogTab = 2 * kWave + 32 + 8;
+constexpr int kLdsCtl = 2 * kWave + 32;    // the control words (word 2 of the int view: Engine::fail_flag)
+constexpr int kLdsCalibRec = kLdsCtl + 2;  // ... of which pt_calibrate_kernel keeps its CalibRec in the last six doubles
+constexpr int kLdsLogTab = kLdsCtl + 8;
 constexpr int kFixedLdsDoubles = kLdsLogTab + kLogTabLdsDoubles;
 
 struct RoundArgs {
@@ -537,26 +539,12 @@ void pt_round_kernel(const RoundArgs grid) {
 // The same rounds with one barrier per step (pt_onebarrier.h): LW likelihood wavefronts plus an
 // owner and three candidate producers.  All-parameter steps only; launches with steps.
 //
-// Every role runs its own copy of the round/step loops (the registers a role carries from step to
-// step are then live in its loop only); what the copies share is the barrier sequence: one at the
-// start of a round, one per step, and one more in a step whose prepared proposal has to be redrawn
-// (every wave reads the same LDS flag for that).
-// Diagnostic build (-DAPEMOST_STAMPS): per wave of workgroup 0, the cycles between leaving a step's
-// barrier and arriving at the next one (g_stamps[wave]); g_stamps[15] = whole steps of the owner,
-// barrier to barrier.  Tells which role the others wait for.
-#ifdef APEMOST_STAMPS
-#define OB_STAMP_DECL u64 ob_busy = 0, ob_t0 = 0, ob_total = 0, ob_prev = 0
-#define OB_STAMP_BEGIN ob_t0 = __builtin_amdgcn_s_memtime()
-#define OB_STAMP_END ob_busy += __builtin_amdgcn_s_memtime() - ob_t0
-#define OB_STAMP_FLUSH                                                                            \
-    if (blockIdx.x == 0 && e.lane == 0)                                                           \
-    atomicAdd(&g_stamps[e.is_helper() ? 14 : e.hw], ob_busy) /* (slots 8-13: the owner's segments when LW = 4) */
-#else
-#define OB_STAMP_DECL
-#define OB_STAMP_BEGIN
-#define OB_STAMP_END
-#define OB_STAMP_FLUSH
-#endif
+// The role is the kernel's outermost branch, decided once per launch, and every role has its own round/step
+// loops (the registers a role carries from step to step are then live in its loop only).  The barriers: one
+// where the pipeline restarts (the restart mask below: every wave computes the same one), and a step's own --
+// ObEngine::closed_step for the producers and the helper, lik_step's and the loop's below for the likelihood
+// waves, the owner's loop below for the owner.
+// Diagnostic build (-DAPEMOST_STAMPS): ObEngine::stamp_begin / stamp_end / stamps_flush (pt_onebarrier.h).
 
 // s_setprio levels of the one-barrier kernels: the owner's, for its whole step (dropping it for the step's later part
 // lost 0.5-12 %, profiles/r04_owner_prio_phase.txt), and, with a helper wavefront, likelihood wave 0's (see where it is set)
@@ -597,7 +585,6 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
     if constexpr (ob_takes_ladder_length(MODEL, LW, LDS_DATA, HELPER))
         ladder_length<MODEL>(a, c);
     e.setup_common(a.d, a.sh, c, lds);
-    OB_STAMP_DECL;
     // bit r % 64: the pipeline restarts at the start of round r (parity 0, the owner's first proposal
     // from the current point, one barrier more): at the launch's start and where a swap attempt moves
     // this chain.  Elsewhere a round's first step is a step like any other.
@@ -624,22 +611,22 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
                 __syncthreads();
             }
             for (unsigned s = 0; s < a.n_steps; s++) {
-                OB_STAMP_BEGIN;
+                e.stamp_begin();
                 if constexpr (decltype(e)::kUser)
                     e.lik_step_user(p); // (the user-supplied model: the decision through its finish())
                 else
                     e.lik_step(p); // (takes one more barrier inside when a proposal has to be redrawn)
-                OB_STAMP_END;
+                e.stamp_end();
                 __syncthreads();
                 p ^= 1;
             }
         }
-        OB_STAMP_FLUSH;
+        e.stamps_flush();
     } else if (e.is_producer()) {
         e.setup_lanes(a.sh, c);
         e.producer_prologue();
         __syncthreads();
-        int p = 0;
+        int p = 0; // parity of the step about to start
         for (unsigned r = 0; r < a.n_rounds; r++) {
             if ((r & 63) == 0)
                 restart = rounds_restarting(e, a, c, r);
@@ -647,33 +634,16 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
                 p = 0;
                 __syncthreads();
             }
-            for (unsigned s = 0; s < a.n_steps; s++) {
-                OB_STAMP_BEGIN;
-#if defined(APEMOST_STAMPS) && defined(APEMOST_STAMP_PHASES)
-                const int ph = e.pipe_phase; // (the first producer's step by phase: slots 8-10 instead of the owner's segments)
-#endif
-                // (the redraw flag requested first and looked at behind the phase's work -- the candidates do not depend
-                // on it, only the barrier count does -- changes nothing: 2.131 vs 2.132e8 at config 2, session 20)
-                if (e.redraw_pending(p))
-                    __syncthreads();
-                e.producer_step(p);
-                OB_STAMP_END;
-#if defined(APEMOST_STAMPS) && defined(APEMOST_STAMP_PHASES)
-                if (blockIdx.x == 0 && e.lane == 0 && e.hw == LW + 1)
-                    atomicAdd(&g_stamps[8 + ph], __builtin_amdgcn_s_memtime() - ob_t0);
-#endif
-                __syncthreads();
-                p ^= 1;
-            }
+            for (unsigned s = 0; s < a.n_steps; s++)
+                p = e.template closed_step<OB_PRODUCER>(p);
         }
-        OB_STAMP_FLUSH;
+        e.stamps_flush();
     } else if (e.is_helper()) {
-        // (HELPER) the helper alone: the barrier sequence of a producer, helper_step per step
         if constexpr (decltype(e)::kHelperWave) {
             e.setup_lanes(a.sh, c);
             e.setup_helper(a.d, a.sh, c);
             __syncthreads();
-            int p = 0;
+            int p = 0; // parity of the step about to start
             for (unsigned r = 0; r < a.n_rounds; r++) {
                 if ((r & 63) == 0)
                     restart = rounds_restarting(e, a, c, r);
@@ -681,17 +651,10 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
                     p = 0;
                     __syncthreads();
                 }
-                for (unsigned s = 0; s < a.n_steps; s++) {
-                    OB_STAMP_BEGIN;
-                    if (e.redraw_pending(p))
-                        __syncthreads();
-                    e.helper_step(p);
-                    OB_STAMP_END;
-                    __syncthreads();
-                    p ^= 1;
-                }
+                for (unsigned s = 0; s < a.n_steps; s++)
+                    p = e.template closed_step<OB_HELPER>(p);
             }
-            OB_STAMP_FLUSH;
+            e.stamps_flush();
         }
     } else {
         // the others wait for this wave at every barrier and it has little to issue: let it go first
@@ -730,9 +693,9 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
                 __syncthreads();
             }
             for (unsigned s = 0; s < a.n_steps; s++) {
-                OB_STAMP_BEGIN;
+                e.stamp_begin();
 #ifdef APEMOST_STAMPS
-                e.seg_last = ob_t0;
+                e.seg_last = e.ob_t0;
 #endif
                 // one batch of LDS reads: the redraw flag, what the prepared proposals settled on
                 // for my parameter, and (owner_results) the partial sums
@@ -750,10 +713,10 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
                     __syncthreads();
                 e.template owner_publish<Model<MODEL % kVariantModel>::kHasPrior>(p, nx);
                 e.tick++;
-                OB_STAMP_END;
+                e.stamp_end();
                 __syncthreads();
 #ifdef APEMOST_STAMPS
-                ob_total += __builtin_amdgcn_s_memtime() - ob_t0;
+                e.ob_total += __builtin_amdgcn_s_memtime() - e.ob_t0;
 #endif
                 p ^= 1;
                 open = true;
@@ -764,10 +727,10 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
             if (my_sample)
                 my_sample += sample_stride;
         }
-        OB_STAMP_FLUSH;
+        e.stamps_flush();
 #ifdef APEMOST_STAMPS
         if (blockIdx.x == 0 && e.lane == 0) {
-            atomicAdd(&g_stamps[15], ob_total);
+            atomicAdd(&g_stamps[15], e.ob_total);
 #ifndef APEMOST_STAMP_PHASES
             if (LW == 4) // (slots 8..13 are free with eight waves per workgroup)
 #else
@@ -981,7 +944,8 @@ void pt_calibrate_kernel(const CalibArgs grid) {
     // per SIMD (pulse_vrot: 238 VGPRs with the record in LDS, 270 + 14 AGPRs without).  Thread 0
     // writes it, a barrier publishes it to every wave.
     static_assert(sizeof(CalibRec) == 6 * sizeof(double), "the record fills the control words of the LDS carve");
-    volatile CalibRec &r = *(volatile CalibRec *)(lds + 2 * kWave + 32 + 2);
+    static_assert(kLdsCalibRec * sizeof(double) + sizeof(CalibRec) <= kLdsLogTab * sizeof(double), "the record ends inside the control words");
+    volatile CalibRec &r = *(volatile CalibRec *)(lds + kLdsCalibRec);
     Engine<MODEL, WAVES, LDS_DATA, PROD> e;
     const int slot = grid.list[blockIdx.x];
     const int c = grid.first + slot;
@@ -1148,7 +1112,6 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
     const int slot = a.list[blockIdx.x];
     const int c = a.first + slot;
     e.setup_common(a.d, a.sh, c, lds);
-    volatile int *s_steps = (volatile int *)(lds + kObCtl); // word 0 (word 2 is the fail flag)
     if (e.is_lik()) {
         e.setup_lik(a.d, a.sh, c);
         if (e.hw < 2)
@@ -1159,7 +1122,7 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
         // change at 2 -- tools/experiments/r04_session17.sh -- not taken)
         for (;;) {
             __syncthreads(); // the block's opening barrier
-            const int n_steps = __builtin_amdgcn_readfirstlane(*s_steps);
+            const int n_steps = __builtin_amdgcn_readfirstlane(*e.block_steps());
             if (n_steps == 0)
                 break;
             int p = 0;
@@ -1177,18 +1140,13 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
         e.producer_prologue();
         __syncthreads();
         for (;;) {
-            __syncthreads();
-            const int n_steps = __builtin_amdgcn_readfirstlane(*s_steps);
+            __syncthreads(); // the block's opening barrier
+            const int n_steps = __builtin_amdgcn_readfirstlane(*e.block_steps());
             if (n_steps == 0)
                 break;
             int p = 0;
-            for (int s = 0; s < n_steps; s++) {
-                if (e.redraw_pending(p))
-                    __syncthreads();
-                e.producer_step(p);
-                __syncthreads();
-                p ^= 1;
-            }
+            for (int s = 0; s < n_steps; s++)
+                p = e.template closed_step<OB_PRODUCER>(p);
         }
     } else if (e.is_helper()) {
         if constexpr (decltype(e)::kHelperWave) {
@@ -1196,18 +1154,13 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
             e.setup_helper(a.d, a.sh, c);
             __syncthreads();
             for (;;) {
-                __syncthreads();
-                const int n_steps = __builtin_amdgcn_readfirstlane(*s_steps);
+                __syncthreads(); // the block's opening barrier
+                const int n_steps = __builtin_amdgcn_readfirstlane(*e.block_steps());
                 if (n_steps == 0)
                     break;
                 int p = 0;
-                for (int s = 0; s < n_steps; s++) {
-                    if (e.redraw_pending(p))
-                        __syncthreads();
-                    e.helper_step(p);
-                    __syncthreads();
-                    p ^= 1;
-                }
+                for (int s = 0; s < n_steps; s++)
+                    p = e.template closed_step<OB_HELPER>(p);
             }
         }
     } else {
@@ -1264,7 +1217,7 @@ __global__ __launch_bounds__(ob_block(LW, HELPER)) __attribute__((amdgpu_waves_p
             if (n_steps)
                 e.owner_first(sweep ? 0 : -1);
             if (e.lane == 0)
-                *s_steps = n_steps;
+                *e.block_steps() = n_steps;
             __syncthreads(); // the block's opening barrier
             if (n_steps == 0)
                 break;

@@ -138,6 +138,9 @@ struct ObThreshold<APEMOST_MODEL_PULSE_VROT> : ObThreshold<APEMOST_MODEL_PULSE> 
     } while (0)
 #endif
 
+// The roles whose step reads no proposal row and so carries the redraw barrier in front of it (ObEngine::closed_step)
+enum ObRole { OB_PRODUCER, OB_HELPER };
+
 // HELPER: a ninth (LW + 5th) wavefront that computes the proposal's half of the threshold (the prior's logarithms);
 // for the models with a prior only, and only where the host finds one workgroup per CU (nine-wave workgroups do not
 // fit a CU twice under the kernel's register budget: ladders of 257-512 chains keep the eight-wave form).
@@ -161,6 +164,7 @@ struct ObEngine {
 #ifdef APEMOST_STAMPS
     u64 seg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     u64 seg_last = 0;
+    u64 ob_busy = 0, ob_t0 = 0, ob_total = 0;
 #endif
     static constexpr int kLikThreads = LW * kWave;
     static constexpr int kProducers = 3;
@@ -227,6 +231,10 @@ struct ObEngine {
     }
     __device__ __forceinline__ double2 *s_cand(u64 t) const { return (double2 *)(lds + kObCand) + (int)(t & 7) * kWave; }
     __device__ __forceinline__ double *s_urow(int parity) const { return lds + kObUserRow + parity * kWave; }
+    // the control words (int view of kObCtl).  Word 0: the calibration's steps in the block about to start (0: the
+    // launch is over), left by the owner in front of the block's opening barrier and read by every other wave behind
+    // it; word 2: Engine's fail flag slot
+    __device__ __forceinline__ volatile int *block_steps() const { return (volatile int *)(lds + kObCtl); }
     __device__ __forceinline__ volatile int *fail_flag() const { return (volatile int *)(lds + kObCtl) + 2; }
 
     // every wave: who am I, where is the data; stages the data vector (all threads copy)
@@ -920,6 +928,69 @@ struct ObEngine {
     __device__ __forceinline__ void owner_fetch_selected(int parity) {
         sel_a = cand() ? s_prop(parity, 0)[grp] : 0.0;
         sel_r = cand() ? s_prop(parity, 1)[grp] : 0.0;
+    }
+
+    // ---- the step protocol of the producers and the helper ----
+    //
+    // What makes the one-barrier kernels correct is that every wave of the workgroup takes the same barriers in the
+    // same order.  A step has one barrier more where s_flag(parity) says that a prepared proposal has to be redrawn
+    // (every wave reads the same word: here for the producers and the helper, inside lik_step / lik_step_user for the
+    // likelihood waves, in the kernels' owner loops for the owner), then its closing barrier; the parity flips
+    // behind it.  closed_step is that sequence for the producers and the helper: both one-barrier kernels run these
+    // roles' steps through it.  Where a block of steps opens (a round, a block of the calibration) is the kernels'
+    // business (pt_kernels.h).  The likelihood waves' and the owner's step loops are still written out in both
+    // kernels: this change kept the device assembly equal to its parent's, and those did not move under it.
+    // (the redraw flag requested first and looked at behind the producer's phase -- the candidates do not depend
+    // on it, only the barrier count does -- changes nothing: 2.131 vs 2.132e8 at config 2, session 20)
+    // (role_step is a member of its own on purpose: written out inside closed_step, the compiler's second look at
+    // the inlined body commutes one integer add in the pulse kernels, and the assembly no longer equals the parent's)
+    template <ObRole ROLE>
+    __device__ __forceinline__ void role_step(int parity) {
+        if (redraw_pending(parity))
+            __syncthreads();
+        if constexpr (ROLE == OB_PRODUCER)
+            producer_step(parity);
+        else
+            helper_step(parity);
+    }
+    template <ObRole ROLE>
+    __device__ __forceinline__ int closed_step(int parity) { // a step with its closing barrier; returns the next step's parity
+        stamp_begin();
+#if defined(APEMOST_STAMPS) && defined(APEMOST_STAMP_PHASES)
+        // the first producer's step by phase: g_stamps[8..10] instead of the owner's segments.  (Calibration launches
+        // of this twin add to these slots too; tools/ob_profile.py reads them around round launches only.)
+        const bool first_producer = ROLE == OB_PRODUCER && blockIdx.x == 0 && lane == 0 && hw == LW + 1;
+        const int ph = first_producer ? pipe_phase : 0;
+#endif
+        role_step<ROLE>(parity);
+        stamp_end();
+#if defined(APEMOST_STAMPS) && defined(APEMOST_STAMP_PHASES)
+        if (first_producer)
+            atomicAdd(&g_stamps[8 + ph], __builtin_amdgcn_s_memtime() - ob_t0);
+#endif
+        __syncthreads();
+        return parity ^ 1;
+    }
+
+    // ---- the diagnostic build (-DAPEMOST_STAMPS; empty in the product): per wave of workgroup 0, the cycles between
+    // leaving a step's barrier and arriving at the next one (g_stamps[wave], the helper's in slot 14; slots 8-13: the
+    // owner's segments when LW = 4; g_stamps[15] = whole steps of the owner, barrier to barrier).  Tells which role
+    // the others wait for.  The round kernel flushes; the calibration kernel counts and drops the sum. ----
+    __device__ __forceinline__ void stamp_begin() { // a step starts: the wave left a barrier
+#ifdef APEMOST_STAMPS
+        ob_t0 = __builtin_amdgcn_s_memtime();
+#endif
+    }
+    __device__ __forceinline__ void stamp_end() { // ... and arrives at the step's closing barrier
+#ifdef APEMOST_STAMPS
+        ob_busy += __builtin_amdgcn_s_memtime() - ob_t0;
+#endif
+    }
+    __device__ __forceinline__ void stamps_flush() const { // the launch's sum leaves through g_stamps
+#ifdef APEMOST_STAMPS
+        if (blockIdx.x == 0 && lane == 0)
+            atomicAdd(&g_stamps[is_helper() ? 14 : hw], ob_busy);
+#endif
     }
 };
 
