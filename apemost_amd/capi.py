@@ -104,6 +104,19 @@ class MbarSums(C.Structure):
     _fields_ = [("m", _dp), ("S0", _dp), ("S1", _dp), ("S2", _dp), ("SS", _dp), ("G", _dp), ("ell_first", _dp)]
 
 
+class ReweightConfig(C.Structure):
+    _fields_ = [("n_cols", C.c_int32), ("cols", C.POINTER(C.c_int32)), ("nbins", C.c_int32), ("lo", _dp), ("hi", _dp)]
+
+
+class ReweightView(C.Structure):
+    _fields_ = [("n", _up), ("n_bad", _up), ("x", _dp)]
+
+
+class ReweightSums(C.Structure):
+    _fields_ = [("m", _dp), ("S0", _dp), ("SS", _dp), ("origin", _dp), ("S1", _dp), ("cross", _dp),
+                ("shift", C.POINTER(C.c_int32)), ("hist", _up), ("q_total", _up)]
+
+
 class AutocorrConfig(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("max_lag", C.c_int32), ("n_cols", C.c_int32),
                 ("cols", C.POINTER(C.c_int32))]
@@ -209,6 +222,9 @@ EXPORTS = [
     "apemost_hip_evidence_set", "apemost_hip_evidence_end",
     "apemost_hip_mbar_begin", "apemost_hip_mbar_accumulate", "apemost_hip_mbar_get", "apemost_hip_mbar_set",
     "apemost_hip_mbar_end", "apemost_hip_mbar_iterate", "apemost_hip_mbar_evaluate", "apemost_hip_mbar_log_weights",
+    "apemost_hip_reweight_begin", "apemost_hip_reweight_accumulate", "apemost_hip_reweight_get",
+    "apemost_hip_reweight_set", "apemost_hip_reweight_end", "apemost_hip_reweight_evaluate",
+    "apemost_hip_reweight_weights",
     "apemost_hip_autocorr_begin", "apemost_hip_autocorr_accumulate", "apemost_hip_autocorr_get",
     "apemost_hip_autocorr_set", "apemost_hip_autocorr_end",
     "apemost_hip_predict_begin", "apemost_hip_predict_accumulate", "apemost_hip_predict_get",
@@ -362,6 +378,13 @@ def lib():
     L.apemost_hip_mbar_iterate.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp]
     L.apemost_hip_mbar_evaluate.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, _dp, C.c_int32, C.POINTER(MbarSums)]
     L.apemost_hip_mbar_log_weights.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, C.c_double, _dp]
+    L.apemost_hip_reweight_begin.argtypes = [vp, C.POINTER(ReweightConfig)]
+    L.apemost_hip_reweight_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.apemost_hip_reweight_get.argtypes = [vp, C.POINTER(ReweightView)]
+    L.apemost_hip_reweight_set.argtypes = [vp, C.POINTER(ReweightView)]
+    L.apemost_hip_reweight_end.argtypes = [vp]
+    L.apemost_hip_reweight_evaluate.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, _dp, C.c_int32, C.POINTER(ReweightSums)]
+    L.apemost_hip_reweight_weights.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, C.c_double, _dp, _up]
     L.apemost_hip_autocorr_begin.argtypes = [vp, C.POINTER(AutocorrConfig)]
     L.apemost_hip_autocorr_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
     L.apemost_hip_autocorr_get.argtypes = [vp, C.POINTER(AutocorrView)]

@@ -29,6 +29,7 @@ extern "C" int apemost_hip_mbar_begin(apemost_hip_sampler *s, const apemost_hip_
         return fail(APEMOST_HIP_ERR_INVALID, "mbar_begin: capacity %llu outside [1, %llu]: capacity x %zu chains is at "
                     "most 2^28 values", (unsigned long long)cfg->capacity, (unsigned long long)(kMbarMaxValues / nc), nc);
     FOLD_TRY(fold_reset(s, s->mb));
+    fold_free(s->rw); // (an attached reweight fold goes with the store whose capacity it shared)
     MbarFold &f = s->mb;
     f.K = K;
     f.L = L;
@@ -109,7 +110,9 @@ extern "C" int apemost_hip_mbar_set(apemost_hip_sampler *s, const apemost_hip_mb
 
 extern "C" int apemost_hip_mbar_end(apemost_hip_sampler *s) {
     CHECK_S(s);
-    return fold_reset(s, s->mb);
+    FOLD_TRY(fold_reset(s, s->mb));
+    fold_free(s->rw); // (its capacity was this fold's)
+    return APEMOST_HIP_OK;
 }
 
 // ---- computing on the store ----

@@ -139,6 +139,23 @@ struct MbarFold {
     FoldMem mem;
 };
 
+// on-device reweighted posteriors (pt_reweight.h): chosen columns of every kept step of every chain, beside an open
+// MbarFold whose capacity, ladders and ranges it shares; n = kept steps stored
+struct ReweightFold {
+    bool open;
+    int n_cols, nbins, words; // words: 2 + n_cols + n_cols (n_cols + 1) / 2 sums per (ladder, target)
+    int cols[16];
+    u64 n;
+    double *d_x;              // [n_cols][capacity][n_chains]
+    double *d_lo, *d_hi;      // [n_cols]
+    double *d_e;              // [capacity][n_chains]: e of the target under way
+    unsigned long long *d_q;  // [capacity][n_chains]: its fixed-point image
+    double *d_beta_t;         // [64]
+    double *d_part;           // [words][n_ladders][tiles_max]
+    unsigned long long *d_bad, *d_mkey; // [n_ladders][n_cols], [64][n_ladders]
+    FoldMem mem;
+};
+
 // on-device autocorrelation (pt_autocorr.h): lag sums of kept chains' columns
 struct AutocorrFold {
     bool open;
@@ -346,6 +363,7 @@ struct apemost_hip_sampler {
     CheckFold ck;
     PeriodogramFold pg;
     MbarFold mb;
+    ReweightFold rw;
 };
 
 // the data rows of ladder b and its column-major matrix on the device (an ordinary sampler: b = 0)
@@ -404,6 +422,7 @@ static void release(apemost_hip_sampler *s) {
     fold_free(s->ck);
     fold_free(s->pg);
     fold_free(s->mb);
+    fold_free(s->rw);
     if (s->ev_copy)
         hipEventDestroy(s->ev_copy);
     for (int k = 0; k < 2; k++) {

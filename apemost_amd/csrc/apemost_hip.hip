@@ -13,6 +13,7 @@
 #include "pt_pointwise_joint.h"
 #include "pt_pointwise_tail.h"
 #include "pt_predict.h"
+#include "pt_reweight.h"
 #include "pt_user_fold.h"
 #include "pt_summary.h"
 #include "pt_text.h"
@@ -1925,6 +1926,7 @@ extern "C" int apemost_hip_samples_wait(apemost_hip_sampler *s) {
 #include "abi/fold_check.h"
 #include "abi/fold_periodogram.h"
 #include "abi/fold_mbar.h"
+#include "abi/fold_reweight.h"
 
 // Host arithmetic only (no device): tools/peaks.c:130, 177-200 and the selection sort of src/gsl_helper.c:102-127.
 extern "C" int apemost_hip_peaks_table(const apemost_hip_peaks_view *v, int32_t n_par, int32_t k, int32_t p,

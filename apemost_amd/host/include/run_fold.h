@@ -1,5 +1,5 @@
 /* The folds of the run phase: what the APEMOST_DUMP tokens summary, peaks, joint, derived, evidence, autocorr, predict,
- * pointwise, check, periodogram and mbar leave of the kept sample rows without a sample file (src/parallel_tempering.c documents the tokens,
+ * pointwise, check, periodogram, mbar and reweight leave of the kept sample rows without a sample file (src/parallel_tempering.c documents the tokens,
  * each fold's own header its files).  One descriptor per fold in the table run_folds[] of src/run_fold.c: the one
  * place a new token is added (a fold that refuses something at parse time adds that to run_folds_check() beside the
  * table: those refusals keep an order of their own, which is not the table's).  The run phase parses APEMOST_DUMP against the table into a mask (bit k: run_folds[k])
@@ -11,6 +11,7 @@
 #include "apemost_bridge.h"
 #include "apemost_hip.h"
 #include "mcmc.h"
+#include "run_mbar.h"
 
 /* what a fold sees of the run: filled once, before the folds open */
 typedef struct {
@@ -39,7 +40,7 @@ typedef struct {
     int (*accumulate)(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip, uint64_t thin);
 } run_fold;
 
-#define RUN_FOLDS 11
+#define RUN_FOLDS 12
 extern const run_fold run_folds[RUN_FOLDS];
 
 /* APEMOST_DUMP, a comma separated list: the item after the one at `spec`, or NULL; 1 when the list holds `token` (an
@@ -49,8 +50,9 @@ int run_dump_requested(const char *token);
 int run_fold_find(const char *spec);
 
 /* what the requested folds refuse at parse time, before any file is opened: a malformed APEMOST_POINTWISE_TAIL or
- * APEMOST_CHECK_BINS, a missing or malformed APEMOST_PERIODOGRAM_FREQS, a summary under -DHISTOGRAMS_MINMAX, and mbar
- * on more than one shard or with a malformed APEMOST_MBAR_TOL or APEMOST_MBAR_ITER */
+ * APEMOST_CHECK_BINS, a missing or malformed APEMOST_PERIODOGRAM_FREQS, a summary under -DHISTOGRAMS_MINMAX, mbar
+ * on more than one shard or with a malformed APEMOST_MBAR_TOL or APEMOST_MBAR_ITER, and reweight without mbar in the
+ * same list or with a malformed APEMOST_REWEIGHT_BINS or APEMOST_REWEIGHT_BETAS */
 void run_folds_check(unsigned int mask);
 /* the kept samples a bounded run will produce from iteration `iter` on; an unbounded run ends the program */
 uint64_t planned_samples(const char *token, const char *why, unsigned int n_swap, unsigned long iter,
@@ -79,5 +81,8 @@ void run_periodogram_open(const run_fold_ctx *c, uint64_t planned), run_periodog
 /* APEMOST_PERIODOGRAM_FREQS=lo:hi:n, which the token requires: an unset or malformed value ends the program */
 void run_periodogram_check_env(void);
 void run_mbar_open(const run_fold_ctx *c, uint64_t planned), run_mbar_close(const run_fold_ctx *c);
+void run_reweight_open(const run_fold_ctx *c, uint64_t planned), run_reweight_close(const run_fold_ctx *c);
+/* the mbar fold's close calls it between its solve and its end, while both stores are on the device (src/run_reweight_device.c) */
+void run_reweight_solved(const run_fold_ctx *c, const run_mbar *m);
 
 #endif

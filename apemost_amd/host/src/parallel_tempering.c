@@ -262,6 +262,14 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            solver's tolerance and iteration cap.  Needs a bounded run, positive, strictly decreasing betas and the
  *            whole ladder on one device.  Combines with every other token and writes no sample file by itself, like
  *            periodogram
+ *   reweight keep the parameters of EVERY kept step of EVERY chain on the device beside the token mbar, which it needs
+ *            in the same list, and at the end, behind MBAR's solve, form there the posterior's moments and marginal
+ *            histograms from all chains' samples with the MBAR weights: write reweight.bin (the sums and the
+ *            fixed-point histograms) and reweight.txt (per target and parameter beta, name, mean, sd and the effective
+ *            sample size; run_reweight.h).  APEMOST_REWEIGHT_BETAS (a comma list of targets >= 0, sampled or not,
+ *            default 1) and APEMOST_REWEIGHT_BINS (default 200) set the targets and the bins; the ranges are the
+ *            params file's.  Needs what mbar needs and no --append.  Combines with every other token and writes no
+ *            sample file by itself, like mbar
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */
@@ -306,7 +314,7 @@ static void sink_parse(sample_sink *k) {
         else if ((fold = run_fold_find(spec)) >= 0)
             k->folds |= 1u << fold;
         else {
-            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived, check, periodogram, mbar; got '%s'\n", spec);
+            fprintf(stderr, "APEMOST_DUMP: expected a comma separated list of text, binary, binary:all, thin:N, summary, peaks, joint, evidence, autocorr, predict, pointwise, derived, check, periodogram, mbar, reweight; got '%s'\n", spec);
             exit(1);
         }
     }

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "run_mbar.h"
+#include "run_reweight.h"
 
 #define BATCH_SIZE_WHY "the batch size of the error estimate is fixed before the first sample"
 #define KEPT_ON_DEVICE_WHY "the columns kept on the device are sized before the first sample"
@@ -13,7 +14,8 @@
 /* In the order the folds open and close.  Only summary and evidence fold every chain, so one fold per shard; the
  * others fold chain 0, which lives on shard 0.  joint and autocorr size nothing by the samples to come and run
  * unbounded too, and so does check; predict needs the bound only for its refusal, and so does periodogram.  mbar keeps
- * every chain's column on one device: its one fold is shard 0's, and more shards than that are refused below. */
+ * every chain's column on one device: its one fold is shard 0's, and more shards than that are refused below.  reweight
+ * keeps the parameters beside it and is evaluated from mbar's close, behind its solve: it needs mbar in the same list. */
 const run_fold run_folds[RUN_FOLDS] = {
     {"summary", BATCH_SIZE_WHY, 1, run_summary_open, run_summary_close, apemost_hip_summary_accumulate},
     {"peaks", KEPT_ON_DEVICE_WHY, 0, run_peaks_open, run_peaks_close, apemost_hip_peaks_accumulate},
@@ -28,7 +30,8 @@ const run_fold run_folds[RUN_FOLDS] = {
     {"check", NULL, 0, run_check_open, run_check_close, apemost_hip_check_accumulate},
     {"periodogram", "periodogram.bin and periodogram.txt are written when the run ends", 0, run_periodogram_open,
      run_periodogram_close, apemost_hip_periodogram_accumulate},
-    {"mbar", KEPT_ON_DEVICE_WHY, 0, run_mbar_open, run_mbar_close, apemost_hip_mbar_accumulate}};
+    {"mbar", KEPT_ON_DEVICE_WHY, 0, run_mbar_open, run_mbar_close, apemost_hip_mbar_accumulate},
+    {"reweight", KEPT_ON_DEVICE_WHY, 0, run_reweight_open, run_reweight_close, apemost_hip_reweight_accumulate}};
 
 static int item_is(const char *spec, const char *token) {
     const size_t len = strlen(token);
@@ -84,6 +87,15 @@ void run_folds_check(unsigned int mask) {
         }
         (void)run_mbar_tol_from_env();
         (void)run_mbar_iter_from_env();
+    }
+    if (in_mask(mask, "reweight")) {
+        double betas[RUN_REWEIGHT_MAX_TARGETS];
+        if (!in_mask(mask, "mbar")) {
+            fprintf(stderr, "APEMOST_DUMP=reweight needs mbar in the same list: the weights are the mbar fold's\n");
+            exit(1);
+        }
+        (void)run_reweight_bins_from_env();
+        (void)run_reweight_betas_from_env(betas);
     }
 }
 

@@ -124,6 +124,7 @@ void run_mbar_close(const run_fold_ctx *ctx) {
             run_mbar_write_text(RUN_MBAR_TEXT, r, &p, tol, max_iter);
         }
     }
+    run_reweight_solved(ctx, r); /* (the token `reweight`: evaluated here, before the end drops its store) */
     apemost_hip_or_die(apemost_hip_mbar_end(sampler), "mbar_end");
     run_mbar_write(RUN_MBAR_FILE, r);
     run_mbar_free(r);

@@ -667,6 +667,45 @@ class HipSampler:
     def mbar_end(self):
         capi.check(self.L.apemost_hip_mbar_end(self._h))
 
+    # -- on-device reweighted posteriors (apemost_amd/reweight.py) ----------------------------------
+    def reweight_begin(self, cols=None, lo=None, hi=None, nbins=200):
+        """start the store of the columns `cols` (None: the parameters; at most 16, strictly increasing) of every kept
+        step of every local chain beside the open mbar fold, before its first mbar_accumulate: the capacity is that
+        fold's.  lo, hi [n_cols]: the histogram ranges (nbins = 0: no histograms)."""
+        from .reweight import check_cols
+        self._rw_cols = check_cols(np.arange(self.n_par) if cols is None else cols, self.n_par)
+        k = len(self._rw_cols)
+        self._rw_nbins = int(nbins)
+        self._rw_lo = np.zeros(k) if lo is None else np.ascontiguousarray(lo, dtype=np.float64).reshape(k)
+        self._rw_hi = np.zeros(k) if hi is None else np.ascontiguousarray(hi, dtype=np.float64).reshape(k)
+        cfg = capi.ReweightConfig(n_cols=k, cols=self._rw_cols.ctypes.data_as(C.POINTER(C.c_int32)), nbins=self._rw_nbins,
+                                  lo=self._rw_lo.ctypes.data_as(capi._dp), hi=self._rw_hi.ctypes.data_as(capi._dp))
+        capi.check(self.L.apemost_hip_reweight_begin(self._h, C.byref(cfg)))
+
+    def reweight_accumulate(self, d_samples, n_steps, skip=0, thin=1):
+        """append the kept steps skip, skip + thin, ... of the device rows [n_steps][n_chains][n_par+2]: the rows
+        mbar_accumulate is given, by a call of its own; asynchronous like it"""
+        capi.check(self.L.apemost_hip_reweight_accumulate(self._h, d_samples, n_steps, skip, thin))
+
+    def reweight(self):
+        """the store so far as a Reweight whose sums run on this sampler's device (synchronises with the accumulates
+        issued so far); good until the next mbar_begin, reweight_begin, reweight_set or either end"""
+        from .reweight import Reweight
+        n = np.zeros(1, dtype=np.uint64)
+        capi.check(self.L.apemost_hip_reweight_get(self._h, C.byref(capi.ReweightView(n=n.ctypes.data_as(capi._up)))))
+        rw = Reweight(np.zeros((len(self._rw_cols), int(n[0]), self.n_chains)), self._rw_cols, self._rw_lo, self._rw_hi,
+                      self._rw_nbins, self.n_ladders, None, self._mb_thin, self)
+        capi.check(self.L.apemost_hip_reweight_get(self._h, C.byref(rw.view())))
+        return rw
+
+    def reweight_set(self, rw):
+        """load a Reweight's store (a resumed run, after mbar_set) into the fold begun with the same columns"""
+        assert rw.cols.tobytes() == self._rw_cols.tobytes() and rw.n <= self._mb_capacity
+        capi.check(self.L.apemost_hip_reweight_set(self._h, C.byref(rw.view())))
+
+    def reweight_end(self):
+        capi.check(self.L.apemost_hip_reweight_end(self._h))
+
     # -- on-device autocorrelation (apemost_amd/autocorr.py) ----------------------------------------
     def autocorr_begin(self, chains=(0,), max_lag=1024, cols=None, thin=1):
         """start the lag sums of the columns `cols` (None: the parameters and prob - prior) of the local chains

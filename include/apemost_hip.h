@@ -889,6 +889,72 @@ int apemost_hip_mbar_evaluate(apemost_hip_sampler *s, uint64_t t0, uint64_t t_co
 int apemost_hip_mbar_log_weights(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, const double *g, double beta_t,
                                  double *host_out);
 
+/* ---- on-device reweighted posteriors: moments and marginals at any beta from every chain --------
+ * The posterior's moments and marginal histograms at any beta_t >= 0, sampled or not, estimated from EVERY kept step of
+ * EVERY chain with the MBAR weights, without a sample dump.  The fold is attached to an open mbar fold with nothing
+ * stored yet and keeps, for n_cols chosen columns of the sample row, the value of every kept step of every chain:
+ * x[n_cols][capacity][n_chains], the capacity being the mbar fold's; n_cols * capacity * n_chains <= 2^30 values.
+ * Per ladder over the kept steps [t0, t0 + t_count), N = t_count * K samples in mbar's stored order, for a target
+ * beta_t: lnD_n, x_tn = beta_t l_n - lnD_n, the exact maximum m_t and e_n = exp(x_tn - m_t) are mbar_evaluate's.  With
+ * origin_a the column's value at the range's first sample of the ladder and d_a = x_a,n - origin_a:
+ *   S0 = sum e,  SS = sum e e,  S1[a] = sum e d_a,  cross[a][b] = sum (e d_a) d_b  (a <= b)
+ * in mbar's fixed order (tiles of 4096, 64 lane partials, the adjacent-pairs tree, tiles in order; csrc/pt_reweight.h),
+ * so m, S0 and SS equal mbar_evaluate's on the bits.  E[x_a] = origin_a + S1[a] / S0, Cov[x_a, x_b] = cross[a][b] / S0
+ * - (S1[a] / S0)(S1[b] / S0), Kish's effective sample size S0^2 / SS.
+ * Histograms: the run summary's bins over [lo[a], hi[a]] (values outside, NaN included, are not counted), weighted by
+ * the fixed-point integers q_n = (uint64) rint(ldexp(e_n, shift)), shift = 63 - bit_length(N): exact scaling, one
+ * rounding, sum q < 2^63, integer sums that do not depend on the grid or the order.  A bin differs from 2^shift sum e
+ * by at most N_bin / 2; relative to the normalisation the error is at most N 2^-(shift+1) / ESS.
+ * The two stores advance by separate calls: mbar_accumulate and reweight_accumulate (mbar_set and reweight_set) of
+ * the same rows; evaluate and weights refuse with "stores out of step" while the kept counts differ.  mbar_begin and
+ * mbar_end drop an attached reweight fold.  Whole ladders, ladder batches and ragged batches; every model (the fold
+ * evaluates none); a shard of a sharded ladder is APEMOST_HIP_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t n_cols;           /* 1 .. 16 */
+    const int32_t *cols;      /* host [n_cols]: columns of the row, 0 .. n_par+1, strictly increasing */
+    int32_t nbins;            /* 0: no histograms; else 1 .. 4096 */
+    const double *lo, *hi;    /* host [n_cols]: the histogram ranges (nbins > 0) */
+} apemost_hip_reweight_config;
+typedef struct {
+    uint64_t *n;              /* kept steps stored */
+    uint64_t *n_bad;          /* [n_ladders][n_cols]: stored values that are not finite */
+    double *x;                /* [n_cols][n][n_chains]: the first n rows of every column */
+} apemost_hip_reweight_view;  /* host arrays; any pointer may be NULL (that part is skipped) */
+typedef struct {
+    double *m, *S0, *SS;      /* [n_ladders][n_t] */
+    double *origin;           /* [n_ladders][n_cols] */
+    double *S1;               /* [n_ladders][n_t][n_cols] */
+    double *cross;            /* [n_ladders][n_t][n_cols (n_cols + 1) / 2]: the upper triangle, row-major */
+    int32_t *shift;           /* [1] */
+    uint64_t *hist;           /* [n_ladders][n_t][n_cols][nbins] */
+    uint64_t *q_total;        /* [n_ladders][n_t]: sum of q over all samples of the range */
+} apemost_hip_reweight_sums;  /* host arrays; any pointer may be NULL (that part is skipped) */
+
+/* allocates the columns' store and the scratch.  Needs an open mbar fold with nothing stored.  A reweight fold begun
+ * before is dropped once the new configuration has been accepted.  APEMOST_HIP_ERR_INVALID, before any device work and
+ * naming the offender, for a NULL config, columns out of range or not increasing, nbins outside [0, 4096], a bad
+ * range, or a store above 2^30 values (the message gives the largest n_cols that fits). */
+int apemost_hip_reweight_begin(apemost_hip_sampler *s, const apemost_hip_reweight_config *cfg);
+/* appends the columns of the kept steps skip, skip + thin, ... of d_samples (DEVICE [n_steps][n_chains][n_par+2]).
+ * Asynchronous and queued like apemost_hip_mbar_accumulate; refused beyond the mbar fold's capacity. */
+int apemost_hip_reweight_accumulate(apemost_hip_sampler *s, const double *d_samples, uint64_t n_steps, uint64_t skip,
+                                    uint64_t thin);
+/* copies the store out (synchronises with the accumulates issued so far) */
+int apemost_hip_reweight_get(apemost_hip_sampler *s, const apemost_hip_reweight_view *v);
+/* loads a view saved by reweight_get (after mbar_set: the resumed run); APEMOST_HIP_ERR_INVALID when n > capacity */
+int apemost_hip_reweight_set(apemost_hip_sampler *s, const apemost_hip_reweight_view *v);
+/* frees the store (mbar_begin, mbar_end and apemost_hip_destroy do too) */
+int apemost_hip_reweight_end(apemost_hip_sampler *s);
+/* the sums above for the targets betas_t [n_t], 1 <= n_t <= 64, each finite and >= 0, shared by all ladders, and the
+ * free energies g [n_chains].  n_ladders * n_t * n_cols * nbins <= 2^24.  The refusals of mbar_iterate, "stores out of
+ * step", and a non-zero n_bad of a column (the message gives the count).  Synchronises. */
+int apemost_hip_reweight_evaluate(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, const double *g,
+                                  const double *betas_t, int32_t n_t, const apemost_hip_reweight_sums *out);
+/* host_e, host_q [t_count][n_chains] (either may be NULL): e_n and q_n of one target, those the evaluation uses, with
+ * which a caller reweights rows of its own.  The refusals of reweight_evaluate. */
+int apemost_hip_reweight_weights(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, const double *g, double beta_t,
+                                 double *host_e, uint64_t *host_q);
+
 /* ---- on-device autocorrelation: lag sums, integrated times, effective sample size ---------------
  * How many independent samples a run holds: what the autocorrelation function of sample columns needs, accumulated
  * from the sample rows while they are still on the device.  A series is one (kept chain, column) pair, series
