@@ -117,6 +117,10 @@ class ReweightSums(C.Structure):
                 ("shift", C.POINTER(C.c_int32)), ("hist", _up), ("q_total", _up)]
 
 
+class ReweightDraws(C.Structure):
+    _fields_ = [("index", C.POINTER(C.c_uint32)), ("x", _dp), ("q_total", _up), ("shift", C.POINTER(C.c_int32))]
+
+
 class AutocorrConfig(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("chains", C.POINTER(C.c_int32)), ("max_lag", C.c_int32), ("n_cols", C.c_int32),
                 ("cols", C.POINTER(C.c_int32))]
@@ -224,7 +228,7 @@ EXPORTS = [
     "apemost_hip_mbar_end", "apemost_hip_mbar_iterate", "apemost_hip_mbar_evaluate", "apemost_hip_mbar_log_weights",
     "apemost_hip_reweight_begin", "apemost_hip_reweight_accumulate", "apemost_hip_reweight_get",
     "apemost_hip_reweight_set", "apemost_hip_reweight_end", "apemost_hip_reweight_evaluate",
-    "apemost_hip_reweight_weights",
+    "apemost_hip_reweight_weights", "apemost_hip_reweight_resample",
     "apemost_hip_autocorr_begin", "apemost_hip_autocorr_accumulate", "apemost_hip_autocorr_get",
     "apemost_hip_autocorr_set", "apemost_hip_autocorr_end",
     "apemost_hip_predict_begin", "apemost_hip_predict_accumulate", "apemost_hip_predict_get",
@@ -385,6 +389,8 @@ def lib():
     L.apemost_hip_reweight_end.argtypes = [vp]
     L.apemost_hip_reweight_evaluate.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, _dp, C.c_int32, C.POINTER(ReweightSums)]
     L.apemost_hip_reweight_weights.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, C.c_double, _dp, _up]
+    L.apemost_hip_reweight_resample.argtypes = [vp, C.c_uint64, C.c_uint64, _dp, C.c_double, C.c_uint32, C.c_uint64,
+                                                C.POINTER(ReweightDraws)]
     L.apemost_hip_autocorr_begin.argtypes = [vp, C.POINTER(AutocorrConfig)]
     L.apemost_hip_autocorr_accumulate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64]
     L.apemost_hip_autocorr_get.argtypes = [vp, C.POINTER(AutocorrView)]

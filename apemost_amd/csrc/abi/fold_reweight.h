@@ -2,12 +2,14 @@
 // abi/fold_common.h).  The fold is attached to the open MBAR fold (abi/fold_mbar.h): the capacity, the ladders and the
 // ranges are that fold's, the two stores advance by separate accumulates and every entry point that computes refuses
 // while their kept counts differ.  evaluate and weights run on copy_stream behind every accumulate and return when
-// their results are on the host.
+// their results are on the host; so does resample (pt_resample.h), whose scratch the fold's first resample allocates
+// at the fold's capacity and the fold's memory frees.
 #pragma once
 
 constexpr u64 kReweightMaxValues = (u64)1 << 30; // n_cols x capacity x n_chains
 constexpr int kReweightMaxTargets = 64;
 constexpr u64 kReweightMaxCounts = (u64)1 << 24; // n_ladders x n_t x n_cols x nbins
+constexpr u64 kResampleMaxValues = (u64)1 << 26; // n_ladders x n_draws x n_cols
 
 extern "C" int apemost_hip_reweight_begin(apemost_hip_sampler *s, const apemost_hip_reweight_config *cfg) {
     CHECK_S(s);
@@ -286,4 +288,66 @@ extern "C" int apemost_hip_reweight_weights(apemost_hip_sampler *s, uint64_t t0,
     FOLD_TRY(down(f.d_e, host_e, count * sizeof(double)));
     FOLD_TRY(down(f.d_q, host_q, count * sizeof(uint64_t)));
     return fold_xfer_wait(s); // (beta_t lives until here)
+}
+
+extern "C" int apemost_hip_reweight_resample(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, const double *g,
+                                             double beta_t, uint32_t n_draws, uint64_t u,
+                                             const apemost_hip_reweight_draws *out) {
+    CHECK_S(s);
+    if (!g)
+        return fail(APEMOST_HIP_ERR_INVALID, "reweight_resample: g is NULL");
+    if (!out)
+        return fail(APEMOST_HIP_ERR_INVALID, "reweight_resample: out is NULL");
+    if (!std::isfinite(beta_t) || !(beta_t >= 0))
+        return fail(APEMOST_HIP_ERR_INVALID, "reweight_resample: the target is %g; a target is finite and >= 0", beta_t);
+    if (n_draws < 1 || n_draws > kResampleMaxDraws)
+        return fail(APEMOST_HIP_ERR_INVALID, "reweight_resample: n_draws %u outside [1,2^24]", n_draws);
+    ReweightFold &f = s->rw;
+    if (f.open && s->mb.open && (u64)s->mb.L * n_draws * (u64)f.n_cols > kResampleMaxValues)
+        return fail(APEMOST_HIP_ERR_INVALID, "reweight_resample: %d ladders x %u draws x %d columns are more than 2^26 "
+                    "values", s->mb.L, n_draws, f.n_cols);
+    ReweightArgs a{};
+    FOLD_TRY(reweight_range(s, "resample", t0, t_count, g, &a));
+    const MbarFold &mb = s->mb;
+    const int L = mb.L;
+    hipStream_t st = s->copy_stream;
+    if (!f.d_C) {
+        FOLD_TRY(fold_alloc(s, f.mem, &f.d_tsum, (size_t)L * mb.tiles_max + L, false));
+        FOLD_TRY(fold_alloc(s, f.mem, &f.d_C, (size_t)mb.capacity * s->cfg.n_chains, false));
+    }
+    HIP_TRY(hipMemcpyAsync(f.d_beta_t, &beta_t, sizeof(double), hipMemcpyHostToDevice, st));
+    FOLD_TRY(reweight_launch_weights(s, a, 0));
+    const size_t lm = (size_t)L * n_draws;
+    FoldScratch scratch;
+    unsigned int *d_index;
+    double *d_out;
+    FOLD_TRY(fold_alloc(s, scratch, &d_index, lm, false));
+    FOLD_TRY(fold_alloc(s, scratch, &d_out, lm * f.n_cols, false));
+    ResampleArgs r{};
+    r.m = a.m;
+    r.q = f.d_q;
+    r.x = f.d_x;
+    r.col_stride = a.col_stride;
+    r.n_cols = f.n_cols;
+    r.tsum = f.d_tsum;
+    r.total = f.d_tsum + (size_t)L * a.m.tiles;
+    r.C = f.d_C;
+    r.M = n_draws;
+    r.u = u;
+    r.index = d_index;
+    r.out = d_out;
+    const dim3 per_tile(a.m.tiles, (unsigned)L);
+    hipLaunchKernelGGL(resample_tile_sum_kernel, per_tile, dim3(kResampleThreads), 0, st, r);
+    hipLaunchKernelGGL(resample_tile_scan_kernel, dim3((unsigned)L), dim3(kResampleScanThreads), 0, st, r);
+    hipLaunchKernelGGL(resample_scan_kernel, per_tile, dim3(kResampleThreads), 0, st, r);
+    hipLaunchKernelGGL(resample_search_kernel, dim3((n_draws + kResampleThreads - 1) / kResampleThreads, (unsigned)L),
+                       dim3(kResampleThreads), 0, st, r);
+    HIP_TRY(hipGetLastError());
+    const FoldCopy down{s, false};
+    FOLD_TRY(down(d_index, out->index, lm * sizeof(unsigned int)));
+    FOLD_TRY(down(d_out, out->x, lm * f.n_cols * sizeof(double)));
+    FOLD_TRY(down(r.total, out->q_total, (size_t)L * sizeof(unsigned long long)));
+    if (out->shift)
+        *out->shift = a.shift;
+    return fold_xfer_wait(s); // (the scratch and beta_t live until here)
 }

@@ -153,6 +153,8 @@ struct ReweightFold {
     double *d_beta_t;         // [64]
     double *d_part;           // [words][n_ladders][tiles_max]
     unsigned long long *d_bad, *d_mkey; // [n_ladders][n_cols], [64][n_ladders]
+    unsigned long long *d_C, *d_tsum;   // pt_resample.h, from the first resample on: [capacity][n_chains] words of C;
+                                        // [n_ladders][tiles_max] tile prefixes and, behind them, [n_ladders] totals
     FoldMem mem;
 };
 

@@ -14,6 +14,7 @@
 #include "pt_pointwise_tail.h"
 #include "pt_predict.h"
 #include "pt_reweight.h"
+#include "pt_resample.h"
 #include "pt_user_fold.h"
 #include "pt_summary.h"
 #include "pt_text.h"

@@ -268,8 +268,12 @@ static unsigned long gcd_ul(unsigned long a, unsigned long b) {
  *            fixed-point histograms) and reweight.txt (per target and parameter beta, name, mean, sd and the effective
  *            sample size; run_reweight.h).  APEMOST_REWEIGHT_BETAS (a comma list of targets >= 0, sampled or not,
  *            default 1) and APEMOST_REWEIGHT_BINS (default 200) set the targets and the bins; the ranges are the
- *            params file's.  Needs what mbar needs and no --append.  Combines with every other token and writes no
- *            sample file by itself, like mbar
+ *            params file's.  APEMOST_RESAMPLE_DRAWS=M (0 .. 2^24, default 0: nothing) also draws, on the device, M
+ *            equally weighted samples per target from all chains' samples (systematic resampling over the fixed-point
+ *            weights; APEMOST_RESAMPLE_SEED, a uint64, default 0, is its offset word) and writes resample.bin and, for
+ *            target t, <paramname>-reweighted-<t>.dump, one "%.15e" line per draw, the format of
+ *            <paramname>-chain-0.prob.dump.  Needs what mbar needs and no --append.  Combines with every other token and
+ *            writes no sample file by itself, like mbar
  * The reference prints one line per chain per step with fprintf, which at device speed was the whole run
  * time.  Here the device formats the text lines (apemost_hip_samples_text_read_async, the
  * bytes glibc's printf gives) and the host only writes them: one fwrite per file and batch. */

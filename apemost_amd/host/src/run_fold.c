@@ -96,6 +96,8 @@ void run_folds_check(unsigned int mask) {
         }
         (void)run_reweight_bins_from_env();
         (void)run_reweight_betas_from_env(betas);
+        (void)run_resample_draws_from_env();
+        (void)run_resample_seed_from_env();
     }
 }
 

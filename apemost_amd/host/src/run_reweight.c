@@ -1,5 +1,5 @@
-/* reweight.bin reader and writer, reweight.txt and the environment of the APEMOST_DUMP token `reweight`
- * (run_reweight.h).  No device symbol. */
+/* reweight.bin reader and writer, reweight.txt, resample.bin, the resampled text dumps and the environment of the
+ * APEMOST_DUMP token `reweight` (run_reweight.h).  No device symbol. */
 #include "run_reweight.h"
 
 #include <math.h>
@@ -14,6 +14,8 @@
 
 #define RUN_REWEIGHT_MAGIC "APEMOSTW"
 #define RUN_REWEIGHT_VERSION 1
+#define RUN_RESAMPLE_MAGIC "APEMOSTS"
+#define RUN_RESAMPLE_VERSION 1
 
 void run_reweight_alloc(run_reweight *r) {
     const size_t k = r->n_cols, nt = r->n_t, ntri = run_tri_count(k);
@@ -185,4 +187,99 @@ unsigned int run_reweight_betas_from_env(double *betas) {
         p = end + 1;
     }
     return n;
+}
+
+/* a decimal uint64 up to `max`, the whole string; 0: malformed */
+static int parse_u64(const char *spec, uint64_t max, uint64_t *out) {
+    uint64_t v = 0;
+    const char *p = spec;
+    if (*p == 0)
+        return 0;
+    for (; *p != 0; p++) {
+        uint64_t d;
+        if (*p < '0' || *p > '9')
+            return 0;
+        d = (uint64_t)(*p - '0');
+        if (v > (max - d) / 10)
+            return 0;
+        v = v * 10 + d;
+    }
+    *out = v;
+    return 1;
+}
+
+uint32_t run_resample_draws_from_env(void) {
+    const char *spec = getenv("APEMOST_RESAMPLE_DRAWS");
+    uint64_t n;
+    if (spec == NULL || *spec == 0)
+        return 0;
+    if (!parse_u64(spec, RUN_RESAMPLE_MAX_DRAWS, &n)) {
+        fprintf(stderr, "APEMOST_RESAMPLE_DRAWS: expected an integer in 0 .. %lu, got '%s'\n", RUN_RESAMPLE_MAX_DRAWS, spec);
+        exit(1);
+    }
+    return (uint32_t)n;
+}
+
+uint64_t run_resample_seed_from_env(void) {
+    const char *spec = getenv("APEMOST_RESAMPLE_SEED");
+    uint64_t u;
+    if (spec == NULL || *spec == 0)
+        return 0;
+    if (!parse_u64(spec, ~(uint64_t)0, &u)) {
+        fprintf(stderr, "APEMOST_RESAMPLE_SEED: expected an integer in 0 .. 2^64 - 1, got '%s'\n", spec);
+        exit(1);
+    }
+    return u;
+}
+
+void run_resample_write(const char *path, const run_reweight *r, uint32_t n_draws, uint64_t u, const uint64_t *q_total,
+                        const uint32_t *index, const double *x) {
+    FILE *f = run_open_or_die(path, "wb");
+    const size_t k = r->n_cols;
+    uint32_t u32[8];
+    uint64_t u64[5];
+    unsigned int t;
+    u32[0] = RUN_RESAMPLE_VERSION;
+    u32[1] = r->n_chains;
+    u32[2] = 1;
+    u32[3] = r->n_cols;
+    u32[4] = r->n_t;
+    u32[5] = n_draws;
+    memcpy(&u32[6], &r->shift, sizeof(int32_t));
+    u32[7] = 0;
+    u64[0] = r->n;
+    u64[1] = r->thin;
+    u64[2] = r->t0;
+    u64[3] = r->t_count;
+    u64[4] = u;
+    fwrite(RUN_RESAMPLE_MAGIC, 1, 8, f);
+    fwrite(u32, sizeof(uint32_t), 8, f);
+    fwrite(u64, sizeof(uint64_t), 5, f);
+    fwrite(r->cols, sizeof(int32_t), RUN_REWEIGHT_MAX_COLS, f);
+    for (t = 0; t < r->n_t; t++) {
+        fwrite(&r->betas_t[t], sizeof(double), 1, f);
+        fwrite(&q_total[t], sizeof(uint64_t), 1, f);
+        fwrite(index + (size_t)t * n_draws, sizeof(uint32_t), n_draws, f);
+        fwrite(x + (size_t)t * n_draws * k, sizeof(double), (size_t)n_draws * k, f);
+    }
+    run_close_or_die(f, path);
+}
+
+void run_resample_write_dumps(const run_reweight *r, unsigned int t, uint32_t n_draws, const double *x,
+                              const char *const *names) {
+    const size_t k = r->n_cols;
+    unsigned int a;
+    uint32_t m;
+    for (a = 0; a < k; a++) {
+        char path[512];
+        FILE *f;
+        if (names != NULL)
+            sprintf(path, "%.400s-reweighted-%u.dump", names[a], t);
+        else
+            sprintf(path, "col%ld-reweighted-%u.dump", (long)r->cols[a], t);
+        f = run_open_or_die(path, "w");
+        for (m = 0; m < n_draws; m++)
+            fprintf(f, "%.15e\n", x[(size_t)m * k + a]);
+        run_close_or_die(f, path);
+    }
 }

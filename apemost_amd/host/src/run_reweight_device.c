@@ -13,6 +13,21 @@
 
 static run_reweight reweight;
 static int is_open, evaluated;
+/* APEMOST_RESAMPLE_DRAWS > 0: the draws of every target, kept from the solve to the close, which writes them */
+static uint32_t n_draws;
+static uint64_t draw_seed;
+static uint64_t *draw_q_total; /* [n_t] */
+static uint32_t *draw_index;   /* [n_t][n_draws] */
+static double *draw_x;         /* [n_t][n_draws][n_cols] */
+
+static void draws_free(void) {
+    free(draw_q_total);
+    free(draw_index);
+    free(draw_x);
+    draw_q_total = NULL;
+    draw_index = NULL;
+    draw_x = NULL;
+}
 
 /* the parameters of every chain beside the mbar fold, which the table has opened before (shard 0, the whole ladder).
  * reweight.bin holds the sums and not the columns, so there is nothing a later run could go on from. */
@@ -26,6 +41,8 @@ void run_reweight_open(const run_fold_ctx *ctx, uint64_t planned) {
     (void)planned; /* (the capacity is the mbar fold's) */
     memset(r, 0, sizeof *r);
     is_open = evaluated = 0;
+    n_draws = run_resample_draws_from_env();
+    draw_seed = run_resample_seed_from_env();
     if (ctx->append) {
         fprintf(stderr, "APEMOST_DUMP=reweight cannot go on from an earlier run (--append): %s holds the sums, not the "
                         "columns\n", RUN_REWEIGHT_FILE);
@@ -64,7 +81,7 @@ void run_reweight_solved(const run_fold_ctx *ctx, const run_mbar *m) {
     apemost_hip_reweight_view v;
     apemost_hip_reweight_sums out;
     uint64_t bad[RUN_REWEIGHT_MAX_COLS];
-    unsigned int p;
+    unsigned int p, t;
     if (!is_open)
         return;
     if (!m->solved) {
@@ -94,16 +111,39 @@ void run_reweight_solved(const run_fold_ctx *ctx, const run_mbar *m) {
     out.q_total = r->q_total;
     apemost_hip_or_die(apemost_hip_reweight_evaluate(sampler, m->t0, m->t_count, m->g, r->betas_t, (int32_t)r->n_t, &out),
                        "reweight_evaluate");
+    if (n_draws > 0) {
+        draw_q_total = (uint64_t *)run_alloc_or_die(r->n_t, sizeof(uint64_t), "resample");
+        draw_index = (uint32_t *)run_alloc_or_die((size_t)r->n_t * n_draws, sizeof(uint32_t), "resample");
+        draw_x = (double *)run_alloc_or_die((size_t)r->n_t * n_draws * r->n_cols, sizeof(double), "resample");
+        for (t = 0; t < r->n_t; t++) {
+            apemost_hip_reweight_draws d;
+            d.index = draw_index + (size_t)t * n_draws;
+            d.x = draw_x + (size_t)t * n_draws * r->n_cols;
+            d.q_total = draw_q_total + t;
+            d.shift = NULL;
+            apemost_hip_or_die(apemost_hip_reweight_resample(sampler, m->t0, m->t_count, m->g, r->betas_t[t], n_draws,
+                                                             draw_seed, &d), "reweight_resample");
+        }
+    }
     evaluated = 1;
 }
 
-/* writes reweight.bin and reweight.txt and frees everything (the mbar fold's end has dropped the device's store) */
+/* writes reweight.bin and reweight.txt, with APEMOST_RESAMPLE_DRAWS also resample.bin and the resampled dumps, and
+ * frees everything (the mbar fold's end has dropped the device's store) */
 void run_reweight_close(const run_fold_ctx *ctx) {
     run_reweight *r = &reweight;
     if (evaluated) {
+        const char *const *names = (const char *const *)get_params_descr(ctx->chains[0]);
         run_reweight_write(RUN_REWEIGHT_FILE, r);
-        run_reweight_write_text(RUN_REWEIGHT_TEXT, r, (const char *const *)get_params_descr(ctx->chains[0]));
+        run_reweight_write_text(RUN_REWEIGHT_TEXT, r, names);
+        if (n_draws > 0) {
+            unsigned int t;
+            run_resample_write(RUN_RESAMPLE_FILE, r, n_draws, draw_seed, draw_q_total, draw_index, draw_x);
+            for (t = 0; t < r->n_t; t++)
+                run_resample_write_dumps(r, t, n_draws, draw_x + (size_t)t * n_draws * r->n_cols, names);
+        }
     }
+    draws_free();
     run_reweight_free(r);
     is_open = evaluated = 0;
 }

@@ -46,6 +46,30 @@ reweight.bin (little-endian), version 1; it holds the sums, not the store:
     double   cross[n_ladders][n_t][n_cols (n_cols + 1) / 2]       (the upper triangle, row-major)
     uint64   hist[n_ladders][n_t][n_cols][nbins]
     uint64   q_total[n_ladders][n_t]
+
+Resampling (Reweight.resample, csrc/pt_resample.h): M equally weighted draws per ladder from the weighted sample of one
+target, for whatever the sums do not answer.  In integers alone, with sample n in stored order and the caller's uint64 u:
+
+    C_n = q_0 + ... + q_n,  Q = C_{N-1} = q_total;   a = Q div M,  b = Q mod M,  o = (u a) >> 64
+    p_m = m a + (m b) div M + o,  m = 0 .. M-1;   draw m is the smallest n with C_n > p_m
+
+systematic resampling with an integer offset: p is non-decreasing and below Q, a sample with q_n = 0 is never drawn and
+sample n is drawn floor(M q_n / Q) or ceil(M q_n / Q) times.  The draws come out in stored order (time-major): equally
+weighted, not exchangeable in order.  resample_numpy is the same rule on the host (np.cumsum in uint64, exact below
+2^63, and np.searchsorted): the same indices whenever the q agree.
+
+resample.bin (little-endian), version 1; one record per target:
+    char[8]  "APEMOSTS"
+    uint32   version, n_chains, n_ladders, n_cols, n_t, n_draws
+    int32    shift
+    uint32   0
+    uint64   n, thin, t0, t_count, u
+    int32    cols[16]                                             (the first n_cols; the rest 0)
+    n_t times:
+        double   beta_t
+        uint64   q_total[n_ladders]
+        uint32   index[n_ladders][n_draws]
+        double   x[n_ladders][n_draws][n_cols]
 """
 import ctypes as C
 import math
@@ -62,6 +86,10 @@ MAGIC = b"APEMOSTW"
 VERSION = 1
 _HEAD = struct.Struct("<8s6IiI4Q16i")
 MAX_COLS, MAX_BINS, MAX_TARGETS = 16, 4096, 64
+RESAMPLE_MAGIC = b"APEMOSTS"
+RESAMPLE_VERSION = 1
+_RESAMPLE_HEAD = struct.Struct("<8s6IiI5Q16i")
+MAX_DRAWS, MAX_DRAW_VALUES = 1 << 24, 1 << 26
 
 
 def shift_of(N):
@@ -72,6 +100,23 @@ def shift_of(N):
 def fixed_point(e, s):
     """q = (uint64) rint(ldexp(e, s))"""
     return np.rint(np.ldexp(e, s)).astype(np.uint64)
+
+
+def systematic_positions(Q, M, u):
+    """p_m = m a + (m b) div M + o, m = 0 .. M-1, with a = Q div M, b = Q mod M, o = (u a) >> 64: uint64 [M],
+    non-decreasing and below Q.  a, b and o are Python integers (u a has 128 bits); every term of p_m is below 2^63, so
+    the uint64 arithmetic over m is exact."""
+    Q, M, u = int(Q), int(M), int(u)
+    if not 1 <= M <= MAX_DRAWS:
+        raise ValueError("n_draws %d outside [1,2^24]" % M)
+    if not 0 <= u < 1 << 64:
+        raise ValueError("u is a uint64")
+    if not M <= Q < 1 << 63:
+        raise ValueError("Q = %d outside [n_draws, 2^63)" % Q)
+    a, b = divmod(Q, M)
+    o = (u * a) >> 64
+    m = np.arange(M, dtype=np.uint64)
+    return m * np.uint64(a) + (m * np.uint64(b)) // np.uint64(M) + np.uint64(o)
 
 
 def check_cols(cols, n_par):
@@ -219,13 +264,18 @@ class Reweight:
         (divide e by its ladder's sum): reweight with them whatever was kept of those rows"""
         mbar, g, t0, t_count = self._args(mbar, g, t0, t_count)
         bt = self._targets([beta])
+        if self._sampler is None:
+            return self._weights_numpy(mbar, g, t0, t_count, bt)
         e = np.zeros((t_count, self.n_chains))
         q = np.zeros((t_count, self.n_chains), dtype=np.uint64)
-        if self._sampler is not None:
-            s = self._sampler
-            capi.check(s.L.apemost_hip_reweight_weights(s._h, t0, t_count, g.ctypes.data_as(capi._dp), float(bt[0]),
-                                                        e.ctypes.data_as(capi._dp), q.ctypes.data_as(capi._up)))
-            return e, q
+        s = self._sampler
+        capi.check(s.L.apemost_hip_reweight_weights(s._h, t0, t_count, g.ctypes.data_as(capi._dp), float(bt[0]),
+                                                    e.ctypes.data_as(capi._dp), q.ctypes.data_as(capi._up)))
+        return e, q
+
+    def _weights_numpy(self, mbar, g, t0, t_count, bt):
+        e = np.zeros((t_count, self.n_chains))
+        q = np.zeros((t_count, self.n_chains), dtype=np.uint64)
         per = self.n_chains // self.n_ladders
         s = shift_of(t_count * per)
         for b in range(self.n_ladders):
@@ -233,6 +283,55 @@ class Reweight:
                 e[:, b * per:(b + 1) * per] = eb.reshape(t_count, per)
                 q[:, b * per:(b + 1) * per] = fixed_point(eb, s).reshape(t_count, per)
         return e, q
+
+    # -- resampling ------------------------------------------------------------------------------------------------------
+    def _draws(self, beta, n_draws, u, t0, t_count):
+        n_draws, u = int(n_draws), int(u)
+        if not 1 <= n_draws <= MAX_DRAWS:
+            raise ValueError("n_draws %d outside [1,2^24]" % n_draws)
+        if self.n_ladders * n_draws * self.n_cols > MAX_DRAW_VALUES:
+            raise ValueError("%d ladders x %d draws x %d columns are more than 2^26 values"
+                             % (self.n_ladders, n_draws, self.n_cols))
+        if not 0 <= u < 1 << 64:
+            raise ValueError("u is a uint64")
+        r = Resampled(self.cols, beta, u, n_draws, self.n_ladders, self.n_chains, self.n, self.thin, (t0, t_count))
+        r.shift = shift_of(t_count * (self.n_chains // self.n_ladders))
+        return r
+
+    def resample(self, mbar=None, beta=1.0, n_draws=4096, u=0, g=None, t0=None, t_count=None):
+        """the Resampled of n_draws equally weighted draws per ladder at the target `beta` (finite, >= 0) with the
+        offset word u (a uint64; a seed) under the Mbar's free energies: on the device where the store is there, else
+        in numpy"""
+        if self._sampler is None:
+            return self.resample_numpy(mbar, beta, n_draws, u, g, t0, t_count)
+        mbar, g, t0, t_count = self._args(mbar, g, t0, t_count)
+        bt = self._targets([beta])
+        r = self._draws(float(bt[0]), n_draws, u, t0, t_count)
+        s = self._sampler
+        shift = np.zeros(1, dtype=np.int32)
+        out = capi.ReweightDraws(index=r.index.ctypes.data_as(C.POINTER(C.c_uint32)), x=r.x.ctypes.data_as(capi._dp),
+                                 q_total=r.q_total.ctypes.data_as(capi._up),
+                                 shift=shift.ctypes.data_as(C.POINTER(C.c_int32)))
+        capi.check(s.L.apemost_hip_reweight_resample(s._h, t0, t_count, g.ctypes.data_as(capi._dp), float(bt[0]),
+                                                     r.n_draws, r.u, C.byref(out)))
+        assert int(shift[0]) == r.shift
+        return r
+
+    def resample_numpy(self, mbar=None, beta=1.0, n_draws=4096, u=0, g=None, t0=None, t_count=None):
+        """resample() on the host: q of evaluate_numpy's path, a uint64 cumsum and searchsorted"""
+        mbar, g, t0, t_count = self._args(mbar, g, t0, t_count)
+        bt = self._targets([beta])
+        r = self._draws(float(bt[0]), n_draws, u, t0, t_count)
+        _, q = self._weights_numpy(mbar, g, t0, t_count, bt)
+        per = self.n_chains // self.n_ladders
+        for b in range(self.n_ladders):
+            ladder = slice(b * per, (b + 1) * per)
+            c = np.cumsum(np.ascontiguousarray(q[:, ladder]).reshape(-1), dtype=np.uint64)
+            r.q_total[b] = c[-1]
+            r.index[b] = np.searchsorted(c, systematic_positions(int(c[-1]), r.n_draws, r.u), side="right")
+            for a in range(self.n_cols):
+                r.x[b, :, a] = np.ascontiguousarray(self.x[a, t0:t0 + t_count, ladder]).reshape(-1)[r.index[b]]
+        return r
 
 
 def weighted_bincount(bins, q, nbins):
@@ -405,6 +504,159 @@ class Reweighted:
         for w, a in zip(cls._WORDS, parts[3:]):
             setattr(r, w, a.reshape(getattr(r, w).shape).astype(getattr(r, w).dtype))
         return r
+
+
+class Resampled:
+    """n_draws equally weighted draws per ladder at one target, in stored order (time-major).  index, x and q_total
+    carry the ladder first; every estimator is [...] for one ladder and [n_ladders][...] for a batch."""
+
+    def __init__(self, cols, beta, u, n_draws, n_ladders, n_chains, n, thin, range_):
+        self.cols = np.ascontiguousarray(cols, dtype=np.int32)
+        self.beta, self.u, self.n_draws = float(beta), int(u), int(n_draws)
+        self.n_ladders, self.n_chains, self.n, self.thin = int(n_ladders), int(n_chains), int(n), int(thin)
+        self.range = (int(range_[0]), int(range_[1]))
+        self.shift = 0
+        self.index = np.zeros((self.n_ladders, self.n_draws), dtype=np.uint32)
+        self.x = np.zeros((self.n_ladders, self.n_draws, len(self.cols)))
+        self.q_total = np.zeros(self.n_ladders, dtype=np.uint64)
+
+    @property
+    def n_cols(self):
+        return len(self.cols)
+
+    @property
+    def per(self):
+        return self.n_chains // self.n_ladders
+
+    @property
+    def step(self):
+        """[n_ladders][n_draws]: the kept step a draw was stored at, t0 + index div K"""
+        return self.range[0] + self.index.astype(np.int64) // self.per
+
+    @property
+    def chain(self):
+        """[n_ladders][n_draws]: the sampler's chain a draw came from, ladder b's first chain being b K"""
+        return np.arange(self.n_ladders)[:, None] * self.per + self.index.astype(np.int64) % self.per
+
+    def _shape(self, a):
+        return a[0] if self.n_ladders == 1 else a
+
+    def counts(self):
+        """how often every sample of the range was drawn: [N], N = t_count K"""
+        N = self.range[1] * self.per
+        return self._shape(np.stack([np.bincount(i, minlength=N) for i in self.index]))
+
+    def mean(self):
+        """[n_cols]: the mean of the draws"""
+        return self._shape(self.x.mean(axis=1))
+
+    def cov(self):
+        """[n_cols][n_cols]: the covariance of the draws about their mean, over n_draws"""
+        d = self.x - self.x.mean(axis=1, keepdims=True)
+        return self._shape(np.einsum("bma,bmc->bac", d, d) / self.n_draws)
+
+    def sd(self):
+        return self._shape(self.x.std(axis=1))
+
+    def quantile(self, p, a, ladder=0):
+        """the p-quantile(s) of column slot a, exact from the sorted draws: the smallest draw v with at least a share p
+        of the draws <= v"""
+        v = np.sort(self.x[ladder, :, a])
+        p = np.asarray(p, dtype=np.float64)
+        if np.any(p < 0) or np.any(p > 1):
+            raise ValueError("a quantile is in [0, 1]")
+        return v[np.clip(np.ceil(p * self.n_draws).astype(np.int64) - 1, 0, self.n_draws - 1)]
+
+    def per_ladder(self):
+        """one Resampled per ladder of a batch"""
+        out = []
+        for b in range(self.n_ladders):
+            one = Resampled(self.cols, self.beta, self.u, self.n_draws, 1, self.per, self.n, self.thin, self.range)
+            one.shift = self.shift
+            one.index, one.x, one.q_total = self.index[b:b + 1].copy(), self.x[b:b + 1].copy(), self.q_total[b:b + 1].copy()
+            out.append(one)
+        return out
+
+    def _one(self):
+        if self.n_ladders != 1:
+            raise ValueError("a batch of %d ladders: take per_ladder() first" % self.n_ladders)
+
+    def text(self, names=None):
+        """per column one line `beta name mean sd median` of one ladder's draws, "%.15e", tab separated"""
+        self._one()
+        names = ["col%d" % c for c in self.cols] if names is None else list(names)
+        mean, sd = self.mean(), self.sd()
+        return "".join("%s\t%s\t%s\t%s\t%s\n" % (_fmt(self.beta), names[a], _fmt(float(mean[a])), _fmt(float(sd[a])),
+                                                 _fmt(float(self.quantile(0.5, a))))
+                       for a in range(self.n_cols))
+
+    def write_dumps(self, directory, names=None, t=0):
+        """one ladder's draws as the reference's text sample dumps: per column <name>-reweighted-<t>.dump, one "%.15e"
+        line per draw, the format of <name>-chain-0.prob.dump; returns the paths"""
+        import os
+        self._one()
+        names = ["col%d" % c for c in self.cols] if names is None else list(names)
+        paths = []
+        for a in range(self.n_cols):
+            paths.append(os.path.join(str(directory), "%s-reweighted-%d.dump" % (names[a], t)))
+            with open(paths[-1], "w") as f:
+                f.write("".join("%.15e\n" % v for v in self.x[0, :, a].tolist()))
+        return paths
+
+    def write(self, path):
+        Resampled.write_all(path, [self])
+
+    @staticmethod
+    def write_all(path, targets):
+        """resample.bin of the targets' draws: the same store, range, n_draws and u, one record per target"""
+        r = targets[0]
+        same = ("n_chains", "n_ladders", "n_draws", "shift", "n", "thin", "range", "u")
+        if any(getattr(o, w) != getattr(r, w) for o in targets for w in same) \
+                or any(o.cols.tobytes() != r.cols.tobytes() for o in targets):
+            raise ValueError("the targets of one file share the store, the range, n_draws and u")
+        cols = np.zeros(MAX_COLS, dtype=np.int32)
+        cols[:r.n_cols] = r.cols
+        with open(path, "wb") as f:
+            f.write(_RESAMPLE_HEAD.pack(RESAMPLE_MAGIC, RESAMPLE_VERSION, r.n_chains, r.n_ladders, r.n_cols, len(targets),
+                                        r.n_draws, r.shift, 0, r.n, r.thin, r.range[0], r.range[1], r.u, *cols.tolist()))
+            for o in targets:
+                f.write(struct.pack("<d", o.beta))
+                f.write(np.ascontiguousarray(o.q_total, dtype="<u8").tobytes())
+                f.write(np.ascontiguousarray(o.index, dtype="<u4").tobytes())
+                f.write(np.ascontiguousarray(o.x, dtype="<f8").tobytes())
+
+    @classmethod
+    def read_all(cls, path):
+        """the Resampled of every target of a resample.bin"""
+        with open(path, "rb") as f:
+            raw = f.read()
+        head = _RESAMPLE_HEAD.unpack_from(raw, 0) if len(raw) >= _RESAMPLE_HEAD.size else (b"",) * 2
+        if head[0] != RESAMPLE_MAGIC or head[1] != RESAMPLE_VERSION:
+            raise ValueError("%s: not a resample file of version %d" % (path, RESAMPLE_VERSION))
+        nc, L, k, nt, M, shift, _, n, thin, t0, t_count, u = head[2:14]
+        if not (1 <= k <= MAX_COLS and 1 <= nt <= MAX_TARGETS and 1 <= M <= MAX_DRAWS and L >= 1):
+            raise ValueError("%s: a header out of range" % path)
+        record = 8 + 8 * L + 4 * L * M + 8 * L * M * k
+        if _RESAMPLE_HEAD.size + nt * record != len(raw):
+            raise ValueError("%s: %d bytes, expected %d" % (path, len(raw), _RESAMPLE_HEAD.size + nt * record))
+        out, off = [], _RESAMPLE_HEAD.size
+        for _ in range(nt):
+            r = cls(np.array(head[14:14 + k]), struct.unpack_from("<d", raw, off)[0], u, M, L, nc, n, thin, (t0, t_count))
+            r.shift = shift
+            off += 8
+            r.q_total = np.frombuffer(raw, dtype="<u8", count=L, offset=off).astype(np.uint64)
+            off += 8 * L
+            r.index = np.frombuffer(raw, dtype="<u4", count=L * M, offset=off).astype(np.uint32).reshape(L, M)
+            off += 4 * L * M
+            r.x = np.frombuffer(raw, dtype="<f8", count=L * M * k, offset=off).astype(np.float64).reshape(L, M, k)
+            off += 8 * L * M * k
+            out.append(r)
+        return out
+
+    @classmethod
+    def read(cls, path, t=0):
+        """target t of a resample.bin"""
+        return cls.read_all(path)[t]
 
 
 def _fmt(v):

@@ -703,6 +703,27 @@ class HipSampler:
         assert rw.cols.tobytes() == self._rw_cols.tobytes() and rw.n <= self._mb_capacity
         capi.check(self.L.apemost_hip_reweight_set(self._h, C.byref(rw.view())))
 
+    def reweight_resample(self, g, beta=1.0, n_draws=4096, u=0, t0=0, t_count=None):
+        """n_draws equally weighted draws per ladder at the target `beta` from the stores as they are on the device,
+        under the free energies g [n_chains] over the kept steps [t0, t0 + t_count) (None: to the last stored): a
+        Resampled, without the copy of the store that reweight() makes for Reweight.resample"""
+        from .reweight import Reweight
+        n = np.zeros(1, dtype=np.uint64)
+        capi.check(self.L.apemost_hip_reweight_get(self._h, C.byref(capi.ReweightView(n=n.ctypes.data_as(capi._up)))))
+        head = Reweight(np.zeros((len(self._rw_cols), 0, self.n_chains)), self._rw_cols, n_ladders=self.n_ladders,
+                        thin=self._mb_thin)
+        t_count = int(n[0]) - t0 if t_count is None else t_count
+        r = head._draws(float(beta), n_draws, u, t0, t_count)
+        r.n = int(n[0])
+        g = np.ascontiguousarray(g, dtype=np.float64).reshape(self.n_chains)
+        shift = np.zeros(1, dtype=np.int32)
+        out = capi.ReweightDraws(index=r.index.ctypes.data_as(C.POINTER(C.c_uint32)), x=r.x.ctypes.data_as(capi._dp),
+                                 q_total=r.q_total.ctypes.data_as(capi._up),
+                                 shift=shift.ctypes.data_as(C.POINTER(C.c_int32)))
+        capi.check(self.L.apemost_hip_reweight_resample(self._h, t0, t_count, g.ctypes.data_as(capi._dp), float(beta),
+                                                        r.n_draws, r.u, C.byref(out)))
+        return r
+
     def reweight_end(self):
         capi.check(self.L.apemost_hip_reweight_end(self._h))
 

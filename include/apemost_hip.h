@@ -955,6 +955,32 @@ int apemost_hip_reweight_evaluate(apemost_hip_sampler *s, uint64_t t0, uint64_t 
 int apemost_hip_reweight_weights(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, const double *g, double beta_t,
                                  double *host_e, uint64_t *host_q);
 
+/* Resampling: n_draws equally weighted draws per ladder from the weighted sample of one target, for whatever the sums
+ * above do not answer (a corner plot, a credible region, the reference's own histogram and peak tools).  With q_n the
+ * integers above, sample n = 0 .. N-1 in mbar's stored order, M = n_draws and the caller's u (csrc/pt_resample.h):
+ *   C_n = q_0 + ... + q_n                          (uint64; Q = C_{N-1} = q_total < 2^63)
+ *   a = Q div M,  b = Q mod M,  o = mulhi64(u, a)  (the high 64 bits of the 128-bit product; 0 <= o < a)
+ *   p_m = m a + (m b) div M + o,  m = 0 .. M-1     (non-decreasing, below Q)
+ *   draw m is the smallest n with C_n > p_m:
+ * systematic resampling with an integer offset, in 64-bit integers alone (Q >= 2^shift >= 2^34 because the largest e
+ * is 1, so a >= 2^10; m b < 2^48).  A sample with q_n = 0 is never drawn; sample n is drawn floor(M q_n / Q) or
+ * ceil(M q_n / Q) times.  No floating point and no atomics: the same index on any grid.  The draws come out in stored
+ * order (time-major, the chain fastest): they are equally weighted, not exchangeable in order. */
+typedef struct {
+    uint32_t *index;    /* [n_ladders][n_draws]: sample n of the ladder within the range; step t0 + n / K, chain n % K */
+    double *x;          /* [n_ladders][n_draws][n_cols] */
+    uint64_t *q_total;  /* [n_ladders] */
+    int32_t *shift;     /* [1] */
+} apemost_hip_reweight_draws;   /* host arrays; any pointer may be NULL (that part is skipped) */
+/* the draws of the target beta_t (finite, >= 0) under the free energies g [n_chains]; q_total is reweight_evaluate's
+ * for that target on the bits.  APEMOST_HIP_ERR_INVALID, before any device work and naming the offender, for a NULL g
+ * or out, n_draws outside [1, 2^24] and n_ladders * n_draws * n_cols above 2^26; then the refusals of
+ * reweight_evaluate.  The first call of a fold allocates 8 bytes per stored sample, which the fold's end frees.
+ * Synchronises. */
+int apemost_hip_reweight_resample(apemost_hip_sampler *s, uint64_t t0, uint64_t t_count, const double *g,
+                                  double beta_t, uint32_t n_draws, uint64_t u,
+                                  const apemost_hip_reweight_draws *out);
+
 /* ---- on-device autocorrelation: lag sums, integrated times, effective sample size ---------------
  * How many independent samples a run holds: what the autocorrelation function of sample columns needs, accumulated
  * from the sample rows while they are still on the device.  A series is one (kept chain, column) pair, series
